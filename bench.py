@@ -23,6 +23,7 @@ FLOP_PER_IMAGE = 1.4264e11       # algorithmic FLOPs per image
 BYTES_PER_STEP_B24 = 28.46e9     # algorithmic HBM bytes per B=24 step
 PEAK_F32_TFLOPS = 157.3          # MI355X_MICROARCH.md: fp32 vector = f32-MFMA peak
 PEAK_HBM_GBS = 8000.0
+DUMP_BYTES = 60 * 10**6          # --dump-outputs in all: under 64 MB with the .npy headers
 
 
 def parse():
@@ -50,7 +51,14 @@ def parse():
     ap.add_argument("--math", default="f32", choices=["f32", "bf16x3", "bf16x2", "bf16", "bf16p"],
                     help="matrix products of the conv GEMMs: native fp32 MFMA (default), or fp32 operands split into 3 / 2 "
                          "bf16 planes on the bf16 MFMA (DESIGN.md section 9); f32 runs also report bf16x3 beside the value")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (losses, generated images, CA_NET "
+                         "mu / logvar, embedding gradient, updated G / EMA / D weights) as DIR/<name>.npy, float32, "
+                         "%d MB at most (a fixed sample of the larger arrays)" % (DUMP_BYTES // 10**6))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def synthetic_batch(B, dev, seed):
@@ -62,6 +70,34 @@ def synthetic_batch(B, dev, seed):
         batch["real"].append(torch.rand(B, 3, s, s, device=dev, generator=g) * 2 - 1)
         batch["wrong"].append(torch.rand(B, 3, s, s, device=dev, generator=g) * 2 - 1)
     return batch, g
+
+
+def step_outputs(tr, out, emb):
+    """What a caller of condGANTrainer.train_step holds after a step, in a fixed order: the returned losses, the generator's
+    images and CA_NET statistics, the gradient w.r.t. the embedding, and the updated flat weights (G, its EMA, every D)."""
+    arrays = [("losses", torch.stack([v.detach().float().reshape(()) for v in out]))]
+    arrays += [("fake_imgs_%d" % f.shape[-1], f) for f in tr.fake_imgs]
+    arrays += [("mu", tr.mu), ("logvar", tr.logvar), ("emb_grad", emb.grad),
+               ("netG", tr.flatG.p), ("netG_ema", tr.flatG.avg)]
+    arrays += [("netD%d" % i, f.p) for i, f in enumerate(tr.flatsD)]
+    return arrays
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """Write every (name, tensor) as out_dir/<name>.npy in float32.  Each array may take an equal share of `budget`; a
+    larger one is replaced by a fixed sample: its elements at sorted random flat indices drawn from a generator seeded by
+    the name, so two runs, or two builds, with the same arguments write the same elements."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = budget // 4 // len(arrays)
+    for name, t in arrays:
+        t = t.detach()
+        if t.numel() > cap:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 PROFILED_JSON = os.path.join(ROOT, "profiles", "roofline_profiled.json")
@@ -377,12 +413,14 @@ def main():
                               descending=True)[0]
         cap_lens = (n_frames // 64).tolist()
 
+    last = {}
+
     def one_step():
         noise.normal_(generator=gen)
         eps.normal_(generator=gen)
         if encoder is not None:
             batch["emb"] = encoder.extract_feature(mel, cap_lens)
-        emb = batch["emb"].detach().requires_grad_(True)
+        emb = last["emb"] = batch["emb"].detach().requires_grad_(True)
         return tr.train_step(batch["real"], batch["wrong"], emb, batch["labels"], noise, eps)
 
     def note(msg):
@@ -415,6 +453,10 @@ def main():
     losses = [float(v) for v in out]
     if not all(abs(v) < 1e6 for v in losses):
         raise RuntimeError("non-finite losses after the timed region: %s" % losses)
+    if args.dump_outputs and rank == 0:
+        # before anything below runs another step on these networks
+        dump_outputs(args.dump_outputs, step_outputs(tr, out, last["emb"]))
+        note("outputs of the last timed step written to %s" % args.dump_outputs)
 
     # executed work of ONE step, from the descriptors of the launches themselves (outside the timed region)
     graph_state, tr._graph = tr._graph, None   # the logged step is enqueued from Python (a graph replay runs no host code)

@@ -1,7 +1,7 @@
 """Back-to-back timing of the BatchNorm finalize kernels (forward statistics, backward sums) for the partial counts the step
 produces (dev tool, GPU box only): 8 - 12 us each including the launch boundary, 23 us for 4608 partial rows."""
 import ctypes, os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from speech_to_image_translation_without_text_amd import ops
 from speech_to_image_translation_without_text_amd._lib import ptr, stream, check
 lib = ops._lib_ready(); dev = torch.device("cuda:0")

@@ -1,5 +1,5 @@
 import os, sys, torch
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from speech_to_image_translation_without_text_amd import ops
 from speech_to_image_translation_without_text_amd._lib import CONV_K4S2
 dev = torch.device("cuda:0")

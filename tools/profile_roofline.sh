@@ -4,7 +4,7 @@
 # usage: tools/profile_roofline.sh <tag> <math> <batch> [conv|wgrad] [kernel-name-substring] [fetch scale]
 #        -> gpurun_out/roofline_<tag>/{stats,fetch,write}/...
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; MATH=$2; B=$3; WHICH=${4:-conv}; KSUB=$5; FSCALE=$6
 OUT=$R/gpurun_out/roofline_$TAG
 mkdir -p $OUT && cd /tmp && export TMPDIR=/tmp

@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 kernel statistics of a bench.py run (GPU box).  usage: tools/profile_step.sh <outdir-under-gpurun_out> <steps+warmup+1> "<title>" <bench args...>
 set -o pipefail
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/$1; NSTEPS=$2; TITLE=$3; shift 3
 mkdir -p $OUT && cd /tmp && export TMPDIR=/tmp
 timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o p -- python3 $R/bench.py "$@" > $OUT/run.log 2>&1

@@ -2,7 +2,8 @@
 step of tests/test_parity_gpu.py::test_ragged_batch_full_train_step twice, the second time after filling and freeing 4 GiB
 with NaN / 1e30 / 0, and compares every gradient and updated weight bitwise (dev tool, GPU box only)."""
 import sys, os, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from helpers import *  # noqa
 import test_parity_gpu as tp
 from speech_to_image_translation_without_text_amd import ops, trainer as T, _lib
