@@ -17,6 +17,7 @@ CONV_K1, CONV_K3S1, CONV_K4S2, TCONV_K4S2, CONV_1D = 0, 1, 2, 3, 4
 ACT_NONE, ACT_GLU, ACT_LRELU, ACT_TANH, ACT_RELU = 0, 1, 2, 3, 4
 PACK_PLAIN, PACK_UPFOLD = 0, 1
 DT_F32, DT_BF16 = 0, 1
+POOL_MAX3S2, POOL_AVG3S1, POOL_GLOBAL = 0, 1, 2
 ABI_VERSION = 4
 
 c_int, c_float, c_void_p, c_size_t, c_ll = (ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
@@ -27,6 +28,11 @@ class ConvDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("kind", "B", "H", "W", "Cx", "Cc", "N", "wmode", "flip", "wR",
                                      "ldw", "act", "stats", "ldy", "groups", "nosplit", "kw", "stride", "pad",
                                      "tile_rows", "in_act", "in_groups")]
+
+
+class Conv2dDesc(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("B", "H", "W", "C", "ldx", "N", "kh", "kw", "sh", "sw", "ph", "pw", "Ho", "Wo",
+                                     "ldy", "coff", "relu", "tile")]
 
 
 class WgradDesc(ctypes.Structure):
@@ -131,6 +137,12 @@ _SIGNATURES = {
     "s2i_plan_create": (c_int, [P, ctypes.POINTER(P), ctypes.POINTER(c_int)]),
     "s2i_plan_replay": (c_int, [P, P]),
     "s2i_plan_destroy": (c_int, [P]),
+    "s2i_conv2d_plan": (c_int, [ctypes.POINTER(Conv2dDesc)]),
+    "s2i_conv2d_weight_elems": (c_size_t, [ctypes.POINTER(Conv2dDesc)]),
+    "s2i_conv2d_forward": (c_int, [ctypes.POINTER(Conv2dDesc), P, P, P, P, P]),
+    "s2i_pool2d": (c_int, [c_int, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
+    "s2i_inception_prep": (c_int, [P, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll, P, c_int, c_int, P]),
+    "s2i_softmax_rows": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

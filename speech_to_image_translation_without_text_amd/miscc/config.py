@@ -47,6 +47,7 @@ def _defaults():
             "DISCRIMINATOR_LR": 2e-4, "GENERATOR_LR": 2e-4, "FLAG": True, "NET_G": "", "NET_D": "",
             "COEFF": {"KL": 2.0, "CAL_LOSS": 0.0, "UNCOND_LOSS": 0.0, "COLOR_LOSS": 0.0},
             "LOG_INTERVAL": 10,
+            "INCEPTION_WEIGHTS": "",   # local Inception-v3 state_dict file: '' = no IS / FID / NLPP during training
         },
         "GAN": {"EMBEDDING_DIM": 128, "DF_DIM": 64, "GF_DIM": 64, "Z_DIM": 100,
                 "NETWORK_TYPE": "default", "R_NUM": 2, "B_CONDITION": True},

@@ -380,12 +380,43 @@ class D_NET1024(_DNet):
 
 
 class INCEPTION_V3(nn.Module):
-    """Placeholder for the reference's Inception-v3 scorer (model.py:17-109), which downloads weights
-    at construction and needs torchvision: evaluation metrics are outside the train-step path
-    (SURVEY.md §2).  Importable so `from model import ... INCEPTION_V3` works; not callable."""
+    """The reference's Inception-v3 scorer (model.py:17-109): forward(images) -> (softmax (B, 1000), pool3 (B, 2048)).
 
-    def __init__(self):
+    `weights` is a local torchvision-layout Inception3 state_dict file (e.g. inception_v3_google-1a9a5a14.pth) or an
+    already loaded dict; the reference downloads that file at construction, nothing is downloaded here.  The network runs
+    on the gfx950 kernels (inception.py), prepared on the first forward's device.  Without weights the module is only
+    importable, as before: forward raises."""
+
+    def __init__(self, weights=None):
         super().__init__()
+        self.state = None
+        if weights is not None:
+            from . import inception
+            sd = weights if isinstance(weights, dict) else torch.load(weights, map_location="cpu", weights_only=True)
+            inception.check_state_dict(sd)
+            self.state = {k: v for k, v in sd.items() if not k.startswith("AuxLogits.")}
+        self._net = None
 
-    def forward(self, x):
-        raise RuntimeError("INCEPTION_V3 (IS/FID scoring) is out of scope of the MI355X train-step path")
+    def net(self, device):
+        """The folded, packed network on `device` (built once)."""
+        if self.state is None:
+            raise RuntimeError("INCEPTION_V3 has no weights: pass INCEPTION_V3(weights='inception_v3_google-1a9a5a14.pth')")
+        if self._net is None or self._net.device != torch.device(device):
+            from . import _lib, inception
+            _lib.require_device()
+            self._net = inception.InceptionNet(self.state, device)
+        return self._net
+
+    def forward(self, *images):
+        """images: one or more (B_i, 3, H, W) fp32 tensors in [-1, 1] on the device, scored as their concatenation."""
+        if self.state is None:
+            raise RuntimeError("INCEPTION_V3 (IS/FID scoring) needs weights: INCEPTION_V3(weights=<local .pth file>)")
+        dev = images[0].device
+        if dev.type != "cuda":
+            raise RuntimeError("INCEPTION_V3 runs on the gfx950 kernels only: the images are on %s" % dev)
+        rows = sum(t.shape[0] for t in images)
+        soft = torch.empty(rows, 1000, device=dev)
+        pool3 = torch.empty(rows, 2048, device=dev)
+        with torch.no_grad():
+            self.net(dev).run([t.detach() for t in images], soft, pool3)
+        return soft, pool3

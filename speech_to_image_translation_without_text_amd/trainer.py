@@ -14,13 +14,17 @@ What is built differently (MI355X-first):
   * the G update does not compute (and never reduces) the discriminators' weight gradients the
     reference's backward produces and then discards (trainer.py:385 zeroes them);
   * per-replica BatchNorm statistics and per-replica class-aware loss, as in the reference's DDP.
-The Inception-v3 forwards, IS/FID and image dumps of the reference loop are evaluation-side and out
-of scope; the loop here runs the update and the checkpoint layout only.
+The reference's quality metrics are opt-in (TRAIN.INCEPTION_WEIGHTS or enable_inception): the Inception-v3 pass over
+each step's fake and real 256 px images runs on the gfx950 kernels (inception.py) into device buffers, and every snapshot
+with >= 500 collected batches reports the Inception score, NLPP and FID (trainer.py:563-565, 603-629); the image dumps
+of the reference loop are not reproduced.
 """
+import json
 import os
 import time
 from copy import deepcopy
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -44,6 +48,63 @@ def compute_mean_covariance(img):
 
 def KL_loss(mu, logvar):
     return ops.KLLoss.apply(mu, logvar)
+
+
+# ---- GAN quality metrics (trainer.py:88-159), host float64 -------------------------------------------------------------
+def compute_inception_score(predictions, num_splits=1):
+    """exp(E_x KL(p(y|x) || p(y))) per split of the softmax rows; (mean, std) over the splits."""
+    predictions = np.asarray(predictions, dtype=np.float64)
+    scores = []
+    for i in range(num_splits):
+        istart = i * predictions.shape[0] // num_splits
+        iend = (i + 1) * predictions.shape[0] // num_splits
+        part = predictions[istart:iend, :]
+        kl = part * (np.log(part) - np.log(np.expand_dims(np.mean(part, 0), 0)))
+        kl = np.mean(np.sum(kl, 1))
+        scores.append(np.exp(kl))
+    return np.mean(scores), np.std(scores)
+
+
+def _trace_sqrtm_product(s1, s2):
+    """trace(sqrtm(s1 @ s2)) for symmetric positive semi-definite s1, s2: s1 @ s2 is similar to
+    sqrt(s1) @ s2 @ sqrt(s1), which is symmetric PSD, so the trace is the sum of the square roots of its eigenvalues
+    (rounding-negative ones count as 0, as the real part of scipy's sqrtm does)."""
+    l, u = np.linalg.eigh(s1)
+    r = (u * np.sqrt(np.clip(l, 0.0, None))) @ u.T
+    m = r @ s2 @ r
+    ev = np.linalg.eigvalsh((m + m.T) * 0.5)
+    return float(np.sum(np.sqrt(np.clip(ev, 0.0, None))))
+
+
+def compute_frethet_distance(predictions_g, predictions_r, eps=1e-6):
+    """Frechet distance between Gaussians fitted to two sets of pool3 rows (the reference's spelling and return value:
+    (distance, [{'mu', 'sigma'} x 2]), where the reference stores mu_g in both entries)."""
+    predictions_g = np.asarray(predictions_g, dtype=np.float64)
+    predictions_r = np.asarray(predictions_r, dtype=np.float64)
+    mu1, sigma1 = np.atleast_1d(np.mean(predictions_g, axis=0)), np.atleast_2d(np.cov(predictions_g, rowvar=False))
+    mu2, sigma2 = np.atleast_1d(np.mean(predictions_r, axis=0)), np.atleast_2d(np.cov(predictions_r, rowvar=False))
+    assert mu1.shape == mu2.shape, 'Training and test mean vectors have different lengths'
+    assert sigma1.shape == sigma2.shape, 'Training and test covariances have different dimensions'
+    diff = mu1 - mu2
+    tr_covmean = _trace_sqrtm_product(sigma1, sigma2)
+    if not np.isfinite(tr_covmean):
+        print('fid calculation produces singular product; adding %s to diagonal of cov estimates' % eps)
+        offset = np.eye(sigma1.shape[0]) * eps
+        tr_covmean = _trace_sqrtm_product(sigma1 + offset, sigma2 + offset)
+    data = [{'mu': mu1, 'sigma': sigma1}, {'mu': mu1, 'sigma': sigma2}]
+    return (diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * tr_covmean), data
+
+
+def negative_log_posterior_probability(predictions, num_splits=1):
+    """-log max_y p(y|x), averaged per split; (mean, std) over the splits."""
+    predictions = np.asarray(predictions, dtype=np.float64)
+    scores = []
+    for i in range(num_splits):
+        istart = i * predictions.shape[0] // num_splits
+        iend = (i + 1) * predictions.shape[0] // num_splits
+        part = predictions[istart:iend, :]
+        scores.append(np.mean(-1. * np.log(np.max(part, 1))))
+    return np.mean(scores), np.std(scores)
 
 
 def weights_init(m):
@@ -255,6 +316,12 @@ class condGANTrainer(object):
         self._g_pass = []
         if os.environ.get("S2I_GRAPH", "0") == "1":
             self.enable_graph()
+        # Inception-v3 scoring (off by default): per step, (softmax, pool3) device rows of [fake; real]
+        self.inception_model = None
+        self.inception_min_batches = 500      # trainer.py:605: metrics once this many batches are collected
+        self._inception_rows = []
+        if cfg.TRAIN.INCEPTION_WEIGHTS:
+            self.enable_inception(cfg.TRAIN.INCEPTION_WEIGHTS)
 
     def _make_d_streams(self):
         """One stream per discriminator, all at the default priority.  (Round 2 gave the largest discriminator's stream the
@@ -669,7 +736,64 @@ class condGANTrainer(object):
             txt_embedding.grad = s['emb'].grad.clone()     # the static gradient buffer is overwritten by the next replay
         return tuple(st['outs'])
 
+    # -- GAN quality metrics (trainer.py:217-232, 563-565, 603-629) ------------------------------------------------------
+    def enable_inception(self, weights):
+        """Score every step's fake_imgs[-1] and real_imgs[-1] with Inception-v3 (`weights`: a local torchvision-layout
+        state_dict file, a loaded dict, or an INCEPTION_V3).  The pass runs after the step on the same stream, as one
+        stacked batch, into device buffers: no host synchronisation until a snapshot scores them.  With data parallelism
+        only rank 0 runs it, so the metrics describe rank 0's shard of the data."""
+        self.inception_model = weights if isinstance(weights, INCEPTION_V3) else INCEPTION_V3(weights)
+        self._inception_rows = []
+
+    def _inception_pass(self, real):
+        if self.distributed and torch.distributed.get_rank() != 0:
+            return
+        fake = self.fake_imgs[-1].detach()
+        real = real.detach()
+        imgs = [t if t.dtype == torch.float32 else t.float() for t in (fake, real)]
+        rows = fake.shape[0] + real.shape[0]
+        soft = torch.empty(rows, 1000, device=fake.device)
+        pool3 = torch.empty(rows, 2048, device=fake.device)
+        self.inception_model.net(fake.device).run(imgs, soft, pool3)
+        self._inception_rows.append((fake.shape[0], soft, pool3))
+
+    def inception_arrays(self):
+        """The collected rows on the host as float64: (predictions_g, predictions_r, activate_g, activate_r)."""
+        pg, pr, ag, ar = [], [], [], []
+        for b, soft, pool3 in self._inception_rows:
+            soft, pool3 = soft.cpu().double().numpy(), pool3.cpu().double().numpy()
+            pg.append(soft[:b]), pr.append(soft[b:]), ag.append(pool3[:b]), ar.append(pool3[b:])
+        cat = np.concatenate
+        return cat(pg, 0), cat(pr, 0), cat(ag, 0), cat(ar, 0)
+
+    def score_inception(self, count):
+        """At a snapshot: with >= inception_min_batches collected batches, IS (10 splits), NLPP (10 splits) and FID of fake
+        vs real pool3; printed, appended as one JSON line to <output_dir>/Log/metrics.jsonl, and the buffers cleared.
+        Returns the record, or None when nothing was scored."""
+        if self.inception_model is None or len(self._inception_rows) < self.inception_min_batches:
+            return None
+        n = len(self._inception_rows)
+        predictions_g, _, activate_g, activate_r = self.inception_arrays()
+        self._inception_rows = []
+        mean, std = compute_inception_score(predictions_g, 10)
+        mean_nlpp, std_nlpp = negative_log_posterior_probability(predictions_g, 10)
+        fid, _ = compute_frethet_distance(activate_g, activate_r)
+        rec = dict(count=int(count), batches=n, images=int(predictions_g.shape[0]), inception_mean=float(mean),
+                   inception_std=float(std), nlpp_mean=float(mean_nlpp), nlpp_std=float(std_nlpp), fid=float(fid))
+        print('[%d] Inception score %.4f +- %.4f  NLPP %.4f +- %.4f  FID %.4f (%d images)'
+              % (count, mean, std, mean_nlpp, std_nlpp, fid, rec['images']))
+        if getattr(self, 'log_dir', None):
+            with open(os.path.join(self.log_dir, 'metrics.jsonl'), 'a') as f:
+                f.write(json.dumps(rec) + '\n')
+        return rec
+
     def train_step(self, real_imgs, wrong_imgs, txt_embedding, class_labels, noise, eps=None):
+        out = self._dispatch_step(real_imgs, wrong_imgs, txt_embedding, class_labels, noise, eps)
+        if self.inception_model is not None:
+            self._inception_pass(real_imgs[-1])
+        return out
+
+    def _dispatch_step(self, real_imgs, wrong_imgs, txt_embedding, class_labels, noise, eps=None):
         st = self._graph
         if st is not None and not self.distributed and torch.cuda.is_available() and self.d_streams:
             if st['graphs'] is not None:
@@ -759,6 +883,7 @@ class condGANTrainer(object):
                 count += 1
                 if count % cfg.TRAIN.SNAPSHOT_INTERVAL == 0:
                     self.save(count)
+                    self.score_inception(count)
             if errD_total is not None and self.gpus[0] == 0:
                 print('[%d/%d][%d] Loss_D: %.2f Loss_G: %.2f Loss_KL: %.2f Time: %.2fs'
                       % (epoch, self.max_epoch, self.num_batches, errD_total.item(), errG_total.item(),
