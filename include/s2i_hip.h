@@ -470,6 +470,39 @@ int s2i_inception_prep(const float* img, int B, int Hin, int Win, long long sb, 
 /* nn.Softmax(dim=1) of `rows` rows of `cols` logits (row strides ldx, ldy) */
 int s2i_softmax_rows(const float* x, int rows, int cols, int ldx, float* y, int ldy, void* stream);
 
+/* ---- speech front end: WAV samples -> log-mel (Audio_to_Image/utils.py:292-340, load_one_audio_file) ---------------
+ * sr 16 kHz, n_fft = win_length = 400, hop 160, symmetric Hamming window, center=True with reflect padding, 40 Slaney mel
+ * bands from 20 Hz, power_to_db(ref=np.max, amin=1e-10, top_db=80), 0 dB fill (or truncation) to T frames.
+ * A batch is a ragged flat fp32 sample buffer: utterance b is x[offsets[b] .. offsets[b] + lens[b]), lens[b] >= 1 (the
+ * reference turns an empty file into 200 zeros; the caller does the same); it has n_frames = 1 + lens[b] / 160 frames.
+ * The sequence is s2i_signal_mean, s2i_logmel_power, s2i_logmel_finish on one stream; the caller owns every buffer. */
+#define S2I_LOGMEL_NFFT          400
+#define S2I_LOGMEL_HOP           160
+#define S2I_LOGMEL_NMEL          40
+#define S2I_LOGMEL_TILE_FRAMES   64  /* frames per entry of the tile table                                        */
+#define S2I_LOGMEL_BFT           0   /* logmel_finish layout: (B, 40, T), the reference's array                   */
+#define S2I_LOGMEL_NHWC          1   /* logmel_finish layout: [B][1][T][40], the layout CNNRNN computes in          */
+
+/* floats of the packed DFT basis (400 x 416, window folded in; 16-byte aligned).  Column pair q of 16-wide pair tile
+   t = q / 16 has a cos column (N-tile 2t) and a sin column (N-tile 2t + 1): (w_n cos(2 pi n q / 400),
+   -w_n sin(2 pi n q / 400)) for q = 1..199, (w_n, w_n cos(pi n)) for q = 0 (bins 0 and 200), zero for q = 200..207.
+   Element (n, column c of N-tile nt) is stored at ((n / 16 * 26 + nt) * 64 + (n % 4) * 16 + c) * 4 + (n % 16) / 4. */
+size_t s2i_logmel_basis_elems(void);
+/* mean[b] = mean of utterance b (y - y.mean(), utils.py:318); also sets maxbits[b] = 0 for s2i_logmel_power */
+int s2i_signal_mean(const float* x, const long long* offsets, const int* lens, int B, float* mean, unsigned* maxbits,
+                    void* stream);
+/* Mel power of every frame (utils.py:319-327: pre-emphasis, librosa.stft, |.|^2, mel_basis . spec).  tiles [ntiles][2]
+   holds (b, first frame) for every 64-frame tile of every utterance; melbank [40][201] is the fp32 mel filter bank and
+   mel_range [40][2] each filter's nonzero bin range [lo, hi).  melpow [B][T][40] receives frames < T; maxbits[b]
+   receives the bits of the largest mel power over ALL frames of utterance b (power_to_db's ref). */
+int s2i_logmel_power(const float* x, const long long* offsets, const int* lens, int B, const float* mean,
+                     const float* basis, const float* melbank, const int* mel_range, const int* tiles, int ntiles,
+                     int T, float* melpow, unsigned* maxbits, void* stream);
+/* power_to_db(ref=max, top_db=80) and the 0 dB fill to T (utils.py:328-338) into `out` in S2I_LOGMEL_BFT or
+   S2I_LOGMEL_NHWC layout */
+int s2i_logmel_finish(const float* melpow, const unsigned* maxbits, const int* lens, int B, int T, int layout,
+                      float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

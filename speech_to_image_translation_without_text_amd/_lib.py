@@ -18,6 +18,8 @@ ACT_NONE, ACT_GLU, ACT_LRELU, ACT_TANH, ACT_RELU = 0, 1, 2, 3, 4
 PACK_PLAIN, PACK_UPFOLD = 0, 1
 DT_F32, DT_BF16 = 0, 1
 POOL_MAX3S2, POOL_AVG3S1, POOL_GLOBAL = 0, 1, 2
+LOGMEL_BFT, LOGMEL_NHWC = 0, 1
+LOGMEL_TILE_FRAMES = 64
 ABI_VERSION = 4
 
 c_int, c_float, c_void_p, c_size_t, c_ll = (ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
@@ -143,6 +145,10 @@ _SIGNATURES = {
     "s2i_pool2d": (c_int, [c_int, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
     "s2i_inception_prep": (c_int, [P, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll, P, c_int, c_int, P]),
     "s2i_softmax_rows": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
+    "s2i_logmel_basis_elems": (c_size_t, []),
+    "s2i_signal_mean": (c_int, [P, P, P, c_int, P, P, P]),
+    "s2i_logmel_power": (c_int, [P, P, P, c_int, P, P, P, P, P, c_int, c_int, P, P, P]),
+    "s2i_logmel_finish": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

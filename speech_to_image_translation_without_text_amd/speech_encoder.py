@@ -122,13 +122,33 @@ class CNNRNN(nn.Module):
         reference requires.  Returns (words_emb (B, D*H, T/64), sent_emb (B, nsent*D))."""
         if self.training:
             raise _lib.S2IError("CNNRNN: only the inference (.eval()) path is built on the MI355X kernels")
-        lib = _lib.load()
+        _lib.load()
         _lib.require_device()
         if x.dim() == 4:
             x = x[:, 0]
         B, F_, T = x.shape
+        return self._encode(ops.ToNHWC.apply(x.reshape(B, F_, 1, T).contiguous(), F_), cap_lens)  # [B, 1, T, 40]
+
+    def extract_feature_nhwc(self, x, lens):
+        return self.forward_nhwc(x, lens)[1]
+
+    @torch.no_grad()
+    def forward_nhwc(self, x, cap_lens):
+        """forward() on log-mel already laid out NHWC, [B, 1, T, 40] (audio.log_mel(..., layout="nhwc")): the same
+        network without the layout conversion.  Returns (words_emb, sent_emb) as forward does."""
+        if self.training:
+            raise _lib.S2IError("CNNRNN: only the inference (.eval()) path is built on the MI355X kernels")
+        _lib.load()
+        _lib.require_device()
+        if x.dim() != 4 or x.shape[1] != 1 or x.shape[3] != self.Conv[1][0].kernel_size[0]:
+            raise _lib.S2IError("CNNRNN.forward_nhwc: expected [B, 1, T, %d], got %s"
+                                % (self.Conv[1][0].kernel_size[0], tuple(x.shape)))
+        return self._encode(x.contiguous(), cap_lens)
+
+    def _encode(self, h, cap_lens):
+        lib = _lib.load()
+        B = h.shape[0]
         prep = self._prepare()
-        h = ops.ToNHWC.apply(x.reshape(B, F_, 1, T).contiguous(), F_)  # [B, 1, T, 40]
         for layer in prep["layers"]:
             if layer[0] == "pool":
                 Bh, Hh, Wh, Ch = h.shape
