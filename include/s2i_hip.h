@@ -234,7 +234,8 @@ int s2i_conv_forward_dt(const s2i_conv_desc* d, const void* x, int x_dtype, cons
 size_t s2i_wgrad_workspace_bytes_dt(const s2i_wgrad_desc* d, int a_dtype, int g_dtype);
 int s2i_conv_wgrad_dt(const s2i_wgrad_desc* d, const void* a, int a_dtype, const float* cvec, const void* g,
                       int g_dtype, float* grad_oihw, void* ws, size_t ws_bytes, void* stream);
-/* `_dt` forms of the BatchNorm / activation / layout kernels below: every activation tensor of the call has `dtype` */
+/* `_dt` forms of the BatchNorm / activation / layout kernels below: every activation tensor of the call has `dtype`; they
+   accept the same activations as the fp32 forms and refuse the others the same way */
 int s2i_bn_act_forward_dt(int dtype, const void* y, long long M, int groups, int C, const float* coef4, int act,
                           const void* residual, void* out, void* stream);
 int s2i_bn_act_bwd_reduce_dt(int dtype, const void* y, const void* dout, int lddout, long long M, int groups, int C,
@@ -285,6 +286,8 @@ int s2i_bn_eval_coeffs(int C, const float* gamma, const float* beta, const float
 /*
  * out = act(scale*y + shift) (+ residual).  GLU halves the channel count (C -> C/2).
  * Replaces BatchNorm apply + GLU / LeakyReLU / ResBlock add (model.py:116-122, 165-169).
+ * act is S2I_ACT_NONE, S2I_ACT_GLU or S2I_ACT_LRELU; any other value (TANH, RELU, out of range) is refused: non-zero
+ * return, message in s2i_last_error(), nothing launched.  The same holds for the two backward passes below.
  */
 int s2i_bn_act_forward(const float* y, long long M, int groups, int C, const float* coef4, int act,
                        const float* residual, float* out, void* stream);
@@ -306,7 +309,8 @@ int s2i_bn_act_bwd_apply(const float* y, const float* dout, int lddout, long lon
                          const float* coef4, const float* red2, int act, float* dy, void* stream);
 
 /* ---- plain activations ---------------------------------------------------------------------- */
-/* dy = dout * act'(out) for LRELU / TANH given the forward OUTPUT (sign- / value-recoverable) */
+/* dy = dout * act'(out) for LRELU / TANH given the forward OUTPUT (sign- / value-recoverable); any other act is refused
+   (non-zero return, message in s2i_last_error(), nothing launched) */
 int s2i_act_backward(const float* out, const float* dout, int lddout, long long M, int C, int act,
                      float* dy, void* stream);
 /* 2-D GLU without BatchNorm (CA_NET, model.py:183): out[M][C/2] */

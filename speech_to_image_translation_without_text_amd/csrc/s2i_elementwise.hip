@@ -389,39 +389,9 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const T* __restrict__ y
   }
 }
 
-template <typename T, int ACT = -1>
-__global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const T* __restrict__ y,
-                                                               const T* __restrict__ dout, int lddout,
-                                                               long long M, int C, const float* __restrict__ coef0,
-                                                               const float* __restrict__ red20, int act_rt,
-                                                               T* __restrict__ dy, int G, unsigned Rg) {
-  const int act = ACT >= 0 ? ACT : act_rt;
-  const int Q = C / 4;
-  const long long total = M * Q;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const long long row = e / Q;
-    const int q = (int)(e - row * Q);
-    const unsigned grp = G > 1 ? (unsigned)row / Rg : 0u;
-    const float* coef = coef0 + (size_t)grp * 4 * C;
-    const float* red2 = red20 + (size_t)grp * 2 * C;
-    const f32x4 yv = ld4(y + row * C + q * 4);
-    const f32x4 dz = act_dz(y, dout, lddout, row, C, q, coef, act, yv);
-    const f32x4 mean = ld4(coef + q * 4), invstd = ld4(coef + C + q * 4), sc = ld4(coef + 2 * C + q * 4);
-    const f32x4 m0 = ld4(red2 + q * 4), m1 = ld4(red2 + C + q * 4);
-    f32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float xh = (yv[j] - mean[j]) * invstd[j];
-      o[j] = sc[j] * (dz[j] - m0[j] - xh * m1[j]);
-    }
-    st4(dy + row * C + q * 4, o);
-  }
-}
-
 // The backward apply as a WALKER (round 2): a thread keeps one channel quad and walks the rows of its block's chunk, as
 // colreduce_kernel does, with EVERY coefficient in registers (loaded by hand before the row loop: the stores to dy inside
-// the loop keep the compiler from hoisting them).  The grid-stride form above re-loads seven to nine 16-byte coefficient
+// the loop keep the compiler from hoisting them).  The grid-stride form it replaced re-loaded seven to nine 16-byte coefficient
 // vectors per quad -- L1 hits, but 168 bytes through the CU's 64 B/clk vector-memory path for 24 bytes of data: on the
 // 32-channel GLU tensors of the generator that path, not HBM, set the 2.3 TB/s.
 template <typename T, int ACT, int RPT = 4>
@@ -495,11 +465,9 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_walk_kernel(const T* __r
   }
 }
 
-template <typename T, int ACT = -1>
+template <typename T, int ACT>  // S2I_ACT_LRELU | S2I_ACT_TANH
 __global__ __launch_bounds__(256) void act_bwd_kernel(const T* __restrict__ out, const T* __restrict__ dout,
-                                                      int lddout, long long M, int C, int act_rt,
-                                                      T* __restrict__ dy) {
-  const int act = ACT >= 0 ? ACT : act_rt;
+                                                      int lddout, long long M, int C, T* __restrict__ dy) {
   const int Q = C / 4;
   const long long total = M * Q;
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
@@ -511,9 +479,8 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const T* __restrict__ out,
     f32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if (act == S2I_ACT_LRELU) o[j] = ov[j] > 0.f ? d[j] : 0.2f * d[j];
-      else if (act == S2I_ACT_TANH) o[j] = d[j] * (1.f - ov[j] * ov[j]);
-      else o[j] = d[j];
+      if (ACT == S2I_ACT_LRELU) o[j] = ov[j] > 0.f ? d[j] : 0.2f * d[j];
+      else o[j] = d[j] * (1.f - ov[j] * ov[j]);
     }
     st4(dy + row * C + q * 4, o);
   }
@@ -1412,6 +1379,8 @@ template <typename T>
 static int bn_act_forward_impl(const T* y, long long M, int groups, int C, const float* coef4, int act,
                                const T* residual, T* out, void* stream) {
   S2I_REQUIRE(y && coef4 && out && M > 0 && C > 0, "bn_act_forward: bad args");
+  S2I_REQUIRE(act == S2I_ACT_NONE || act == S2I_ACT_GLU || act == S2I_ACT_LRELU,
+              "bn_act_forward: activation %d is not NONE, GLU or LRELU", act);
   S2I_REQUIRE(groups >= 1 && M % groups == 0 && M < (1ll << 31), "bn_act_forward: rows do not split into groups");
   S2I_REQUIRE(act == S2I_ACT_GLU ? C % 8 == 0 : C % 4 == 0, "bn_act_forward: C=%d not aligned for act %d", C, act);
   S2I_REQUIRE(!(residual && act == S2I_ACT_GLU), "bn_act_forward: residual with GLU unsupported");
@@ -1424,8 +1393,7 @@ static int bn_act_forward_impl(const T* y, long long M, int groups, int C, const
       const RowGeom g = row_geom(Cout / 8, M / groups, groups, 0);
       if (act == S2I_ACT_GLU) S2I_FWDR(8, S2I_ACT_GLU);
       else if (act == S2I_ACT_LRELU) S2I_FWDR(8, S2I_ACT_LRELU);
-      else if (act == S2I_ACT_NONE) S2I_FWDR(8, S2I_ACT_NONE);
-      else S2I_FWDR(8, -1);
+      else S2I_FWDR(8, S2I_ACT_NONE);
     } else {
       const RowGeom g = row_geom(Cout / 4, M / groups, groups, 0);
       S2I_FWDR(4, -1);
@@ -1439,8 +1407,7 @@ static int bn_act_forward_impl(const T* y, long long M, int groups, int C, const
                                          act, residual, out, groups, (unsigned)(M / groups))
   if (act == S2I_ACT_GLU) S2I_FWD(S2I_ACT_GLU);
   else if (act == S2I_ACT_LRELU) S2I_FWD(S2I_ACT_LRELU);
-  else if (act == S2I_ACT_NONE) S2I_FWD(S2I_ACT_NONE);
-  else S2I_FWD(-1);
+  else S2I_FWD(S2I_ACT_NONE);
 #undef S2I_FWD
   S2I_LAUNCH_CHECK("bn_act_forward");
   return 0;
@@ -1461,18 +1428,18 @@ template <typename T>
 static int bn_act_bwd_reduce_impl(const T* y, const T* dout, int lddout, long long M, int groups, int C,
                                   const float* coef4, int act, float* part, int nparts, void* stream) {
   S2I_REQUIRE(y && dout && coef4 && part && M > 0 && nparts > 0, "bn_act_bwd_reduce: bad args");
+  S2I_REQUIRE(act == S2I_ACT_NONE || act == S2I_ACT_GLU || act == S2I_ACT_LRELU,
+              "bn_act_bwd_reduce: activation %d is not NONE, GLU or LRELU", act);
   S2I_REQUIRE(groups >= 1 && M % groups == 0 && nparts % groups == 0, "bn_act_bwd_reduce: bad grouping");
   S2I_REQUIRE(act == S2I_ACT_GLU ? C % 8 == 0 : C % 4 == 0, "bn_act_bwd_reduce: C alignment");
   S2I_REQUIRE(lddout % 4 == 0, "bn_act_bwd_reduce: lddout alignment");
   RedGeom g = red_geom(C);
   // the activation as a template constant: see colreduce_kernel
-  const bool spec = true;
 #define S2I_RED(ACTV) hipLaunchKernelGGL((colreduce_kernel<1, T, ACTV, 4>), dim3(nparts, g.gy), dim3(256), 0, ST, y, C, \
                                          dout, lddout, M, C, coef4, act, part, nparts, g.cpb, nparts / groups, M / groups)
-  if (spec && act == S2I_ACT_LRELU) S2I_RED(S2I_ACT_LRELU);
-  else if (spec && act == S2I_ACT_GLU) S2I_RED(S2I_ACT_GLU);
-  else if (spec && act == S2I_ACT_NONE) S2I_RED(S2I_ACT_NONE);
-  else S2I_RED(-1);
+  if (act == S2I_ACT_LRELU) S2I_RED(S2I_ACT_LRELU);
+  else if (act == S2I_ACT_GLU) S2I_RED(S2I_ACT_GLU);
+  else S2I_RED(S2I_ACT_NONE);
 #undef S2I_RED
   S2I_LAUNCH_CHECK("bn_act_bwd_reduce");
   return 0;
@@ -1499,31 +1466,22 @@ template <typename T>
 static int bn_act_bwd_apply_impl(const T* y, const T* dout, int lddout, long long M, int groups, int C,
                                  const float* coef4, const float* red2, int act, T* dy, void* stream) {
   S2I_REQUIRE(y && dout && coef4 && red2 && dy && M > 0, "bn_act_bwd_apply: bad args");
+  S2I_REQUIRE(act == S2I_ACT_NONE || act == S2I_ACT_GLU || act == S2I_ACT_LRELU,
+              "bn_act_bwd_apply: activation %d is not NONE, GLU or LRELU", act);
   S2I_REQUIRE(groups >= 1 && M % groups == 0 && M < (1ll << 31), "bn_act_bwd_apply: rows do not split into groups");
   S2I_REQUIRE(act == S2I_ACT_GLU ? C % 8 == 0 : C % 4 == 0, "bn_act_bwd_apply: C alignment");
   S2I_REQUIRE(lddout % 4 == 0, "bn_act_bwd_apply: lddout alignment");
-  if (act == S2I_ACT_GLU || act == S2I_ACT_LRELU || act == S2I_ACT_NONE) {
-    RedGeom g = red_geom(C);
-    const long long Rg = M / groups;
-    const int rpb = 256 / g.cpb;
-    const int ppg = rows_ppg(Rg, rpb, groups, g.gy, 16);
+  RedGeom g = red_geom(C);
+  const long long Rg = M / groups;
+  const int rpb = 256 / g.cpb;
+  const int ppg = rows_ppg(Rg, rpb, groups, g.gy, 16);
 #define S2I_APPW(ACTV) hipLaunchKernelGGL((bn_act_bwd_apply_walk_kernel<T, ACTV>), dim3(groups * ppg, g.gy), dim3(256), 0, ST, y, \
                                           dout, lddout, M, C, coef4, red2, dy, g.cpb, ppg, Rg)
-    if (act == S2I_ACT_GLU) S2I_APPW(S2I_ACT_GLU);
-    else if (act == S2I_ACT_LRELU) S2I_APPW(S2I_ACT_LRELU);
-    else S2I_APPW(S2I_ACT_NONE);
+  if (act == S2I_ACT_GLU) S2I_APPW(S2I_ACT_GLU);
+  else if (act == S2I_ACT_LRELU) S2I_APPW(S2I_ACT_LRELU);
+  else S2I_APPW(S2I_ACT_NONE);
 #undef S2I_APPW
-    S2I_LAUNCH_CHECK("bn_act_bwd_apply(walk)");
-    return 0;
-  }
-#define S2I_APP(ACTV) hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, ACTV>), dim3(grid_for(M * (C / 4))), dim3(256), 0, ST, y, dout, \
-                                         lddout, M, C, coef4, red2, act, dy, groups, (unsigned)(M / groups))
-  if (act == S2I_ACT_GLU) S2I_APP(S2I_ACT_GLU);
-  else if (act == S2I_ACT_LRELU) S2I_APP(S2I_ACT_LRELU);
-  else if (act == S2I_ACT_NONE) S2I_APP(S2I_ACT_NONE);
-  else S2I_APP(-1);
-#undef S2I_APP
-  S2I_LAUNCH_CHECK("bn_act_bwd_apply");
+  S2I_LAUNCH_CHECK("bn_act_bwd_apply(walk)");
   return 0;
 }
 extern "C" int s2i_bn_act_bwd_apply(const float* y, const float* dout, int lddout, long long M, int groups, int C,
@@ -1541,12 +1499,11 @@ extern "C" int s2i_bn_act_bwd_apply_dt(int dtype, const void* y, const void* dou
 template <typename T>
 static int act_backward_impl(const T* out, const T* dout, int lddout, long long M, int C, int act, T* dy, void* stream) {
   S2I_REQUIRE(out && dout && dy && M > 0 && C > 0 && C % 4 == 0 && lddout % 4 == 0, "act_backward: bad args");
+  S2I_REQUIRE(act == S2I_ACT_LRELU || act == S2I_ACT_TANH, "act_backward: activation %d is not LRELU or TANH", act);
   if (act == S2I_ACT_LRELU)
-    hipLaunchKernelGGL((act_bwd_kernel<T, S2I_ACT_LRELU>), dim3(grid_for(M * (C / 4))), dim3(256), 0, ST, out, dout, lddout, M, C, act, dy);
-  else if (act == S2I_ACT_TANH)
-    hipLaunchKernelGGL((act_bwd_kernel<T, S2I_ACT_TANH>), dim3(grid_for(M * (C / 4))), dim3(256), 0, ST, out, dout, lddout, M, C, act, dy);
+    hipLaunchKernelGGL((act_bwd_kernel<T, S2I_ACT_LRELU>), dim3(grid_for(M * (C / 4))), dim3(256), 0, ST, out, dout, lddout, M, C, dy);
   else
-    hipLaunchKernelGGL((act_bwd_kernel<T, -1>), dim3(grid_for(M * (C / 4))), dim3(256), 0, ST, out, dout, lddout, M, C, act, dy);
+    hipLaunchKernelGGL((act_bwd_kernel<T, S2I_ACT_TANH>), dim3(grid_for(M * (C / 4))), dim3(256), 0, ST, out, dout, lddout, M, C, dy);
   S2I_LAUNCH_CHECK("act_backward");
   return 0;
 }

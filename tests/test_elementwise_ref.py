@@ -1,0 +1,236 @@
+"""The fp64 reference of tests/elementwise_ref.py against stock torch modules and autograd, and the committed census of
+the non-matrix launches (tests/step_elementwise_launches.json) against it.  No GPU needed."""
+import json
+import os
+
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+import elementwise_ref as R
+import test_step_elementwise_gpu as E
+from speech_to_image_translation_without_text_amd._lib import ACT_GLU, ACT_LRELU, ACT_NONE
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+D64 = torch.float64
+
+
+def _rows(x):
+    """NCHW -> NHWC rows [M][C]."""
+    return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])
+
+
+def _group_part(y, G, ppg):
+    """colstats of each group's rows, ppg chunks per group: [2][G * ppg][C]."""
+    Y = y.reshape(G, -1, y.shape[1])
+    return torch.cat([R.colstats(Y[g], ppg) for g in range(G)], 1)
+
+
+@pytest.mark.parametrize("act,residual", [(ACT_GLU, False), (ACT_LRELU, False), (ACT_NONE, False), (ACT_NONE, True),
+                                          (ACT_LRELU, True)])
+@pytest.mark.parametrize("G", [1, 3])
+def test_bn_act_chain_matches_autograd(act, residual, G):
+    """Forward finalize + apply, then reduce -> backward finalize -> apply, equal F.batch_norm(training=True) of each of
+    the G stacked batches + GLU(dim=channel) / LeakyReLU(0.2) / identity (+ residual) and its autograd."""
+    g = torch.Generator().manual_seed(7 + act + 10 * G)
+    Bg, C, H, W = 2, 8, 5, 3
+    x = torch.randn(G * Bg, C, H, W, generator=g, dtype=D64).requires_grad_(True)
+    gamma = torch.randn(C, generator=g, dtype=D64).requires_grad_(True)
+    beta = torch.randn(C, generator=g, dtype=D64).requires_grad_(True)
+    z = torch.cat([F.batch_norm(xg, None, None, gamma, beta, training=True, eps=1e-5) for xg in x.chunk(G)])
+    out = F.glu(z, dim=1) if act == ACT_GLU else (F.leaky_relu(z, 0.2) if act == ACT_LRELU else z)
+    res = torch.randn(out.shape, generator=g, dtype=D64) if residual else None
+    if residual:
+        out = out + res
+    dout = torch.randn(out.shape, generator=g, dtype=D64)
+    out.backward(dout)
+
+    y = _rows(x.detach())
+    count = Bg * H * W
+    coef = R.bn_finalize(_group_part(y, G, 4), G, count, gamma.detach(), beta.detach())[0]
+    got = R.bn_act_forward(y, G, coef, act, None if res is None else _rows(res))
+    torch.testing.assert_close(got, _rows(out.detach()), rtol=1e-12, atol=1e-12)
+
+    d = _rows(dout)
+    nparts = 3 * G
+    part = R.bn_act_bwd_reduce(y, d, G, coef, act, nparts)
+    dg0, db0 = torch.randn(C, generator=g, dtype=D64), torch.randn(C, generator=g, dtype=D64)
+    red2, dg, db = R.bn_bwd_finalize(part, G, count, dg0, db0, accumulate=True)
+    dy = R.bn_act_bwd_apply(y, d, G, coef, red2, act)
+    torch.testing.assert_close(dy, _rows(x.grad), rtol=1e-10, atol=1e-12)
+    torch.testing.assert_close(dg - dg0, gamma.grad, rtol=1e-10, atol=1e-12)
+    torch.testing.assert_close(db - db0, beta.grad, rtol=1e-10, atol=1e-12)
+    _, dg_assign, _ = R.bn_bwd_finalize(part, G, count, dg0, db0, accumulate=False)
+    torch.testing.assert_close(dg_assign, gamma.grad, rtol=1e-10, atol=1e-12)
+    if act == ACT_GLU:      # a channel-slice dout (ldd > Cout): only the first Cout columns count
+        wide = torch.cat((d, torch.randn(d.shape, generator=g, dtype=D64)), 1)
+        torch.testing.assert_close(R.bn_act_bwd_reduce(y, wide, G, coef, act, nparts), part)
+
+
+@pytest.mark.parametrize("G", [1, 2, 3])
+def test_bn_finalize_matches_batchnorm2d(G):
+    """Finalize + apply = nn.BatchNorm2d (momentum 0.1, eps 1e-5) in training mode run on the G stacked batches one after
+    another, running statistics and num_batches_tracked included."""
+    g = torch.Generator().manual_seed(G)
+    Bg, C, H, W = 3, 6, 4, 4
+    bn = nn.BatchNorm2d(C, momentum=0.1, eps=1e-5).double().train()
+    with torch.no_grad():
+        bn.weight.copy_(torch.randn(C, generator=g, dtype=D64))
+        bn.bias.copy_(torch.randn(C, generator=g, dtype=D64))
+        bn.running_mean.copy_(torch.randn(C, generator=g, dtype=D64))
+        bn.running_var.copy_(torch.rand(C, generator=g, dtype=D64) + 0.5)
+        bn.num_batches_tracked.fill_(5)
+    rm0, rv0 = bn.running_mean.clone(), bn.running_var.clone()
+    x = torch.randn(G * Bg, C, H, W, generator=g, dtype=D64) * 2 + 0.5
+    with torch.no_grad():
+        want = torch.cat([bn(xg) for xg in x.chunk(G)])
+    y = _rows(x)
+    coef, rm, rv, nbt = R.bn_finalize(_group_part(y, G, 5), G, Bg * H * W, bn.weight.detach(), bn.bias.detach(), rm0,
+                                      rv0, torch.tensor(5), 0.1, 1e-5)
+    torch.testing.assert_close(R.bn_act_forward(y, G, coef, ACT_NONE), _rows(want), rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(rm, bn.running_mean, rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(rv, bn.running_var, rtol=1e-12, atol=1e-12)
+    assert int(nbt) == int(bn.num_batches_tracked) == 5 + G
+    biased = R.bn_finalize(_group_part(y, G, 5), G, Bg * H * W, bn.weight, bn.bias, rm0, rv0, None, 0.1, 1e-5,
+                           biased_running=True)[2]
+    assert not torch.allclose(biased, bn.running_var, rtol=1e-6, atol=0)
+
+
+@pytest.mark.parametrize("H,W", [(2, 2), (5, 7), (8, 8)])
+def test_tap_sums_and_cvec_grads_match_conv_autograd(H, W):
+    """A spatially constant input c through F.conv2d(padding=1): the output is conv(h) + the border-class bias table,
+    and c.grad / weight.grad are dc / dW from the tap sums of dY."""
+    g = torch.Generator().manual_seed(H * W)
+    B, Cc, N = 2, 4, 5
+    c = torch.randn(B, Cc, generator=g, dtype=D64).requires_grad_(True)
+    w = torch.randn(N, Cc, 3, 3, generator=g, dtype=D64).requires_grad_(True)
+    Y = F.conv2d(c.view(B, Cc, 1, 1).expand(B, Cc, H, W), w, padding=1)
+    dY = torch.randn(Y.shape, generator=g, dtype=D64)
+    Y.backward(dY)
+    packed = torch.zeros(9, Cc + 3, N + 3, dtype=D64)        # P[t][Ip][Op], padded as s2i_pack_conv_weight pads
+    packed[:, :Cc, :N] = w.detach().permute(2, 3, 1, 0).reshape(9, Cc, N)
+    torch.testing.assert_close(R.packed_to_oihw(packed, Cc, N), w.detach())
+    table = R.cvec_bias_table(c.detach(), packed, Cc, N)
+    cls = torch.tensor([[3 * (0 if i == 0 else (2 if i == H - 1 else 1)) + (0 if j == 0 else (2 if j == W - 1 else 1))
+                         for j in range(W)] for i in range(H)]).view(-1)
+    got = table[:, cls, :].permute(0, 2, 1).reshape(B, N, H, W)
+    torch.testing.assert_close(got, Y.detach(), rtol=1e-12, atol=1e-12)
+    tap = R.tap_sums(dY.permute(0, 2, 3, 1))
+    torch.testing.assert_close(R.cvec_dc(packed, tap, Cc, N), c.grad, rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(R.cvec_dw(c.detach(), tap, N), w.grad, rtol=1e-12, atol=1e-12)
+    if H > 2:      # the wrong restatement differs
+        assert not torch.allclose(R.tap_sums(dY.permute(0, 2, 3, 1), swap_top_bottom=True), tap)
+
+
+def test_adam_matches_torch_optim():
+    g = torch.Generator().manual_seed(3)
+    p0 = torch.randn(37, generator=g, dtype=D64)
+    p = p0.clone().requires_grad_(True)
+    opt = torch.optim.Adam([p], lr=2e-4, betas=(0.5, 0.999), eps=1e-8)
+    q, m, v = p0.clone(), torch.zeros(37, dtype=D64), torch.zeros(37, dtype=D64)
+    for step in range(1, 6):
+        grad = torch.randn(37, generator=g, dtype=D64)
+        p.grad = grad.clone()
+        opt.step()
+        q, m, v = R.adam_step(q, grad * 4, m, v, 2e-4, 0.5, 0.999, 1e-8, step, gscale=0.25)
+        torch.testing.assert_close(q, p.detach(), rtol=1e-12, atol=1e-14)
+    st = opt.state[p]
+    torch.testing.assert_close(m, st["exp_avg"], rtol=1e-12, atol=1e-15)
+    torch.testing.assert_close(v, st["exp_avg_sq"], rtol=1e-12, atol=1e-18)
+
+
+def test_bce_multi_matches_binary_cross_entropy():
+    g = torch.Generator().manual_seed(4)
+    G, H, B = 3, 2, 5
+    probs = [torch.rand(G * B, generator=g, dtype=D64).requires_grad_(True) for _ in range(H)]
+    with torch.no_grad():
+        probs[0][1], probs[1][2] = 0.0, 1.0          # torch's log clamp at -100
+    target = torch.tensor([1.0, 0.0, 0.0, 1.0, 0.0, 0.0], dtype=D64)
+    weight = torch.tensor([1.0, 0.5, 2.0, 0.25, 1.5, 0.75], dtype=D64)
+    want = sum(weight[gi * H + h] * F.binary_cross_entropy(probs[h][gi * B:(gi + 1) * B],
+                                                           target[gi * H + h].expand(B))
+               for gi in range(G) for h in range(H))
+    gout = 1.7
+    (want * gout).backward()
+    got = R.bce_multi_forward([p.detach() for p in probs], target, weight, G, B)
+    torch.testing.assert_close(got, want.detach(), rtol=1e-12, atol=1e-12)
+    for h, d in enumerate(R.bce_multi_backward([p.detach() for p in probs], target, weight, G, B, gout)):
+        torch.testing.assert_close(d, probs[h].grad, rtol=1e-8, atol=1e-12)   # ~3e11 at p = 0: order of roundings
+    # the single-term restatement (s2i_bce_forward / backward) is the same term
+    p = probs[0].detach()[:B]
+    torch.testing.assert_close(R.bce_forward(p, 1.0, 0.5), 0.5 * F.binary_cross_entropy(p, torch.ones(B, dtype=D64)))
+
+
+def test_heads_and_ca_net_match_autograd():
+    g = torch.Generator().manual_seed(9)
+    B, C, E = 3, 6, 4
+    x = torch.randn(B, 4, 4, C, generator=g, dtype=D64).requires_grad_(True)
+    conv = nn.Conv2d(C, 1, 4, 4).double()
+    prob = torch.sigmoid(conv(x.permute(0, 3, 1, 2))).view(-1)
+    dprob = torch.randn(B, generator=g, dtype=D64)
+    prob.backward(dprob)
+    w, b = conv.weight.detach(), conv.bias.detach()
+    torch.testing.assert_close(R.logit_forward(x.detach(), w, b), prob.detach())
+    _, dx, dw, db = R.logit_backward(x.detach(), w, prob.detach(), dprob)
+    torch.testing.assert_close(dx, x.grad)
+    torch.testing.assert_close(dw, conv.weight.grad)
+    torch.testing.assert_close(db, conv.bias.grad)
+    h = torch.randn(B, 2 * E, generator=g, dtype=D64).requires_grad_(True)
+    eps = torch.randn(B, E, generator=g, dtype=D64)
+    c = eps * torch.exp(0.5 * h[:, E:]) + h[:, :E]
+    kl = -0.5 * torch.mean(1 + h[:, E:] - h[:, :E] ** 2 - torch.exp(h[:, E:]))
+    dc = torch.randn(B, E, generator=g, dtype=D64)
+    torch.testing.assert_close(R.reparam_forward(h.detach(), eps), c.detach())
+    torch.testing.assert_close(R.kl_forward(h.detach()[:, :E], h.detach()[:, E:]), kl.detach())
+    ((c * dc).sum() + 2.5 * kl).backward()
+    dmu, dlv = R.kl_backward(h.detach()[:, :E], h.detach()[:, E:], 2.5)
+    torch.testing.assert_close(R.reparam_backward(h.detach(), eps, dc) + torch.cat((dmu, dlv), 1), h.grad)
+    a = torch.randn(B, 2 * E, generator=g, dtype=D64).requires_grad_(True)
+    F.glu(a, 1).backward(dc)
+    torch.testing.assert_close(R.glu(a.detach()), F.glu(a.detach(), 1))
+    torch.testing.assert_close(R.glu_backward(a.detach(), dc), a.grad)
+
+
+def test_cal_loss_matches_autograd():
+    """class_aware_loss of the reference trainer as stock ops on X: the restated dS gives dX = dS X."""
+    g = torch.Generator().manual_seed(2)
+    B, D = 8, 5
+    X = torch.randn(B, D, generator=g, dtype=D64).requires_grad_(True)
+    labels = torch.tensor([0, 1, 0, 2, 1, 0, 3, 2])
+    S = X @ X.t()
+    same = (labels.view(-1, 1) == labels.view(1, -1)) & ~torch.eye(B, dtype=torch.bool)
+    loss = torch.clamp(S.mean() - S[same].mean(), min=0) / D
+    loss.backward()
+    got, dS = R.cal_loss(S.detach(), labels, D)
+    torch.testing.assert_close(got, loss.detach())
+    torch.testing.assert_close(dS @ X.detach(), X.grad)
+
+
+def test_layouts_and_cast():
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(2, 3, 4, 5, generator=g)
+    y = R.nchw_to_nhwc(x, 8)
+    assert y.shape == (2, 4, 5, 8) and not y[..., 3:].any()
+    assert torch.equal(R.nhwc_to_nchw(y.reshape(-1, 8), 2, 3, 4, 5), x)
+    assert R.cast(torch.tensor([1 + 2 ** -8]), torch.bfloat16).item() == 1.0       # ties to even
+
+
+def test_census_file_is_well_formed():
+    path = os.path.join(HERE, "step_elementwise_launches.json")
+    with open(path) as fp:
+        census = json.load(fp)
+    assert set(census) == set(E.MODES)
+    for mode, recs in census.items():
+        assert recs, mode
+        assert [json.dumps(r, sort_keys=True) for r in recs] == sorted({json.dumps(r, sort_keys=True) for r in recs}), \
+            "%s: records not deduplicated and sorted" % mode
+        for rec in recs:
+            fn = rec["fn"]
+            assert not E._is_matrix(fn), "%s: matrix entry point %s belongs to tests/step_launches.json" % (mode, fn)
+            assert fn in R.RESTATES, "%s: %s has no fp64 restatement" % (mode, fn)
+            assert fn in E.REPLAY, "%s: %s has no replay" % (mode, fn)
+            names = set(E.ARGS[fn].split()) - set(E.NOT_RECORDED)
+            assert set(rec) - {"fn"} == names, (mode, fn, sorted(set(rec) - {"fn"} ^ names))
+        acts = {(r["fn"], r["act"]) for r in recs if "act" in r}
+        assert all(a in (ACT_NONE, ACT_GLU, ACT_LRELU) for f, a in acts if f.startswith("s2i_bn_act")), acts
