@@ -474,6 +474,30 @@ int s2i_inception_prep(const float* img, int B, int Hin, int Win, long long sb, 
 /* nn.Softmax(dim=1) of `rows` rows of `cols` logits (row strides ldx, ldy) */
 int s2i_softmax_rows(const float* x, int rows, int cols, int ldx, float* y, int ldy, void* stream);
 
+/* ---- BVLC GoogLeNet image features (Audio_to_Image/prepare_image_feature.py:86-118, deploy net up to pool5/7x7_s1) ---
+ * Forward only, fp32, NHWC (speech_to_image_translation_without_text_amd/googlenet.py).  The convolutions are
+ * s2i_conv2d_forward; the pieces below are what it cannot do. */
+/* get_one_image_feature's input stage (prepare_image_feature.py:88-93 with load_net_transformer's Transformer,
+   :100-116): image b is the uint8 RGB HWC array img[offsets[b] .. offsets[b] + 3 hs[b] ws[b]) (offsets, hs, ws are
+   DEVICE arrays; nbytes is the size of img).  Bilinear resize to 227 x 227 with half-pixel centres (edge-clamped when
+   a side grows), RGB -> BGR, minus the BGR mean, then the ten 224 x 224 views: crops at (x0, y0) = (0,0), (3,0),
+   (1,1), (0,3), (3,3), then the same five of the up-down flipped image (np.fliplr of the CHW array reverses rows).
+   y is [B * 10][224][224][4] fp32, view-major per image, the 4th channel zero. */
+int s2i_googlenet_prep(const unsigned char* img, long long nbytes, const long long* offsets, const int* hs,
+                       const int* ws, int B, float mean_b, float mean_g, float mean_r, float* y, void* stream);
+/* Caffe MAX pooling, kernel 3, stride 1 or 2, pad 0 or 1, the ceil output rule (F.max_pool2d(..., ceil_mode=True)):
+   GoogLeNet's pool3/3x3_s2, pool4/3x3_s2 (stride 2, pad 0) and every inception/pool (stride 1, pad 1).  NHWC, x pixel
+   stride ldx, y pixel stride ldy, written at channel offset coff. */
+int s2i_maxpool3(const float* x, int B, int H, int W, int C, int ldx, int stride, int pad, float* y, int ldy, int coff,
+                 void* stream);
+/* LRN (ACROSS_CHANNELS: y = x (k + alpha / size * sum of x^2 over channels c - size/2 .. c + size/2, zero padded)^-beta)
+   fused with the adjacent 3x3 stride-2 ceil max pool, in one launch:
+   S2I_POOL_THEN_LRN is pool1/3x3_s2 -> pool1/norm1, S2I_LRN_THEN_POOL is conv2/norm2 -> pool2/3x3_s2.  size odd, <= 9. */
+#define S2I_POOL_THEN_LRN 0
+#define S2I_LRN_THEN_POOL 1
+int s2i_lrn_maxpool3(int order, const float* x, int B, int H, int W, int C, int ldx, float* y, int ldy, int coff,
+                     int size, float alpha, float beta, float k, void* stream);
+
 /* ---- speech front end: WAV samples -> log-mel (Audio_to_Image/utils.py:292-340, load_one_audio_file) ---------------
  * sr 16 kHz, n_fft = win_length = 400, hop 160, symmetric Hamming window, center=True with reflect padding, 40 Slaney mel
  * bands from 20 Hz, power_to_db(ref=np.max, amin=1e-10, top_db=80), 0 dB fill (or truncation) to T frames.

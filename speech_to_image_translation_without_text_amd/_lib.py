@@ -18,6 +18,7 @@ ACT_NONE, ACT_GLU, ACT_LRELU, ACT_TANH, ACT_RELU = 0, 1, 2, 3, 4
 PACK_PLAIN, PACK_UPFOLD = 0, 1
 DT_F32, DT_BF16 = 0, 1
 POOL_MAX3S2, POOL_AVG3S1, POOL_GLOBAL = 0, 1, 2
+POOL_THEN_LRN, LRN_THEN_POOL = 0, 1
 LOGMEL_BFT, LOGMEL_NHWC = 0, 1
 LOGMEL_TILE_FRAMES = 64
 ABI_VERSION = 4
@@ -145,6 +146,10 @@ _SIGNATURES = {
     "s2i_pool2d": (c_int, [c_int, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
     "s2i_inception_prep": (c_int, [P, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll, P, c_int, c_int, P]),
     "s2i_softmax_rows": (c_int, [P, c_int, c_int, c_int, P, c_int, P]),
+    "s2i_googlenet_prep": (c_int, [P, c_ll, P, P, P, c_int, c_float, c_float, c_float, P, P]),
+    "s2i_maxpool3": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P]),
+    "s2i_lrn_maxpool3": (c_int, [c_int, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_float, c_float,
+                                 c_float, P]),
     "s2i_logmel_basis_elems": (c_size_t, []),
     "s2i_signal_mean": (c_int, [P, P, P, c_int, P, P, P]),
     "s2i_logmel_power": (c_int, [P, P, P, c_int, P, P, P, P, P, c_int, c_int, P, P, P]),

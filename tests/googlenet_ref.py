@@ -1,0 +1,95 @@
+"""Float64 CPU restatement of the GoogLeNet feature extractor (Audio_to_Image/prepare_image_feature.py:86-118 with Caffe's
+Transformer and the BVLC deploy network up to pool5/7x7_s1) -- TEST INFRASTRUCTURE ONLY.
+
+Written from the semantics, not from the kernels: the resize is skimage's order-1 resize with half-pixel centres
+(edge-clamped where the image grows), the views are numpy slices of the (C, H, W) array and of its np.fliplr, and the
+network is F.conv2d / F.max_pool2d(ceil_mode=True) / F.local_response_norm / a mean in float64."""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+CROPS = ((0, 0), (3, 0), (1, 1), (0, 3), (3, 3))   # (x0, y0)
+MEAN_BGR = (104.00698793, 116.66876762, 122.67891434)
+
+
+def resize_bilinear(img, out=227):
+    """(H, W, 3) -> (out, out, 3) float64: src = (dst + 0.5) * in / out - 0.5, clamped to [0, in - 1]."""
+    a = np.asarray(img, dtype=np.float64)
+    H, W = a.shape[:2]
+
+    def axis(n):
+        s = (np.arange(out) + 0.5) * (n / out) - 0.5
+        s = np.clip(s, 0.0, n - 1)
+        i0 = np.floor(s).astype(np.int64)
+        i1 = np.minimum(i0 + 1, n - 1)
+        return i0, i1, s - i0
+
+    y0, y1, ly = axis(H)
+    x0, x1, lx = axis(W)
+    top = a[y0][:, x0] * (1 - lx)[None, :, None] + a[y0][:, x1] * lx[None, :, None]
+    bot = a[y1][:, x0] * (1 - lx)[None, :, None] + a[y1][:, x1] * lx[None, :, None]
+    return top * (1 - ly)[:, None, None] + bot * ly[:, None, None]
+
+
+def preprocess(img, mean_bgr=MEAN_BGR):
+    """Transformer.preprocess: resize, HWC -> CHW, RGB -> BGR, x255 (the uint8 source is already 0..255), minus mean."""
+    r = resize_bilinear(img)
+    chw = r.transpose(2, 0, 1)[::-1]
+    return chw - np.asarray(mean_bgr, dtype=np.float64)[:, None, None]
+
+
+def views(img, mean_bgr=MEAN_BGR):
+    """get_one_image_feature's ten (3, 224, 224) views: five crops, then the same five of np.fliplr(CHW)."""
+    chw = preprocess(img, mean_bgr)
+    flip = np.fliplr(chw)
+    out = [chw[:, y0:y0 + 224, x0:x0 + 224] for x0, y0 in CROPS]
+    out += [flip[:, y0:y0 + 224, x0:x0 + 224] for x0, y0 in CROPS]
+    return np.stack(out)
+
+
+def lrn(x):
+    return F.local_response_norm(x, 5, alpha=1e-4, beta=0.75, k=1.0)
+
+
+def pool_s2(x):
+    return F.max_pool2d(x, 3, 2, 0, ceil_mode=True)
+
+
+def forward(weights, x):
+    """x (N, 3, 224, 224) float64 -> (N, 1024) pool5/7x7_s1 features; weights {layer: (w, b)}."""
+    from speech_to_image_translation_without_text_amd import googlenet as G
+
+    def conv(name, t):
+        _cin, _cout, _k, s, p = G.architecture()[name]
+        w, b = weights[name]
+        w = torch.as_tensor(np.asarray(w), dtype=torch.float64)
+        b = torch.as_tensor(np.asarray(b), dtype=torch.float64).reshape(-1)
+        return F.relu(F.conv2d(t, w, b, s, p))
+
+    x = torch.as_tensor(x, dtype=torch.float64)
+    x = conv("conv1/7x7_s2", x)
+    x = lrn(pool_s2(x))
+    x = conv("conv2/3x3_reduce", x)
+    x = conv("conv2/3x3", x)
+    x = pool_s2(lrn(x))
+    for blk in G.BLOCKS:
+        n = blk[0]
+        x = torch.cat([conv(n + "/1x1", x),
+                       conv(n + "/3x3", conv(n + "/3x3_reduce", x)),
+                       conv(n + "/5x5", conv(n + "/5x5_reduce", x)),
+                       conv(n + "/pool_proj", F.max_pool2d(x, 3, 1, 1))], 1)
+        if n in G.POOL_AFTER:
+            x = pool_s2(x)
+    return x.mean(dim=(2, 3))
+
+
+def random_weights(seed=0):
+    """Seeded He-scaled {layer: (w float32, b float32)} of the whole feature network."""
+    from speech_to_image_translation_without_text_amd import googlenet as G
+    rng = np.random.default_rng(seed)
+    out = {}
+    for name, ((o, i, k, _), _b) in G.weight_shapes().items():
+        w = rng.standard_normal((o, i, k, k)) * np.sqrt(2.0 / (i * k * k))
+        b = rng.standard_normal(o) * 0.1
+        out[name] = (w.astype(np.float32), b.astype(np.float32))
+    return out
