@@ -531,6 +531,17 @@ int s2i_logmel_power(const float* x, const long long* offsets, const int* lens, 
 int s2i_logmel_finish(const float* melpow, const unsigned* maxbits, const int* lens, int B, int T, int layout,
                       float* out, void* stream);
 
+/* ---- streaming feature moments for the Frechet distance (StackGAN_v2/trainer.py:103-144) -----------------------------
+ * compute_frethet_distance fits a Gaussian to each set of Inception pool3 rows with np.mean and np.cov.  Both follow
+ * from the row count, the column sums and the Gram matrix X^T X, which add up exactly across chunks of rows, so the
+ * rows can be scored chunk by chunk and dropped (speech_to_image_translation_without_text_amd/gan_metrics.py). */
+/* colsum[D] += sum over r of x_r and gram[D][D] += X^T X for the fp32 rows x_r = x + r ldx (r < rows, ldx >= D), both
+   fp64 on the device, in place.  Products are exact (fp32 -> fp64, v_mfma_f64_16x16x4_f64); the sums are fp64 in a
+   fixed order, so a result is bit-identical from run to run.  Only the 64 x 64 tiles of gram on or above the diagonal
+   are written (a diagonal tile in full): the entries below the diagonal tiles keep whatever they held, and a reader
+   mirrors the upper triangle.  rows = 0 is a no-op.  No atomics, no workspace, no synchronisation. */
+int s2i_moments_accumulate(const float* x, int rows, int D, long long ldx, double* colsum, double* gram, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

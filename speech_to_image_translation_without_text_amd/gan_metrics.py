@@ -1,0 +1,335 @@
+"""Score a trained generator on the test split: Inception score, NLPP and FID, the paper's metrics (StackGAN_v2/
+trainer.py:88-159, whose evaluate() computes them only in dead code after its early return, :803-825).
+
+    python -m speech_to_image_translation_without_text_amd.gan_metrics --cfg cfg/birds_3stages.yml \\
+        --netG output/Model/netG_600.pth --inception inception_v3_google-1a9a5a14.pth --data_dir data/birds \\
+        [--real_stats stats.npz] [--save_images] [--seed S] [--max_items K] [--out metrics.json]
+
+G runs in .eval() over every embedding column of every test item, its last-stage images go through the native
+Inception-v3 (inception.py), and the pool3 rows of each pass are folded into fp64 moments on the device
+(s2i_moments_accumulate: column sums and X^T X), so no pool3 row is kept and the Gaussian of each set costs one D2H copy
+of D (D + 1) doubles.  The softmax rows, which the split-wise IS and NLPP need in order, are kept on the device.
+The values are those of torchvision's Inception-v3 weights: the paper used TF Inception models, so they are not
+comparable to its numbers.
+"""
+import argparse
+import json
+import os
+import queue
+import random
+import threading
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import check, ptr, stream
+from .trainer import (_frechet_from_moments, compute_inception_score, negative_log_posterior_probability,
+                      save_singleimages)
+
+POOL3, CLASSES = 2048, 1000
+# Sentences of one batch are stacked into one G launch up to this many images.  The largest G tensor at
+# cfg/birds_3stages.yml widths is the stage-3 joint input, 128 x 128 x 160 fp32 = 10.5 MB per image, so 96 images stay
+# at 1.0 GB, half of the 2 GiB that the kernels' 32-bit byte offsets reach.
+G_STACK_IMAGES = 96
+
+
+class FeatureMoments:
+    """Count, column sums and Gram matrix of a stream of D-wide fp32 rows, accumulated in fp64 on `device`."""
+
+    def __init__(self, D, device):
+        self.D = int(D)
+        self.device = torch.device(device)
+        self._buf = torch.zeros(self.D + 1, self.D, dtype=torch.float64, device=self.device)   # [colsum; gram]
+        self.colsum, self.gram = self._buf[0], self._buf[1:]
+        self.n = 0
+
+    def update(self, rows):
+        """Fold (N, D) fp32 device rows (row stride >= D) into the moments: one launch on the current stream, no sync."""
+        if (rows.dim() != 2 or rows.shape[1] != self.D or rows.dtype != torch.float32 or rows.stride(1) != 1
+                or rows.device != self.device):
+            raise ValueError("rows must be (N, %d) fp32 with unit column stride on %s, got %s %s on %s"
+                             % (self.D, self.device, tuple(rows.shape), rows.dtype, rows.device))
+        if rows.shape[0] == 0:
+            return
+        check(_lib.load().s2i_moments_accumulate(ptr(rows), rows.shape[0], self.D, rows.stride(0), ptr(self.colsum),
+                                                 ptr(self.gram), stream()), "s2i_moments_accumulate")
+        self.n += rows.shape[0]
+
+    def mean_cov(self):
+        """float64 (mu, sigma, n): sigma normalised by n - 1, as np.cov(rowvar=False)."""
+        if self.n < 2:
+            raise ValueError("a covariance needs at least 2 rows, have %d" % self.n)
+        buf = self._buf.cpu().numpy()
+        g = np.triu(buf[1:])           # the kernel maintains the tiles on and above the diagonal
+        g = g + np.triu(g, 1).T
+        s, n = buf[0], self.n
+        return s / n, (g - np.outer(s, s) / n) / (n - 1), n
+
+    def save(self, path):
+        mu, sigma, n = self.mean_cov()
+        save_stats(path, mu, sigma, n)
+
+    @staticmethod
+    def load(path, D=None):
+        return load_stats(path, D)
+
+
+def save_stats(path, mu, sigma, n):
+    np.savez(path, mu=np.asarray(mu, np.float64), sigma=np.asarray(sigma, np.float64), n=np.int64(n))
+
+
+def load_stats(path, D=None):
+    """(mu, sigma, n) of a .npz written by save_stats; ValueError unless mu is (D,), sigma (D, D) and n >= 2."""
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in ("mu", "sigma", "n") if k not in z.files]
+        if missing:
+            raise ValueError("%s lacks %s" % (path, missing))
+        mu, sigma, n = z["mu"].astype(np.float64), z["sigma"].astype(np.float64), int(z["n"])
+    d = mu.shape[0] if mu.ndim == 1 else -1
+    if d < 1 or sigma.shape != (d, d):
+        raise ValueError("%s: mu %s and sigma %s are not (D,) and (D, D)" % (path, mu.shape, sigma.shape))
+    if D is not None and d != D:
+        raise ValueError("%s holds %d-d statistics, expected %d" % (path, d, D))
+    if n < 2:
+        raise ValueError("%s: statistics of %d rows (need >= 2)" % (path, n))
+    return mu, sigma, n
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
+    """The Frechet distance of compute_frethet_distance from two fitted Gaussians."""
+    mu1, mu2 = np.atleast_1d(np.asarray(mu1, np.float64)), np.atleast_1d(np.asarray(mu2, np.float64))
+    sigma1, sigma2 = np.atleast_2d(np.asarray(sigma1, np.float64)), np.atleast_2d(np.asarray(sigma2, np.float64))
+    if mu1.shape != mu2.shape or sigma1.shape != sigma2.shape or sigma1.shape != mu1.shape * 2:
+        raise ValueError("mismatched statistics: mu %s / %s, sigma %s / %s"
+                         % (mu1.shape, mu2.shape, sigma1.shape, sigma2.shape))
+    return float(_frechet_from_moments(mu1, sigma1, mu2, sigma2, eps))
+
+
+def nhwc4_as_nchw(img):
+    """G's nhwc=True output (B, H, W, 4) as the (B, 3, H, W) view Inception's input stage reads (any strides)."""
+    return img[..., :3].permute(0, 3, 1, 2)
+
+
+class GeneratorScorer:
+    """IS / NLPP over the fake softmax rows (kept on the device in arrival order, in a buffer preallocated for n_fake_max
+    rows that grows if more arrive) and FID between the streamed fake and real pool3 moments.  `inception` is a
+    model.INCEPTION_V3 with weights or an inception.InceptionNet."""
+
+    def __init__(self, inception, n_fake_max, device=None):
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.net = inception.net(self.device) if hasattr(inception, "net") else inception
+        self.soft = torch.empty(max(1, int(n_fake_max)), CLASSES, device=self.device)
+        self.n_fake = 0
+        self.fake = FeatureMoments(POOL3, self.device)
+        self.real = FeatureMoments(POOL3, self.device)
+        self._pool3 = self._soft_real = None
+
+    def _scratch(self, n):
+        if self._pool3 is None or self._pool3.shape[0] < n:
+            self._pool3 = torch.empty(n, POOL3, device=self.device)
+            self._soft_real = torch.empty(n, CLASSES, device=self.device)
+        return self._pool3[:n]
+
+    def _images(self, images):
+        imgs = [images] if torch.is_tensor(images) else list(images)
+        return imgs, sum(t.shape[0] for t in imgs)
+
+    def add_fake(self, images):
+        """One Inception pass over (B, 3, H, W) fp32 images in [-1, 1] (or a list of them, scored as their concatenation):
+        softmax rows appended to the kept rows, pool3 rows folded into the fake moments."""
+        imgs, n = self._images(images)
+        if self.n_fake + n > self.soft.shape[0]:      # more than announced: grow (one device copy per doubling)
+            grown = torch.empty(max(2 * self.soft.shape[0], self.n_fake + n), CLASSES, device=self.device)
+            grown[:self.n_fake].copy_(self.soft[:self.n_fake])
+            self.soft = grown
+        pool3 = self._scratch(n)
+        self.net.run(imgs, self.soft[self.n_fake:self.n_fake + n], pool3)
+        self.fake.update(pool3)
+        self.n_fake += n
+
+    def add_real(self, images):
+        imgs, n = self._images(images)
+        pool3 = self._scratch(n)
+        self.net.run(imgs, self._soft_real[:n], pool3)
+        self.real.update(pool3)
+
+    def fake_predictions(self):
+        return self.soft[:self.n_fake].cpu().double().numpy()
+
+    def result(self, num_splits=10, real_stats=None):
+        """{is_mean, is_std, nlpp_mean, nlpp_std, fid, n_fake, n_real} plus the fitted 'fake_stats' / 'real_stats'
+        (mu, sigma, n).  real_stats, if given, replaces the streamed real moments."""
+        pred = self.fake_predictions()
+        is_mean, is_std = compute_inception_score(pred, num_splits)
+        nlpp_mean, nlpp_std = negative_log_posterior_probability(pred, num_splits)
+        fake = self.fake.mean_cov()
+        real = real_stats if real_stats is not None else self.real.mean_cov()
+        fid = frechet_distance(fake[0], fake[1], real[0], real[1])
+        return dict(is_mean=float(is_mean), is_std=float(is_std), nlpp_mean=float(nlpp_mean), nlpp_std=float(nlpp_std),
+                    fid=fid, n_fake=int(fake[2]), n_real=int(real[2]), fake_stats=fake, real_stats=real)
+
+
+class _PngWriter:
+    """Writes save_singleimages PNGs on a host thread once the device copy of a batch has landed."""
+
+    def __init__(self, save_dir, split_dir="valid"):
+        self.save_dir, self.split_dir = save_dir, split_dir
+        self.q = queue.Queue(maxsize=4)
+        self.err = None
+        self.t = threading.Thread(target=self._run, daemon=True)
+        self.t.start()
+
+    def put(self, img_nhwc, filenames, sentence_ids):
+        u8 = ops.images_to_uint8_hwc(img_nhwc)
+        host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(u8, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.q.put((ev, host, list(filenames), list(sentence_ids)))
+
+    def _run(self):
+        while True:
+            job = self.q.get()
+            if job is None:
+                return
+            if self.err is not None:
+                continue
+            ev, host, names, sids = job
+            try:
+                ev.synchronize()
+                a = host.numpy()
+                B = len(names)
+                for k, s in enumerate(sids):
+                    save_singleimages(a[k * B:(k + 1) * B], names, self.save_dir, self.split_dir, s, a.shape[1], 0)
+            except Exception as e:   # reported by close()
+                self.err = e
+
+    def close(self):
+        self.q.put(None)
+        self.t.join()
+        if self.err is not None:
+            raise self.err
+
+
+@torch.no_grad()
+def score_generator(netG, loader, scorer, seed, sentences=None, max_items=None, save_images=None,
+                    stack_images=G_STACK_IMAGES):
+    """Drive G (.eval()) over the test loader's (images per branch, embeddings (B, S, D), filenames) batches and feed
+    `scorer`: each batch's last-branch real images once, then its fake images sentence by sentence, items in order within
+    a sentence (the reference's row order).  z (B, Z_DIM) then eps (B, EMBEDDING_DIM) are drawn per sentence from one
+    CPU generator seeded with `seed`, so stacking sentences into one G launch (up to stack_images images) draws the same
+    noise.  `save_images`: a directory that receives the reference-named PNGs (single_samples/valid/...).
+    Returns the number of test items scored."""
+    from .miscc.config import cfg
+    dev = scorer.device
+    netG.eval()
+    g = torch.Generator().manual_seed(int(seed))
+    writer = _PngWriter(save_images) if save_images else None
+    items = 0
+    try:
+        for imgs, emb, names in loader:
+            if max_items is not None and items >= max_items:
+                break
+            B = emb.shape[0] if max_items is None else min(emb.shape[0], max_items - items)
+            emb = emb[:B].float().to(dev)
+            names = list(names)[:B]
+            real = imgs[-1][:B].to(dev, non_blocking=True)
+            scorer.add_real(ops.images_from_uint8_hwc(real.contiguous()) if real.dtype == torch.uint8 else real.float())
+            sent = list(range(emb.shape[1])) if sentences is None else list(sentences)
+            per = max(1, int(stack_images) // B)
+            for s0 in range(0, len(sent), per):
+                ss = sent[s0:s0 + per]
+                zs, es = [], []
+                for _ in ss:
+                    zs.append(torch.randn(B, cfg.GAN.Z_DIM, generator=g))
+                    es.append(torch.randn(B, cfg.GAN.EMBEDDING_DIM, generator=g))
+                c = torch.cat([emb[:, s] for s in ss]).contiguous()
+                fake, _, _ = netG(torch.cat(zs).to(dev), c, torch.cat(es).to(dev), True)
+                scorer.add_fake(nhwc4_as_nchw(fake[-1]))
+                if writer is not None:
+                    writer.put(fake[-1], names, ss)
+            items += B
+    finally:
+        if writer is not None:
+            writer.close()
+    return items
+
+
+# ---- command line ----------------------------------------------------------------------------------------------------
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="IS, NLPP and FID of a trained generator on the test split")
+    p.add_argument("--cfg", default=None, help="YAML of the generator (widths, branches, batch size)")
+    p.add_argument("--netG", required=True, help="generator state_dict (netG_<N>.pth)")
+    p.add_argument("--inception", required=True, help="torchvision-layout Inception-v3 state_dict (local file)")
+    p.add_argument("--data_dir", required=True, help="dataset root holding test.json and test/audio_features_*.pickle")
+    p.add_argument("--feature_switch", default="image", help="test/audio_features_<switch>.pickle")
+    p.add_argument("--real_stats", default=None,
+                   help=".npz of the real images' mu / sigma / n: read if it exists (real images are not scored), "
+                        "else written")
+    p.add_argument("--save_images", action="store_true", default=False,
+                   help="write the PNGs under <netG dir>/iteration<N>/single_samples/valid/")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--max_items", type=int, default=None, help="score only the first K test items")
+    p.add_argument("--batch_size", type=int, default=None, help="default: TRAIN.BATCH_SIZE")
+    p.add_argument("--workers", type=int, default=None, help="default: WORKERS")
+    p.add_argument("--out", default="metrics.json", help="JSON record; fid_stats_fake/real.npz go next to it")
+    args = p.parse_args(argv)
+    if args.max_items is not None and args.max_items < 1:
+        p.error("--max_items must be >= 1")
+    args.real_stats_mode = None if not args.real_stats else ("read" if os.path.isfile(args.real_stats) else "write")
+    return args
+
+
+def _image_dir(netG_path):
+    """<netG dir>/iteration<N>, as the reference's evaluate names it (trainer.py:714-718)."""
+    iteration = int(netG_path[netG_path.rfind('_') + 1:netG_path.rfind('.')])
+    return '%s/iteration%d' % (os.path.dirname(os.path.abspath(netG_path)), iteration)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from .datasets import BirdsDataset, default_image_transform, make_dataloader
+    from .miscc.config import cfg, cfg_from_file
+    from .model import INCEPTION_V3
+    from .speech_to_image import load_generator
+    if args.cfg:
+        cfg_from_file(args.cfg)
+    _lib.require_device()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    real_stats = load_stats(args.real_stats, POOL3) if args.real_stats_mode == "read" else None
+    random.seed(args.seed)          # the test transform's random crop and flip (main.py:127-131)
+    torch.manual_seed(args.seed)
+    imsize = cfg.TREE.BASE_SIZE * (2 ** (cfg.TREE.BRANCH_NUM - 1))
+    dataset = BirdsDataset(args.data_dir, train=False, base_size=cfg.TREE.BASE_SIZE,
+                           transform=default_image_transform(imsize), feature_switch=args.feature_switch)
+    bs = args.batch_size or cfg.TRAIN.BATCH_SIZE
+    loader = make_dataloader(dataset, bs, shuffle=False,
+                             workers=cfg.WORKERS if args.workers is None else args.workers)
+    n_items = len(dataset) if args.max_items is None else min(len(dataset), args.max_items)
+    n_sent = dataset.embedding.shape[1]
+    scorer = GeneratorScorer(INCEPTION_V3(args.inception), n_items * n_sent, dev)
+    netG = load_generator(args.netG, dev)
+    score_generator(netG, loader, scorer, args.seed, max_items=args.max_items,
+                    save_images=_image_dir(args.netG) if args.save_images else None)
+    res = scorer.result(10, real_stats)
+    out_dir = os.path.dirname(os.path.abspath(args.out))
+    os.makedirs(out_dir, exist_ok=True)
+    fake_stats, rstats = res.pop("fake_stats"), res.pop("real_stats")
+    save_stats(os.path.join(out_dir, "fid_stats_fake.npz"), *fake_stats)
+    save_stats(os.path.join(out_dir, "fid_stats_real.npz"), *rstats)
+    if args.real_stats_mode == "write":
+        save_stats(args.real_stats, *rstats)
+    rec = dict(res, netG=os.path.abspath(args.netG), seed=args.seed, items=n_items, sentences=n_sent,
+               real_stats=os.path.abspath(args.real_stats) if args.real_stats else None)
+    with open(args.out, "w") as f:
+        json.dump(rec, f)
+        f.write("\n")
+    print("IS %.4f +- %.4f, NLPP %.4f +- %.4f, FID %.4f (%d fake, %d real)"
+          % (res["is_mean"], res["is_std"], res["nlpp_mean"], res["nlpp_std"], res["fid"], res["n_fake"],
+             res["n_real"]))
+    return rec
+
+
+if __name__ == "__main__":
+    main()

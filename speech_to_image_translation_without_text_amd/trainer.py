@@ -85,14 +85,20 @@ def compute_frethet_distance(predictions_g, predictions_r, eps=1e-6):
     mu2, sigma2 = np.atleast_1d(np.mean(predictions_r, axis=0)), np.atleast_2d(np.cov(predictions_r, rowvar=False))
     assert mu1.shape == mu2.shape, 'Training and test mean vectors have different lengths'
     assert sigma1.shape == sigma2.shape, 'Training and test covariances have different dimensions'
+    data = [{'mu': mu1, 'sigma': sigma1}, {'mu': mu1, 'sigma': sigma2}]
+    return _frechet_from_moments(mu1, sigma1, mu2, sigma2, eps), data
+
+
+def _frechet_from_moments(mu1, sigma1, mu2, sigma2, eps=1e-6):
+    """||mu1 - mu2||^2 + tr(sigma1) + tr(sigma2) - 2 tr(sqrtm(sigma1 sigma2)), retried with eps on the diagonals when the
+    product is singular (trainer.py:125-144)."""
     diff = mu1 - mu2
     tr_covmean = _trace_sqrtm_product(sigma1, sigma2)
     if not np.isfinite(tr_covmean):
         print('fid calculation produces singular product; adding %s to diagonal of cov estimates' % eps)
         offset = np.eye(sigma1.shape[0]) * eps
         tr_covmean = _trace_sqrtm_product(sigma1 + offset, sigma2 + offset)
-    data = [{'mu': mu1, 'sigma': sigma1}, {'mu': mu1, 'sigma': sigma2}]
-    return (diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * tr_covmean), data
+    return diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * tr_covmean
 
 
 def negative_log_posterior_probability(predictions, num_splits=1):
@@ -144,6 +150,17 @@ def class_aware_loss(x_activates, class_labels):
 
 def _unwrap(net):
     return net.module if hasattr(net, 'module') else net
+
+
+def save_singleimages(images_u8, filenames, save_dir, split_dir, sentenceID, imsize, sample_idx=0):
+    """images_u8: (B,H,W,3) uint8 on the host.  Same file naming as the reference (trainer.py:664-679)."""
+    from PIL import Image
+    for i in range(images_u8.shape[0]):
+        s_tmp = '%s/single_samples/%s/%s' % (save_dir, split_dir, filenames[i])
+        folder = s_tmp[:s_tmp.rfind('/')]
+        if not os.path.isdir(folder):
+            mkdir_p(folder)
+        Image.fromarray(images_u8[i]).save('%s_%d_sentence%d_%d.png' % (s_tmp, imsize, sentenceID, sample_idx))
 
 
 class _Replica(nn.Module):
@@ -902,22 +919,19 @@ class condGANTrainer(object):
         self.flatG.p.copy_(live)
         ops.refresh_packed(self.flatG.params)
 
-    # -- evaluation (trainer.py:664-679, 681-803): images only; the Inception metrics are short-circuited upstream too
+    # -- evaluation (trainer.py:664-679, 681-825): the PNGs, and with TRAIN.INCEPTION_WEIGHTS set the IS / FID / NLPP that
+    # the reference computes only after its early return (gan_metrics.GeneratorScorer)
     def save_singleimages(self, images_u8, filenames, save_dir, split_dir, sentenceID, imsize, sample_idx=0):
-        """images_u8: (B,H,W,3) uint8 on the host.  Same file naming as the reference."""
-        from PIL import Image
-        for i in range(images_u8.shape[0]):
-            s_tmp = '%s/single_samples/%s/%s' % (save_dir, split_dir, filenames[i])
-            folder = s_tmp[:s_tmp.rfind('/')]
-            if not os.path.isdir(folder):
-                mkdir_p(folder)
-            Image.fromarray(images_u8[i]).save('%s_%d_sentence%d_%d.png' % (s_tmp, imsize, sentenceID, sample_idx))
+        save_singleimages(images_u8, filenames, save_dir, split_dir, sentenceID, imsize, sample_idx)
 
     @torch.no_grad()
     def evaluate(self, split_dir):
         """G in eval mode over every embedding of every test item -> PNGs under <NET_G dir>/iteration<N>/.
         BatchNorm uses the running statistics (no batch barrier); the [-1,1] -> uint8 HWC conversion is one
-        kernel on the NHWC output.  Returns the reference's placeholder metrics (trainer.py:803)."""
+        kernel on the NHWC output.  Returns the reference's placeholder metrics (trainer.py:803), or, with an Inception
+        model (TRAIN.INCEPTION_WEIGHTS), prints the reference's IS / FID / NLPP line over every fake image against each
+        batch's last-branch real images (scored once per batch) and returns [{'mu', 'sigma'} fake, {'mu', 'sigma'} real];
+        the noise draws and the PNGs are the same either way."""
         if cfg.TRAIN.NET_G == '':
             print('Error: the path for morels is not found!')
             return None
@@ -934,14 +948,29 @@ class condGANTrainer(object):
         netG.eval()
         nz = cfg.GAN.Z_DIM
         imsize = cfg.TREE.BASE_SIZE * (2 ** (cfg.TREE.BRANCH_NUM - 1))
+        scorer = None
+        if self.inception_model is not None:
+            from . import gan_metrics
+            n_items = len(getattr(self.data_loader, 'dataset', ())) or self.batch_size * len(self.data_loader)
+            scorer = gan_metrics.GeneratorScorer(self.inception_model, 10 * n_items, dev)   # ten sentences per item
         for data in self.data_loader:
             imgs, t_embeddings, filenames = data
             t_embeddings = t_embeddings.float().to(dev)
             batch_size = t_embeddings.shape[0]
             noise = torch.empty(batch_size, nz, device=dev)
+            if scorer is not None:
+                real = imgs[-1].to(dev)
+                scorer.add_real(ops.images_from_uint8_hwc(real) if real.dtype == torch.uint8 else real.float())
             for i in range(t_embeddings.size(1)):
                 noise.normal_(0, 1)
                 fake_imgs, _, _ = netG.module(noise, t_embeddings[:, i, :].contiguous(), None, True)
+                if scorer is not None:
+                    scorer.add_fake(gan_metrics.nhwc4_as_nchw(fake_imgs[-1]))
                 u8 = ops.images_to_uint8_hwc(fake_imgs[-1]).cpu().numpy()
                 self.save_singleimages(u8, filenames, save_dir, split_dir, i, imsize, 0)
-        return [{'mu': 0, 'sigma': 0}, {'mu': 0, 'sigma': 0}]
+        if scorer is None:
+            return [{'mu': 0, 'sigma': 0}, {'mu': 0, 'sigma': 0}]
+        res = scorer.result(10)
+        print("total, IS mean:{}, FID mean:{}, NLPP mean:{}".format(res['is_mean'], res['fid'], res['nlpp_mean']))
+        (mu_g, sigma_g, _), (mu_r, sigma_r, _) = res['fake_stats'], res['real_stats']
+        return [{'mu': mu_g, 'sigma': sigma_g}, {'mu': mu_r, 'sigma': sigma_r}]

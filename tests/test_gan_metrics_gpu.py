@@ -1,0 +1,283 @@
+"""GPU suite of the test-split scorer: s2i_moments_accumulate against float64 numpy, FeatureMoments against np.mean /
+np.cov and the reference's FIDs, GeneratorScorer / score_generator against a host pipeline (the oracle's eval-mode G,
+then Inception rows, then the float64 metric functions), the opt-in scoring of condGANTrainer.evaluate, and the command
+line end to end."""
+import importlib.util
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from helpers import CASES, GOLDEN, build_nets, configure, make_cub_tree, oracle_dims
+from test_inception_cpu import random_state_dict
+
+pytestmark = pytest.mark.gpu
+
+_spec = importlib.util.spec_from_file_location("make_golden_inception_metrics",
+                                               os.path.join(GOLDEN, "make_golden_inception_metrics.py"))
+mgm = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(mgm)
+
+EPS64 = 2.0 ** -53
+
+
+def moments(gpu, x, D, colsum=None, gram=None):
+    """One s2i_moments_accumulate launch on the fp32 device rows x (row stride x.stride(0)); returns (colsum, gram)."""
+    from speech_to_image_translation_without_text_amd import _lib
+    if colsum is None:
+        colsum = torch.zeros(D, dtype=torch.float64, device=gpu)
+        gram = torch.zeros(D, D, dtype=torch.float64, device=gpu)
+    _lib.check(_lib.load().s2i_moments_accumulate(_lib.ptr(x), x.shape[0], D, x.stride(0), _lib.ptr(colsum),
+                                                  _lib.ptr(gram), _lib.stream()), "s2i_moments_accumulate")
+    return colsum, gram
+
+
+def mirrored(gram):
+    g = np.triu(gram.cpu().numpy())
+    return g + np.triu(g, 1).T
+
+
+def check_against_fp64(x64, colsum, gram, what):
+    """|err| <= rows * 2^-53 * sum |x_i x_j| (the standard bound of an n-term fp64 sum of exact products; measured at
+    most 4.1e-15 against 1.1e-13 at 1000 rows, and the column sums exact)."""
+    n = x64.shape[0]
+    g_ref, s_ref = x64.T @ x64, x64.sum(0)
+    a = np.abs(x64)
+    g_err = np.abs(mirrored(gram) - g_ref) / (a.T @ a + 1e-300)
+    s_err = np.abs(colsum.cpu().numpy() - s_ref) / (a.sum(0) + 1e-300)
+    print("%s: gram max rel err %.3g, colsum %.3g (bound %.3g)" % (what, g_err.max(), s_err.max(), n * EPS64))
+    assert g_err.max() <= n * EPS64 and s_err.max() <= n * EPS64, what
+
+
+@pytest.mark.parametrize("D", [64, 100, 2048])
+@pytest.mark.parametrize("rows", [1, 3, 17, 48, 480, 1000])
+def test_moments_kernel_against_float64(gpu, rows, D):
+    g = torch.Generator().manual_seed(rows * 7 + D)
+    x = torch.randn(rows, D, generator=g).abs_() * 3 - 1          # non-zero mean, mixed signs
+    colsum, gram = moments(gpu, x.to(gpu), D)
+    torch.cuda.synchronize()
+    check_against_fp64(x.double().numpy(), colsum, gram, "rows %d D %d" % (rows, D))
+    # a second identical run is bit-identical
+    colsum2, gram2 = moments(gpu, x.to(gpu), D)
+    assert torch.equal(colsum, colsum2) and torch.equal(gram, gram2)
+
+
+@pytest.mark.parametrize("D", [64, 100, 2048])
+def test_moments_of_row_slices_and_chunked_accumulation(gpu, D):
+    g = torch.Generator().manual_seed(D)
+    wide = torch.randn(700, D + 37, generator=g).to(gpu)
+    x = wide[:, 5:5 + D]                                           # ldx = D + 37, base not 16-byte aligned
+    x64 = x.double().cpu().numpy()
+    colsum, gram = moments(gpu, x, D)
+    check_against_fp64(x64, colsum, gram, "slice D %d" % D)
+    cs, gr = None, None
+    for a, b in ((0, 1), (1, 18), (18, 48), (48, 529), (529, 700)):   # uneven chunks, one launch each
+        cs, gr = moments(gpu, x[a:b], D, cs, gr)
+    torch.cuda.synchronize()
+    check_against_fp64(x64, cs, gr, "chunked D %d" % D)
+    d_g = np.abs(mirrored(gr) - mirrored(gram)).max() / np.abs(mirrored(gram)).max()
+    print("chunked vs one launch: max rel diff %.3g, bitwise equal %s" % (d_g, torch.equal(gr, gram)))
+    assert d_g <= 700 * EPS64                       # measured: bit-identical
+
+
+def test_feature_moments_against_numpy_cov(gpu):
+    from speech_to_image_translation_without_text_amd import gan_metrics as GM
+    x = torch.randn(333, 100, generator=torch.Generator().manual_seed(1)) + 0.5
+    m = GM.FeatureMoments(100, gpu)
+    for a, b in ((0, 100), (100, 101), (101, 333)):
+        m.update(x[a:b].to(gpu))
+    mu, sigma, n = m.mean_cov()
+    x64 = x.double().numpy()
+    assert n == 333
+    e_mu = np.abs(mu - x64.mean(0)).max()
+    e_s = np.abs(sigma - np.cov(x64, rowvar=False)).max() / np.abs(np.cov(x64, rowvar=False)).max()
+    print("mean max err %.3g, cov max rel err %.3g" % (e_mu, e_s))
+    assert e_mu <= 1e-15 and e_s <= 6e-15          # measured 0 and 2.8e-15
+
+
+def test_streamed_fid_reproduces_the_reference_fids(gpu, tmp_path):
+    from speech_to_image_translation_without_text_amd import gan_metrics as GM
+    gold = np.load(os.path.join(GOLDEN, "inception_metrics.npz"))
+    for seed, rg, rr, dim in mgm.FID_CASES:
+        g, r = mgm.features(seed, rg, rr, dim)
+        stats = []
+        for rows in (g, r):
+            m = GM.FeatureMoments(dim, gpu)
+            t = torch.from_numpy(rows).float().to(gpu)
+            n = rows.shape[0]
+            cuts = [0, 7, n // 3, n // 3 + 1, n // 2 + 5, n]
+            for a, b in zip(cuts[:-1], cuts[1:]):
+                m.update(t[a:b])
+            stats.append(m.mean_cov())
+        fid = GM.frechet_distance(stats[0][0], stats[0][1], stats[1][0], stats[1][1])
+        print("FID case %d: %.10g vs %.10g" % (seed, fid, float(gold["fid_%d" % seed])))
+        # the rows enter as fp32 (the reference's arrays are fp64): 4e-8 is 2x the measured 1.95e-8
+        np.testing.assert_allclose(fid, gold["fid_%d" % seed], rtol=4e-8)
+        m.save(str(tmp_path / "s.npz"))
+        mu, sigma, n = GM.FeatureMoments.load(str(tmp_path / "s.npz"), dim)
+        assert n == r.shape[0] and np.array_equal(mu, stats[1][0]) and np.array_equal(sigma, stats[1][1])
+
+
+# ---- the scorer on a seeded generator ----------------------------------------------------------------------------------
+def inception_weights():
+    sd = random_state_dict(seed=5)
+    sd["fc.weight"] = sd["fc.weight"] * 0.01       # no posterior underflows to 0 (log(0) makes IS nan)
+    return sd
+
+
+def synthetic_loader(case, sizes=(3, 2), sentences=3, seed=11):
+    g = torch.Generator().manual_seed(seed)
+    out, k = [], 0
+    for B in sizes:
+        imgs = [torch.rand(B, 3, 64 * 2 ** i, 64 * 2 ** i, generator=g) * 2 - 1 for i in range(3)]
+        emb = torch.randn(B, sentences, case['t'], generator=g)
+        out.append((imgs, emb, ["bird%d/img%d" % (j % 2, j) for j in range(k, k + B)]))
+        k += B
+    return out
+
+
+def host_pipeline(gpu, netG, loader, incep, case, seed):
+    """The same noise through the oracle's eval-mode G, then Inception rows, then the float64 metric functions."""
+    from oracle import stackgan_oracle as orc
+    from speech_to_image_translation_without_text_amd import trainer as T
+    p = {k: v.detach().cpu().clone() for k, v in netG.state_dict().items()}
+    g = torch.Generator().manual_seed(seed)
+    soft, pf, pr = [], [], []
+    net = incep.net(gpu)
+    for imgs, emb, _ in loader:
+        B = emb.shape[0]
+        real = imgs[-1].to(gpu)
+        s = torch.empty(B, 1000, device=gpu)
+        q = torch.empty(B, 2048, device=gpu)
+        net.run([real], s, q)
+        pr.append(q.cpu().double().numpy())
+        for i in range(emb.shape[1]):
+            z = torch.randn(B, case['z'], generator=g)
+            eps = torch.randn(B, case['ef'], generator=g)
+            with torch.no_grad():
+                fakes, _, _ = orc.g_forward(p, z, emb[:, i], eps, oracle_dims(case), training=False)
+            s = torch.empty(B, 1000, device=gpu)
+            q = torch.empty(B, 2048, device=gpu)
+            net.run([fakes[-1].float().to(gpu)], s, q)
+            soft.append(s.cpu().double().numpy())
+            pf.append(q.cpu().double().numpy())
+    soft, pf, pr = np.concatenate(soft), np.concatenate(pf), np.concatenate(pr)
+    is_m, is_s = T.compute_inception_score(soft, 10)
+    nl_m, nl_s = T.negative_log_posterior_probability(soft, 10)
+    fid, _ = T.compute_frethet_distance(pf, pr)
+    return dict(is_mean=is_m, is_std=is_s, nlpp_mean=nl_m, nlpp_std=nl_s, fid=float(fid), n_fake=soft.shape[0],
+                n_real=pr.shape[0])
+
+
+def compare(got, want, rtol, what):
+    for k in ("is_mean", "is_std", "nlpp_mean", "nlpp_std", "fid"):
+        scale = abs(want[k.replace("_std", "_mean")])      # a spread is compared on the scale of its mean
+        rel = abs(got[k] - want[k]) / max(scale, 1e-12)
+        print("%s %s: %.10g vs %.10g (rel %.3g)" % (what, k, got[k], want[k], rel))
+        assert rel <= rtol, (what, k, got[k], want[k])
+    assert got["n_fake"] == want["n_fake"] and got["n_real"] == want["n_real"]
+
+
+def test_score_generator_matches_the_host_pipeline(gpu, tmp_path):
+    from speech_to_image_translation_without_text_amd import gan_metrics as GM, model
+    case = CASES['small3']
+    netG, _ = build_nets(case)
+    gsd = torch.Generator().manual_seed(3)
+    for k, v in netG.state_dict().items():         # non-trivial running statistics
+        if k.endswith('running_mean'):
+            v.copy_(0.1 * torch.randn(v.shape, generator=gsd))
+        elif k.endswith('running_var'):
+            v.copy_(0.5 + torch.rand(v.shape, generator=gsd))
+    loader = synthetic_loader(case)
+    incep = model.INCEPTION_V3(weights=inception_weights())
+    want = host_pipeline(gpu, netG, loader, incep, case, seed=4)
+    netG.to(gpu)
+    res = {}
+    for name, stack in (("stacked", GM.G_STACK_IMAGES), ("per-sentence", 1)):
+        scorer = GM.GeneratorScorer(incep, 4, gpu)               # fewer than arrive: the softmax buffer grows
+        n = GM.score_generator(netG, loader, scorer, seed=4, stack_images=stack,
+                               save_images=str(tmp_path / name) if name == "stacked" else None)
+        assert n == 5
+        res[name] = scorer.result(10)
+        compare(res[name], want, 1e-8, name)                      # 2x the measured 5.3e-9 (FID)
+    compare(res["per-sentence"], res["stacked"], 1e-10, "per-sentence vs stacked")   # measured: identical
+    png = tmp_path / "stacked" / "single_samples" / "valid" / "bird0" / "img4_256_sentence2_0.png"
+    assert png.exists(), png
+    # max_items and a subset of sentences
+    scorer = GM.GeneratorScorer(incep, 8, gpu)
+    assert GM.score_generator(netG, loader, scorer, seed=4, sentences=[1], max_items=4) == 4
+    assert scorer.n_fake == 4 and scorer.real.n == 4
+
+
+def test_evaluate_scores_when_inception_weights_are_set(gpu, tmp_path):
+    from speech_to_image_translation_without_text_amd import trainer as T
+    from speech_to_image_translation_without_text_amd.miscc.config import cfg
+    case = CASES['small3']
+    netG, _ = build_nets(case)
+    wpath = str(tmp_path / "inception.pth")
+    torch.save(inception_weights(), wpath)
+    out = {}
+    try:
+        for key in ("", wpath):
+            model_dir = tmp_path / ("m%d" % len(out)) / "Model"
+            model_dir.mkdir(parents=True)
+            torch.save({'module.' + k: v.clone() for k, v in netG.state_dict().items()}, str(model_dir / "netG_12.pth"))
+            cfg.TRAIN.NET_G = str(model_dir / "netG_12.pth")
+            cfg.TRAIN.FLAG = False
+            cfg.TRAIN.INCEPTION_WEIGHTS = key
+            loader = [(imgs, emb, names) for imgs, emb, names in synthetic_loader(case)]
+            tr = T.condGANTrainer(str(tmp_path / ("out%d" % len(out))), loader, 256, False)
+            torch.manual_seed(77)
+            ret = tr.evaluate('test')
+            pngs = sorted((model_dir / "iteration12").rglob("*.png"))
+            out[key] = (ret, {p.relative_to(model_dir): p.read_bytes() for p in pngs})
+    finally:
+        cfg.TRAIN.NET_G, cfg.TRAIN.FLAG, cfg.TRAIN.INCEPTION_WEIGHTS = '', True, ''
+    plain, scored = out[""], out[wpath]
+    assert plain[0] == [{'mu': 0, 'sigma': 0}, {'mu': 0, 'sigma': 0}]
+    for d in scored[0]:
+        assert d['mu'].shape == (2048,) and d['sigma'].shape == (2048, 2048) and np.isfinite(d['sigma']).all()
+    assert not np.array_equal(scored[0][0]['mu'], scored[0][1]['mu'])
+    assert len(plain[1]) == 15 and plain[1] == scored[1]          # same noise draws, byte-identical PNGs
+
+
+def test_command_line_end_to_end(gpu, tmp_path):
+    from speech_to_image_translation_without_text_amd import gan_metrics as GM
+    case = CASES['small3']
+    netG, _ = build_nets(case)
+    root = tmp_path / "birds"
+    make_cub_tree(str(root), n=7, dim=case['t'])
+    (tmp_path / "Model").mkdir()
+    torch.save(netG.state_dict(), str(tmp_path / "Model" / "netG_5.pth"))
+    torch.save(inception_weights(), str(tmp_path / "inception.pth"))
+    (tmp_path / "g.yml").write_text(
+        "TREE:\n  BRANCH_NUM: 3\nTRAIN:\n  BATCH_SIZE: 4\nGAN:\n  GF_DIM: %d\n  EMBEDDING_DIM: %d\n  Z_DIM: %d\n"
+        "  R_NUM: 2\n  B_CONDITION: True\nTEXT:\n  DIMENSION: %d\n" % (case['gf'], case['ef'], case['z'], case['t']))
+    stats = tmp_path / "real_stats.npz"
+    recs = []
+    try:
+        for k in range(2):
+            out = tmp_path / ("run%d" % k) / "metrics.json"
+            argv = ["--cfg", str(tmp_path / "g.yml"), "--netG", str(tmp_path / "Model" / "netG_5.pth"),
+                    "--inception", str(tmp_path / "inception.pth"), "--data_dir", str(root), "--real_stats",
+                    str(stats), "--seed", "2", "--out", str(out), "--workers", "0"]
+            if k == 0:
+                argv += ["--save_images", "--max_items", "6"]
+            else:
+                argv += ["--max_items", "6"]
+            assert GM.parse_args(argv).real_stats_mode == ("write", "read")[k]
+            GM.main(argv)
+            rec = json.loads(out.read_text())
+            for f in ("fid_stats_fake.npz", "fid_stats_real.npz"):
+                assert (out.parent / f).exists()
+            recs.append(rec)
+    finally:
+        configure(case)
+    assert stats.exists()
+    assert recs[0]["n_fake"] == 60 and recs[0]["n_real"] == 6 and recs[1]["n_real"] == 6
+    print("CLI FID %.10g / %.10g" % (recs[0]["fid"], recs[1]["fid"]))
+    assert recs[1]["fid"] == pytest.approx(recs[0]["fid"], rel=1e-9)
+    assert recs[1]["is_mean"] == pytest.approx(recs[0]["is_mean"], rel=1e-9)
+    assert (tmp_path / "Model" / "iteration5" / "single_samples" / "valid").is_dir()
