@@ -20,6 +20,7 @@
 // Rows of the GEMM are output pixels; a block owns a tile of 128 of them shaped TB x TH x TW (powers of two) chosen
 // from the map size, e.g. 4 x 32 pixels of one image on wide maps, 8 whole 4x4 maps at the discriminators' tails.
 #include "s2i_common.h"
+#include "s2i_tile.h"
 #include <stdio.h>
 
 namespace {
@@ -60,6 +61,26 @@ __device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, int byte_off)
   return __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
 }
 
+// output pixel of row r of the TB x TH x TW pixel tile at (b0, oy0, ox0); false beyond the batch
+__device__ __forceinline__ bool tile_pixel(const ConvBP& p, int b0, int oy0, int ox0, int r, int& b, int& oy, int& ox) {
+  const int TW = 1 << p.lgTW, TH = 1 << p.lgTH;
+  const int tx = r & (TW - 1), ty = (r >> p.lgTW) & (TH - 1), tb = r >> (p.lgTW + p.lgTH);
+  b = b0 + tb;
+  oy = oy0 + ty;
+  ox = ox0 + tx;
+  return b < p.B;
+}
+
+// global row (pixel of y) of that tile row; false beyond the batch.  A transposed-conv phase (py, px) interleaves its rows.
+template <int KIND>
+__device__ __forceinline__ bool tile_out_row(const ConvBP& p, int b0, int oy0, int ox0, int py, int px, int r, long long& row) {
+  int b, oy, ox;
+  if (!tile_pixel(p, b0, oy0, ox0, r, b, oy, ox)) return false;
+  if (KIND == KB_TCONV) row = ((long long)b * (2 * p.Ho) + 2 * oy + py) * (2 * p.Wo) + 2 * ox + px;
+  else row = ((long long)b * p.Ho + oy) * p.Wo + ox;
+  return true;
+}
+
 __device__ __forceinline__ unsigned pack2(float a, float b) {
   f32x2 v = {a, b};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
@@ -90,23 +111,11 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(ConvBP p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
   const int l31 = lane & 31, lh = lane >> 5;
-  // XCD-aware block order (round 3).  The gridDim.y channel blocks and the gridDim.z phases / K splits of ONE pixel tile
-  // read the same input patch; blocks are dealt round-robin over the 8 XCDs (an L2 each), and in launch order the
-  // siblings of a tile are gridDim.x ids apart: another XCD, another time.  Linear id L -> (tile, sibling) such that all
-  // siblings of a tile have the same L % 8 and consecutive ids on that XCD (a bijection: the last group of tiles uses
-  // its own modulus).
-  int bx, by, bz;
-  {
-    const int sib = gridDim.y * gridDim.z;
-    const int L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const int per_group = 8 * sib;
-    const int grp = L / per_group, Ll = L - grp * per_group;
-    const int in_group = min(8, (int)gridDim.x - grp * 8);
-    bx = grp * 8 + Ll % in_group;
-    const int u = Ll / in_group;
-    by = u % gridDim.y;
-    bz = u / gridDim.y;
-  }
+  // XCD-aware block order (round 3): the gridDim.y channel blocks and the gridDim.z phases / K splits of ONE pixel tile read
+  // the same input patch and are its siblings
+  int bx, sib;
+  xcd_block_map(gridDim.x, gridDim.y * gridDim.z, bx, sib);
+  const int by = sib % gridDim.y, bz = sib / gridDim.y;
   int phase = 0, split = bz;
   if (KIND == KB_TCONV) { phase = bz / p.splitk; split = bz - phase * p.splitk; }
   const int py = phase >> 1, px = phase & 1;
@@ -226,12 +235,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(ConvBP p) {
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   if (s_begin < s_end) fetch(s_begin, true);
   stamp(1);
@@ -306,46 +310,12 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(ConvBP p) {
 
   // ---- epilogue ----
   const bool raw = p.splitk > 1;
-  // global row (pixel of y) of tile row r, or -1 beyond the batch
-  auto out_row = [&](int r) -> long long {
-    const int tx = r & (TW - 1), ty = (r >> p.lgTW) & (TH - 1), tb = r >> (p.lgTW + p.lgTH);
-    const int b = b0 + tb, oy = oy0 + ty, ox = ox0 + tx;
-    if (b >= p.B) return -1;
-    if (KIND == KB_TCONV) return ((long long)b * (2 * p.Ho) + 2 * oy + py) * (2 * p.Wo) + 2 * ox + px;
-    return ((long long)b * p.Ho + oy) * p.Wo + ox;
-  };
-  if (p.cls_bias && !raw) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rr = wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const int tx = rr & (TW - 1), ty = (rr >> p.lgTW) & (TH - 1), tb = rr >> (p.lgTW + p.lgTH);
-        const int b = b0 + tb, oy = oy0 + ty, ox = ox0 + tx;
-        if (b >= p.B) continue;
-        const int cls = 3 * (oy == 0 ? 0 : (oy == p.Ho - 1 ? 2 : 1)) + (ox == 0 ? 0 : (ox == p.Wo - 1 ? 2 : 1));
-        const float* bp = p.cls_bias + ((size_t)b * 9 + cls) * p.N;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int n = n0 + wn * TN * 32 + j * 32 + l31;
-          if (n < p.N) acc[i][j][r] += bp[n];
-        }
-      }
-  }
+  auto out_row = [&](int r, long long& row) { return tile_out_row<KIND>(p, b0, oy0, ox0, py, px, r, row); };
+  if (p.cls_bias && !raw)
+    add_class_bias<TM, TN>(p.cls_bias, p.N, p.Ho, p.Wo, acc, lane, wm, wn, n0,
+                           [&](int r, int& b, int& oy, int& ox) { return tile_pixel(p, b0, oy0, ox0, r, b, oy, ox); });
   if (raw) {
-    float* outp = p.slab + (size_t)split * p.Mrows * p.N;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const long long row = out_row(wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh);
-        if (row < 0) continue;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int n = n0 + wn * TN * 32 + j * 32 + l31;
-          if (n < p.N) outp[row * p.N + n] = acc[i][j][r];
-        }
-      }
+    store_slab<TM, TN>(p.slab + (size_t)split * p.Mrows * p.N, p.N, acc, lane, wm, wn, n0, out_row);
     return;
   }
   // bf16 tile through LDS: lanes l and l^1 (columns c, c+1) exchange one register of each row pair so that every lane
@@ -362,8 +332,8 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(ConvBP p) {
         const float give = odd ? mine0 : mine1;
         const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, give), 0xB1, 0xF, 0xF, true));
         const int reg = 2 * q + (odd ? 1 : 0);
-        const int rr = wm * TM * 32 + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-        const int col = wn * TN * 32 + j * 32 + (l31 & ~1);
+        const int rr = acc_row(wm, TM, i, reg, lh);
+        const int col = acc_col(wn, TN, j, l31 & ~1);
         const unsigned v = odd ? pack2(got, mine1) : pack2(mine0, got);
         *reinterpret_cast<unsigned*>(smem + rr * ERS + col * 2) = v;
       }
@@ -375,52 +345,18 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(ConvBP p) {
     for (int q = 0; q < 128 * SPR / 256; ++q) {
       const int e = tid + q * 256;
       const int rr = e / SPR, sg = e & (SPR - 1);
-      const long long row = out_row(rr);
+      long long row;
+      const bool live = out_row(rr, row);
       const int n = n0 + sg * 8;
-      if (row >= 0 && n < p.N && !(DBG & 16))
+      if (live && n < p.N && !(DBG & 16))
         *reinterpret_cast<u32x4*>(p.y + row * p.ldy + n) = *reinterpret_cast<const u32x4*>(smem + rr * ERS + sg * 16);
     }
   }
   stamp(51);
-  if (p.stats) {
-    // column sums of the fp32 accumulators over this block's valid rows (rows beyond the batch gathered zeros)
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);  // [2][WAVES_M][BN]
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      float sv = 0.f, sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float v = acc[i][j][r];
-          sv += v;
-          sq += v * v;
-        }
-      sv += __shfl_xor(sv, 32);
-      sq += __shfl_xor(sq, 32);
-      if (lh == 0) {
-        const int col = wn * TN * 32 + j * 32 + l31;
-        red[(0 * WAVES_M + wm) * BN + col] = sv;
-        red[(1 * WAVES_M + wm) * BN + col] = sq;
-      }
-    }
-    __syncthreads();
-    if (tid < BN) {
-      const int n = n0 + tid;
-      if (n < p.N) {
-        float sv = 0.f, sq = 0.f;
-#pragma unroll
-        for (int q = 0; q < WAVES_M; ++q) {
-          sv += red[(0 * WAVES_M + q) * BN + tid];
-          sq += red[(1 * WAVES_M + q) * BN + tid];
-        }
-        const int gm = phase * gridDim.x + bx;
-        p.part[((size_t)0 * p.nparts + gm) * p.N + n] = sv;
-        p.part[((size_t)1 * p.nparts + gm) * p.N + n] = sq;
-      }
-    }
-  }
+  // column sums of the fp32 accumulators over this block's valid rows (rows beyond the batch gathered zeros)
+  if (p.stats)
+    tile_col_stats<TM, TN, WAVES_M, BN>(p.part, p.nparts, p.N, reinterpret_cast<float*>(smem), acc, tid, lane, wm, wn, n0,
+                                        phase * gridDim.x + bx);
   stamp(52);
   if constexpr ((DBG & 32) != 0) {
     if (tid == 0) {
@@ -634,15 +570,7 @@ __global__ __launch_bounds__(512, 1) void conv_bf16_v2_kernel(ConvBP p) {
 
   u32x4 ra[NPL], rb[2][NBL];
   f32x16 acc[TM][TN];
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  };
-  zero_acc();
+  zero_acc(acc);
   stamp(1);
 
   int tile = blockIdx.x;
@@ -677,45 +605,12 @@ __global__ __launch_bounds__(512, 1) void conv_bf16_v2_kernel(ConvBP p) {
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int l31 = lane & 31, lh = lane >> 5;
     const bool raw = p.splitk > 1;
-    auto out_row = [&](int r) -> long long {
-      const int tx = r & (TW - 1), ty = (r >> p.lgTW) & (TH - 1), tb = r >> (p.lgTW + p.lgTH);
-      const int b = tp.b0 + tb, oy = tp.oy0 + ty, ox = tp.ox0 + tx;
-      if (b >= p.B) return -1;
-      if (KIND == KB_TCONV) return ((long long)b * (2 * p.Ho) + 2 * oy + py) * (2 * p.Wo) + 2 * ox + px;
-      return ((long long)b * p.Ho + oy) * p.Wo + ox;
-    };
-    if (p.cls_bias && !raw) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int rr = wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          const int tx = rr & (TW - 1), ty = (rr >> p.lgTW) & (TH - 1), tb = rr >> (p.lgTW + p.lgTH);
-          const int b = tp.b0 + tb, oy = tp.oy0 + ty, ox = tp.ox0 + tx;
-          if (b >= p.B) continue;
-          const int cls = 3 * (oy == 0 ? 0 : (oy == p.Ho - 1 ? 2 : 1)) + (ox == 0 ? 0 : (ox == p.Wo - 1 ? 2 : 1));
-          const float* bp = p.cls_bias + ((size_t)b * 9 + cls) * p.N;
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const int n = n0 + wn * TN * 32 + j * 32 + l31;
-            if (n < p.N) acc[i][j][r] += bp[n];
-          }
-        }
-    }
+    auto out_row = [&](int r, long long& row) { return tile_out_row<KIND>(p, tp.b0, tp.oy0, tp.ox0, py, px, r, row); };
+    if (p.cls_bias && !raw)
+      add_class_bias<TM, TN>(p.cls_bias, p.N, p.Ho, p.Wo, acc, lane, wm, wn, n0,
+                             [&](int r, int& b, int& oy, int& ox) { return tile_pixel(p, tp.b0, tp.oy0, tp.ox0, r, b, oy, ox); });
     if (raw) {
-      float* outp = p.slab + (size_t)split * p.Mrows * p.N;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const long long row = out_row(wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh);
-          if (row < 0) continue;
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const int n = n0 + wn * TN * 32 + j * 32 + l31;
-            if (n < p.N) outp[row * p.N + n] = acc[i][j][r];
-          }
-        }
+      store_slab<TM, TN>(p.slab + (size_t)split * p.Mrows * p.N, p.N, acc, lane, wm, wn, n0, out_row);
       return;
     }
     constexpr int ERS = BN * 2 + 16;
@@ -730,8 +625,8 @@ __global__ __launch_bounds__(512, 1) void conv_bf16_v2_kernel(ConvBP p) {
           const float give = odd ? mine0 : mine1;
           const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, give), 0xB1, 0xF, 0xF, true));
           const int reg = 2 * q + (odd ? 1 : 0);
-          const int rr = wm * TM * 32 + i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-          const int col = wn * TN * 32 + j * 32 + (l31 & ~1);
+          const int rr = acc_row(wm, TM, i, reg, lh);
+          const int col = acc_col(wn, TN, j, l31 & ~1);
           const unsigned v = odd ? pack2(got, mine1) : pack2(mine0, got);
           *reinterpret_cast<unsigned*>(smem + rr * ERS + col * 2) = v;
         }
@@ -743,51 +638,17 @@ __global__ __launch_bounds__(512, 1) void conv_bf16_v2_kernel(ConvBP p) {
       for (int q = 0; q < BM * SPR / NT; ++q) {
         const int e = tid + q * NT;
         const int rr = e / SPR, sg = e & (SPR - 1);
-        const long long row = out_row(rr);
+        long long row;
+        const bool live = out_row(rr, row);
         const int n = n0 + sg * 8;
-        if (row >= 0 && n < p.N)
+        if (live && n < p.N)
           *reinterpret_cast<u32x4*>(p.y + row * p.ldy + n) = *reinterpret_cast<const u32x4*>(smem + rr * ERS + sg * 16);
       }
     }
     stamp(51);
-    if (p.stats) {
-      __syncthreads();
-      float* red = reinterpret_cast<float*>(smem);  // [2][WAVES_M][BN]
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        float sv = 0.f, sq = 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float v = acc[i][j][r];
-            sv += v;
-            sq += v * v;
-          }
-        sv += __shfl_xor(sv, 32);
-        sq += __shfl_xor(sq, 32);
-        if (lh == 0) {
-          const int col = wn * TN * 32 + j * 32 + l31;
-          red[(0 * WAVES_M + wm) * BN + col] = sv;
-          red[(1 * WAVES_M + wm) * BN + col] = sq;
-        }
-      }
-      __syncthreads();
-      if (tid < BN) {
-        const int n = n0 + tid;
-        if (n < p.N) {
-          float sv = 0.f, sq = 0.f;
-#pragma unroll
-          for (int q = 0; q < WAVES_M; ++q) {
-            sv += red[(0 * WAVES_M + q) * BN + tid];
-            sq += red[(1 * WAVES_M + q) * BN + tid];
-          }
-          const int gm = phase * ntiles + tile_id;
-          p.part[((size_t)0 * p.nparts + gm) * p.N + n] = sv;
-          p.part[((size_t)1 * p.nparts + gm) * p.N + n] = sq;
-        }
-      }
-    }
+    if (p.stats)
+      tile_col_stats<TM, TN, WAVES_M, BN>(p.part, p.nparts, p.N, reinterpret_cast<float*>(smem), acc, tid, lane, wm, wn, n0,
+                                          phase * ntiles + tile_id);
     stamp(52);
   };
 
@@ -938,7 +799,7 @@ __global__ __launch_bounds__(512, 1) void conv_bf16_v2_kernel(ConvBP p) {
     // tile's first patch chunk is still in registers and its first weight stages sit behind the patch region.
     epilogue(cur, tile);
     if (!more_tiles) break;
-    zero_acc();
+    zero_acc(acc);
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < NPL; ++q) *adst(As, plo_of(q)) = ra[q];

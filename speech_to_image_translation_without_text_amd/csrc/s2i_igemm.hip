@@ -18,6 +18,7 @@
 // (ds_read_b32, conflict-free).  Global->LDS staging goes through registers with the next chunk's
 // loads in flight during the MFMA loop.
 #include "s2i_common.h"
+#include "s2i_tile.h"
 
 namespace {
 
@@ -50,8 +51,10 @@ struct IgemmP {
   int in_rows_per_group;   // output rows of THIS launch per BatchNorm group of the producer (rows beyond: next group)
 };
 
-__device__ __forceinline__ void geom(const IgemmP& p, int kind, int& s, int& pad, int& kw) {
-  if (kind == S2I_CONV_1D) { s = p.g_s; pad = p.g_pad; kw = p.g_kw; }
+// stride, padding and taps per kernel row of a kind; S2I_CONV_1D takes its own from the descriptor (IgemmP::g_*; the weight
+// gradient has no 1-D form and passes the 1 x 1 values)
+__device__ __forceinline__ void geom(int kind, int s1d, int pad1d, int kw1d, int& s, int& pad, int& kw) {
+  if (kind == S2I_CONV_1D) { s = s1d; pad = pad1d; kw = kw1d; }
   else if (kind == S2I_CONV_K3S1) { s = 1; pad = 1; kw = 3; }
   else if (kind == S2I_CONV_K4S2) { s = 2; pad = 1; kw = 4; }
   else { s = 1; pad = 0; kw = 1; }
@@ -69,12 +72,6 @@ __device__ __forceinline__ void tap_delta(int kind, int kw, int t, int py, int p
     dy = t / kw;
     dx = t - dy * kw;
   }
-}
-
-__device__ __forceinline__ void geom(int kind, int& s, int& pad, int& kw) {
-  if (kind == S2I_CONV_K3S1) { s = 1; pad = 1; kw = 3; }
-  else if (kind == S2I_CONV_K4S2) { s = 2; pad = 1; kw = 4; }
-  else { s = 1; pad = 0; kw = 1; }
 }
 
 // bit t set <=> tap t of the pixel whose base coordinate is (by,bx) falls inside the H x W tensor
@@ -103,6 +100,40 @@ __device__ __forceinline__ int tap_weight(int kind, int flip, int T, int t, int 
     return k4y * 4 + k4x;
   }
   return flip ? (T - 1 - t) : t;
+}
+
+// output pixel of GEMM row m (the output extents are powers of two); P: IgemmP, or WgradP whose pixels are the reduction index
+template <class P>
+__device__ __forceinline__ void row_pixel(const P& p, int m, int& b, int& oy, int& ox) {
+  b = m >> p.lgHoWo;
+  const int r = m & ((1 << p.lgHoWo) - 1);
+  oy = r >> p.lgWo;
+  ox = r & (p.Wo - 1);
+}
+
+// Row decode of the gather of igemm_fwd_kernel / igemm_fwd_split_kernel.  Thread (mrow, kq) stages channel quad kq of rows
+// m0 + mrow + 32 i; per slot i: the byte offset of that quad in the row's base pixel (may be negative; only used when in
+// bounds), the mask of taps that fall inside the tensor, and the byte offset of the quad in the row's image of cvec.
+template <int ASLOTS>
+__device__ __forceinline__ void gather_rows(const IgemmP& p, int m0, int mrow, int kq, int s, int pad, int kw, int py, int px,
+                                            int (&aoff)[ASLOTS], unsigned (&amask)[ASLOTS], int (&acoff)[ASLOTS]) {
+#pragma unroll
+  for (int i = 0; i < ASLOTS; ++i) {
+    const int m = m0 + mrow + 32 * i;
+    unsigned mask = 0;
+    int base = 0, coff = 0;
+    if (m < p.M) {
+      int b, oy, ox;
+      row_pixel(p, m, b, oy, ox);
+      const int by = p.kind == S2I_CONV_1D ? oy : oy * s - pad, bx = ox * s - pad;
+      mask = tap_mask(p.kind, kw, by, bx, p.H, p.W, py, px);
+      base = (((b * p.H + by) * p.W + bx) * p.Cx + kq * 4) * 4;
+      coff = (b * p.Cc + kq * 4) * 4;
+    }
+    aoff[i] = base;
+    amask[i] = mask;
+    acoff[i] = coff;
+  }
 }
 
 // One 32-deep K chunk: 16 k-pairs, each TM x TN v_mfma_f32_32x32x2_f32.  The fragments of pair kk+1 are read
@@ -166,7 +197,6 @@ __device__ __forceinline__ f32x4 bload4_any(__amdgpu_buffer_rsrc_t r, int byte_o
   return f32x4{__builtin_bit_cast(float, v[0] << 16), __builtin_bit_cast(float, v[0] & 0xffff0000u),
                __builtin_bit_cast(float, v[1] << 16), __builtin_bit_cast(float, v[1] & 0xffff0000u)};
 }
-__device__ __forceinline__ unsigned short f2bf(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
 
 // CA32: gathered channel count (and the broadcast-vector part of it) is a multiple of 32, so a 32-deep K
 // chunk lies inside ONE tap (and entirely in x or entirely in cvec): the tap decode is scalar work.
@@ -193,28 +223,17 @@ __global__ __launch_bounds__(256, 3) void igemm_fwd_kernel(IgemmP p) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-  // XCD-aware block order (round 3): the column blocks, phases and K splits of ONE row tile gather the same input pixels;
-  // launch order puts them gridDim.x ids apart (another XCD's L2, another time).  Linear id -> (row tile, sibling) with all
-  // siblings of a row tile on one XCD (same id % 8) and adjacent there; a bijection for any grid.
-  int bx, by, bz;
-  {
-    const int sib = gridDim.y * gridDim.z;
-    const int L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const int per_group = 8 * sib;
-    const int grp = L / per_group, Ll = L - grp * per_group;
-    const int in_group = min(8, (int)gridDim.x - grp * 8);
-    bx = grp * 8 + Ll % in_group;
-    const int u = Ll / in_group;
-    by = u % gridDim.y;
-    bz = u / gridDim.y;
-  }
+  // XCD-aware block order (round 3): the column blocks, phases and K splits of ONE row tile are its siblings
+  int bx, sib;
+  xcd_block_map(gridDim.x, gridDim.y * gridDim.z, bx, sib);
+  const int by = sib % gridDim.y, bz = sib / gridDim.y;
   int phase = 0, split = bz;
   if (p.kind == S2I_TCONV_K4S2) { phase = bz / p.splitk; split = bz - phase * p.splitk; }
   const int py = phase >> 1, px = phase & 1;
   const int m0 = bx * BM, n0 = by * BN;
   const int kq = tid & 7, mrow = tid >> 3;
   int s, pad, kw;
-  geom(p, p.kind, s, pad, kw);
+  geom(p.kind, p.g_s, p.g_pad, p.g_kw, s, pad, kw);
 
   // hardware-bounds-checked descriptors: an invalid element is fetched at S2I_OOB and reads as zero,
   // so the gather needs no exec-mask branches
@@ -222,27 +241,9 @@ __global__ __launch_bounds__(256, 3) void igemm_fwd_kernel(IgemmP p) {
   const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)p.cvec, 0, p.c_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
 
-  int aoff[ASLOTS];     // byte offset of the slot's base pixel (may be negative; only used when in bounds)
+  int aoff[ASLOTS], acoff[ASLOTS];
   unsigned amask[ASLOTS];
-  int acoff[ASLOTS];    // byte offset of the slot's row of cvec
-#pragma unroll
-  for (int i = 0; i < ASLOTS; ++i) {
-    const int m = m0 + mrow + 32 * i;
-    unsigned mask = 0;
-    int base = 0, coff = 0;
-    if (m < p.M) {
-      const int b = m >> p.lgHoWo;
-      const int r = m & ((1 << p.lgHoWo) - 1);
-      const int oy = r >> p.lgWo, ox = r & (p.Wo - 1);
-      const int by = p.kind == S2I_CONV_1D ? oy : oy * s - pad, bx = ox * s - pad;
-      mask = tap_mask(p.kind, kw, by, bx, p.H, p.W, py, px);
-      base = (((b * p.H + by) * p.W + bx) * p.Cx + kq * 4) * 4;
-      coff = (b * p.Cc + kq * 4) * 4;
-    }
-    aoff[i] = base;
-    amask[i] = mask;
-    acoff[i] = coff;
-  }
+  gather_rows<ASLOTS>(p, m0, mrow, kq, s, pad, kw, py, px, aoff, amask, acoff);
   // per-thread constant parts of the weight addresses
   const int bcol4 = tid % (BN / 4), brow = tid / (BN / 4);
   int wconst[BSLOTS];
@@ -333,12 +334,7 @@ __global__ __launch_bounds__(256, 3) void igemm_fwd_kernel(IgemmP p) {
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int c_begin = split * p.cps;
   const int c_end = min(p.nchunks, c_begin + p.cps);
@@ -378,6 +374,9 @@ __global__ __launch_bounds__(256, 3) void igemm_fwd_kernel(IgemmP p) {
   }
 
   // ---- epilogue ----
+  // This kernel keeps its own copy of the class bias, tile store and column sums that the other matrix kernels take from
+  // s2i_tile.h: built on the shared pieces, its 3x3 forward launches ran 1 - 3.5 us (1.3 - 5 %) slower on the MI355X
+  // (DESIGN.md section 4a).  A change to the shared epilogue pieces has to be repeated here.
   const int l31 = lane & 31, lh = lane >> 5;
   const bool tconv = p.kind == S2I_TCONV_K4S2;
   const bool raw = p.splitk > 1;
@@ -531,33 +530,15 @@ __global__ __launch_bounds__(256, 3) void igemm_fwd_split_kernel(IgemmP p) {
   const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
   const int kq = tid & 7, mrow = tid >> 3;
   int s, pad, kw;
-  geom(p, p.kind, s, pad, kw);
+  geom(p.kind, p.g_s, p.g_pad, p.g_kw, s, pad, kw);
 
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void*)p.cvec, 0, p.c_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)p.wsp, 0, p.wsp_bytes, 0x00020000);
 
-  int aoff[ASLOTS];
+  int aoff[ASLOTS], acoff[ASLOTS];
   unsigned amask[ASLOTS];
-  int acoff[ASLOTS];
-#pragma unroll
-  for (int i = 0; i < ASLOTS; ++i) {
-    const int m = m0 + mrow + 32 * i;
-    unsigned mask = 0;
-    int base = 0, coff = 0;
-    if (m < p.M) {
-      const int b = m >> p.lgHoWo;
-      const int r = m & ((1 << p.lgHoWo) - 1);
-      const int oy = r >> p.lgWo, ox = r & (p.Wo - 1);
-      const int by = p.kind == S2I_CONV_1D ? oy : oy * s - pad, bx = ox * s - pad;
-      mask = tap_mask(p.kind, kw, by, bx, p.H, p.W, py, px);
-      base = (((b * p.H + by) * p.W + bx) * p.Cx + kq * 4) * 4;
-      coff = (b * p.Cc + kq * 4) * 4;
-    }
-    aoff[i] = base;
-    amask[i] = mask;
-    acoff[i] = coff;
-  }
+  gather_rows<ASLOTS>(p, m0, mrow, kq, s, pad, kw, py, px, aoff, amask, acoff);
   int bconst[BLOADS], blds[BLOADS];
 #pragma unroll
   for (int q = 0; q < BLOADS; ++q) {
@@ -594,12 +575,7 @@ __global__ __launch_bounds__(256, 3) void igemm_fwd_split_kernel(IgemmP p) {
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int l31 = lane & 31, lh = lane >> 5;
   const int fsw = ((lh ^ ((l31 >> 2) & 3)) << 4);  // swizzled segment of k-step 0; k-step 1 is fsw ^ 32
@@ -653,97 +629,28 @@ __global__ __launch_bounds__(256, 3) void igemm_fwd_split_kernel(IgemmP p) {
     __syncthreads();
   }
 
-  // ---- epilogue (as igemm_fwd_kernel) ----
-  const bool tconv = p.kind == S2I_TCONV_K4S2;
+  // ---- epilogue: class bias, the split-K slab or y, BatchNorm column sums (rows >= M gathered zeros) ----
   const bool raw = p.splitk > 1;
-  if (p.cls_bias && !raw) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (m >= p.M) continue;
-        const int b = m >> p.lgHoWo;
-        const int rr = m & ((1 << p.lgHoWo) - 1);
-        const int oy = rr >> p.lgWo, ox = rr & (p.Wo - 1);
-        const int cls = 3 * (oy == 0 ? 0 : (oy == p.Ho - 1 ? 2 : 1)) + (ox == 0 ? 0 : (ox == p.Wo - 1 ? 2 : 1));
-        const float* bpt = p.cls_bias + ((size_t)b * 9 + cls) * p.N;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int n = n0 + wn * TN * 32 + j * 32 + l31;
-          if (n < p.N) acc[i][j][r] += bpt[n];
-        }
-      }
-  }
-  float* outp = raw ? p.slab + (size_t)split * p.Mrows * p.N : p.y;
-  const int ldo = raw ? p.N : p.ldy;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      if (m >= p.M) continue;
-      long long row = m;
-      if (tconv) {
-        const int b = m >> p.lgHoWo;
-        const int rr = m & ((1 << p.lgHoWo) - 1);
-        const int oy = rr >> p.lgWo, ox = rr & (p.Wo - 1);
-        row = ((long long)b * (2 * p.Ho) + 2 * oy + py) * (2 * p.Wo) + 2 * ox + px;
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * TN * 32 + j * 32 + l31;
-        if (n < p.N) {
-          float v = acc[i][j][r];
-          if (!raw) {
-            if (p.bias) v += p.bias[n];
-            if (p.act == S2I_ACT_LRELU) v = v > 0.f ? v : 0.2f * v;
-            else if (p.act == S2I_ACT_TANH) v = tanhf(v);
-            else if (p.act == S2I_ACT_RELU) v = fmaxf(v, 0.f);
-          }
-          outp[row * ldo + n] = v;
-        }
-      }
-    }
-  }
-  if (p.stats && !raw) {
-    float* red = reinterpret_cast<float*>(smem);  // [2][WAVES_M][BN]
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      float sv = 0.f, sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float v = acc[i][j][r];
-          sv += v;
-          sq += v * v;
-        }
-      sv += __shfl_xor(sv, 32);
-      sq += __shfl_xor(sq, 32);
-      if (lh == 0) {
-        const int col = wn * TN * 32 + j * 32 + l31;
-        red[(0 * WAVES_M + wm) * BN + col] = sv;
-        red[(1 * WAVES_M + wm) * BN + col] = sq;
-      }
-    }
-    __syncthreads();
-    if (tid < BN) {
-      const int n = n0 + tid;
-      if (n < p.N) {
-        float sv = 0.f, sq = 0.f;
-#pragma unroll
-        for (int q = 0; q < WAVES_M; ++q) {
-          sv += red[(0 * WAVES_M + q) * BN + tid];
-          sq += red[(1 * WAVES_M + q) * BN + tid];
-        }
-        const int gm = phase * gridDim.x + blockIdx.x;
-        p.part[((size_t)0 * p.nparts + gm) * p.N + n] = sv;
-        p.part[((size_t)1 * p.nparts + gm) * p.N + n] = sq;
-      }
-    }
-  }
+  if (p.cls_bias && !raw)
+    add_class_bias<TM, TN>(p.cls_bias, p.N, p.Ho, p.Wo, acc, lane, wm, wn, n0,
+                           [&](int r, int& b, int& oy, int& ox) {
+                             if (m0 + r >= p.M) return false;
+                             row_pixel(p, m0 + r, b, oy, ox);
+                             return true;
+                           });
+  store_tile<TM, TN>(raw ? p.slab + (size_t)split * p.Mrows * p.N : p.y, raw ? p.N : p.ldy, p.N, raw, p.bias, p.act, 0 /* y is always fp32 here */, acc, lane,
+                     wm, wn, n0, [&](int r, long long& row) {
+                       const int m = m0 + r;
+                       if (m >= p.M) return false;
+                       row = m;
+                       if (p.kind == S2I_TCONV_K4S2) {   // the rows of a phase interleave into the 2Ho x 2Wo map
+                         int b, oy, ox;
+                         row_pixel(p, m, b, oy, ox);
+                         row = ((long long)b * (2 * p.Ho) + 2 * oy + py) * (2 * p.Wo) + 2 * ox + px;
+                       }
+                       return true;
+                     });
+  if (p.stats && !raw) tile_col_stats<TM, TN, WAVES_M, BN>(p.part, p.nparts, p.N, reinterpret_cast<float*>(smem), acc, tid, lane, wm, wn, n0, phase * gridDim.x + blockIdx.x);
 }
 
 // fp32 packed weights P[T][R][C] -> NP bf16 planes in BOTH operand layouts from one read:
@@ -803,7 +710,7 @@ __global__ __launch_bounds__(256) void small_n_conv_kernel(IgemmP p) {
   const int phase = blockIdx.z;
   const int py = phase >> 1, px = phase & 1;
   int s, pad, kw;
-  geom(p, p.kind, s, pad, kw);
+  geom(p.kind, p.g_s, p.g_pad, p.g_kw, s, pad, kw);
   // stage the 4 output columns of every (tap, channel) row
   for (int e = tid; e < p.T * p.Ca; e += 256) {
     const int t = e / p.Ca, c = e - t * p.Ca;
@@ -924,7 +831,7 @@ __device__ __forceinline__ void load8(const IgemmP& p, long long xe, float (&v)[
 __global__ __launch_bounds__(256) void thin_out_kernel(IgemmP p, const float* __restrict__ table) {
   const int phase = blockIdx.z, py = phase >> 1, px = phase & 1;
   int s, pad, kw;
-  geom(p, p.kind, s, pad, kw);
+  geom(p.kind, p.g_s, p.g_pad, p.g_kw, s, pad, kw);
   const float* __restrict__ wph = table + (size_t)phase * p.T * p.Ca * 4;
   for (int m = blockIdx.x * 256 + threadIdx.x; m < p.M; m += gridDim.x * 256) {
     const int b = m >> p.lgHoWo;
@@ -1129,7 +1036,7 @@ __global__ __launch_bounds__(256) void conv3_n4_tile_kernel(IgemmP p, const floa
 template <int NOUT>
 __global__ __launch_bounds__(256) void thin_in_kernel(IgemmP p, const float* __restrict__ table) {
   int s, pad, kw;
-  geom(p, p.kind, s, pad, kw);
+  geom(p.kind, p.g_s, p.g_pad, p.g_kw, s, pad, kw);
   for (int m = blockIdx.x * 256 + threadIdx.x; m < p.M; m += gridDim.x * 256) {
     const int b = m >> p.lgHoWo;
     const int r = m & ((1 << p.lgHoWo) - 1);
@@ -1230,7 +1137,7 @@ __global__ __launch_bounds__(256) void rgb_out_kernel(IgemmP p, const unsigned s
   const int l31 = lane & 31, lh = lane >> 5;
   const int phase = blockIdx.z, py = phase >> 1, px = phase & 1;
   int s, pad, kw;
-  geom(p, p.kind, s, pad, kw);
+  geom(p.kind, p.g_s, p.g_pad, p.g_kw, s, pad, kw);
   bf16x8_t A[KSTEPS];
 #pragma unroll
   for (int ks = 0; ks < KSTEPS; ++ks)
@@ -1286,7 +1193,7 @@ __global__ __launch_bounds__(256) void rgb_in_kernel(IgemmP p, const unsigned sh
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int l31 = lane & 31, lh = lane >> 5;
   int s, pad, kw;
-  geom(p, p.kind, s, pad, kw);
+  geom(p.kind, p.g_s, p.g_pad, p.g_kw, s, pad, kw);
   bf16x8_t A[MT][KH];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
@@ -1428,20 +1335,25 @@ struct WgradP {
   int a_groups, a_ipg;   // BatchNorm groups of the producer, images per group
 };
 
-// XCD-aware block order of the weight-gradient grids (tiles x pixel-range splits).  Every tile of ONE split reads the same
-// pixels of both operands, and blocks are dealt round-robin over the chip's 8 XCDs, each with an L2 of its own
-// (MI355X_MICROARCH.md): in launch order (tile fastest) the 8 k-tiles of a split land on 8 different XCDs and every one of
-// them pulls the split's `g` rows through the fabric (profiles/r03_roofline_bf16_wgrad_b48: 1.25 GB fetched for 453 MB of
-// operands).  Here linear block id L maps to (tile, split) such that all tiles of a split have the same L % 8 -- one XCD --
-// and consecutive ids on that XCD; a bijection for any split count (the last group of splits uses its own modulus).
-__device__ __forceinline__ void wgrad_block_map(int& tile, int& split) {
-  const int tiles = gridDim.x * gridDim.y, nsplit = gridDim.z;
-  const int L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-  const int per_group = 8 * tiles;
-  const int grp = L / per_group, Ll = L - grp * per_group;
-  const int in_group = min(8, nsplit - grp * 8);         // splits of this group (the last one may hold fewer)
-  split = grp * 8 + Ll % in_group;
-  tile = Ll / in_group;
+// (tap, channel) of gathered column kcol: fixed for a thread's whole pixel loop; false beyond K
+__device__ __forceinline__ bool wgrad_col(const WgradP& p, int kcol, int kw, int& c, int& dy, int& dx) {
+  c = 0;
+  dy = 0;
+  dx = 0;
+  if (kcol >= p.K) return false;
+  const int t = kcol / p.Cin;
+  c = kcol - t * p.Cin;
+  dy = t / kw;
+  dx = t - dy * kw;
+  return true;
+}
+
+// the block's tile -> the slab [K][N] of its pixel-range split; tile row -> slab row k0 + row = (tap, cin)
+template <int TM, int TN>
+__device__ __forceinline__ void store_wgrad_slab(const WgradP& p, int split, int k0, int n0, const f32x16 (&acc)[TM][TN], int lane,
+                                                 int wm, int wn) {
+  store_slab<TM, TN>(p.slab + (size_t)split * p.K * p.N, p.N, acc, lane, wm, wn, n0,
+                     [&](int r, long long& row) { row = k0 + r; return k0 + r < p.K; });
 }
 
 // (HIP's second launch bound is waves per SIMD: 3 = three 256-thread blocks per CU, 4 = two 512-thread blocks or one of 1024)
@@ -1459,24 +1371,17 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N > 4 ? 4 
   float* Bs = smem + 32 * LDA;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-  int tile_, split;
-  wgrad_block_map(tile_, split);
+  // XCD-aware block order: the (k, n) tiles of ONE pixel-range split read the same pixels of both operands and are siblings
+  int split, tile_;
+  xcd_block_map(gridDim.z, gridDim.x * gridDim.y, split, tile_);
   const int k0 = (tile_ % gridDim.x) * BM, n0 = (tile_ / gridDim.x) * BN;
   int s, pad, kw;
-  geom(p.kind, s, pad, kw);
+  geom(p.kind, 1, 0, 1, s, pad, kw);
 
   const int acol4 = tid % (BM / 4), arow = tid / (BM / 4);
   const int bcol4 = tid % (BN / 4), brow = tid / (BN / 4);
-  // this thread's 4 gathered columns: fixed (tap, channel) for the whole pixel loop
-  const int kcol = k0 + acol4 * 4;
-  const bool kvalid = kcol < p.K;
-  int c = 0, dy = 0, dx = 0;
-  if (kvalid) {
-    const int t = kcol / p.Cin;
-    c = kcol - t * p.Cin;
-    dy = t / kw;
-    dx = t - dy * kw;
-  }
+  int c, dy, dx;
+  const bool kvalid = wgrad_col(p, k0 + acol4 * 4, kw, c, dy, dx);   // this thread's 4 gathered columns
   const bool from_vec = c < p.Cc;
   const int nb = n0 + bcol4 * 4;
   const bool nvalid = nb < p.N;
@@ -1507,9 +1412,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N > 4 ? 4 
     for (int q = 0; q < APASS; ++q) {
       const int m = pc * 32 + arow + q * AROWS;
       if (APRED && arow + q * AROWS >= 32) continue;
-      const int b = m >> p.lgHoWo;
-      const int r = m & ((1 << p.lgHoWo) - 1);
-      const int oy = r >> p.lgWo, ox = r & (p.Wo - 1);
+      int b, oy, ox;
+      row_pixel(p, m, b, oy, ox);
       const int iy = oy * s - pad + dy, ix = ox * s - pad + dx;
       const bool ok = kvalid && m < p.M && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
       if constexpr (AACT) {
@@ -1528,12 +1432,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N > 4 ? 4 
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int c_begin = split * p.cps;
   const int c_end = min(p.nchunks, c_begin + p.cps);
@@ -1566,20 +1465,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N > 4 ? 4 
     __syncthreads();
   }
 
-  const int l31 = lane & 31, lh = lane >> 5;
-  float* outp = p.slab + (size_t)split * p.K * p.N;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int krow = k0 + wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      if (krow >= p.K) continue;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * TN * 32 + j * 32 + l31;
-        if (n < p.N) outp[(size_t)krow * p.N + n] = acc[i][j][r];
-      }
-    }
+  store_wgrad_slab<TM, TN>(p, split, k0, n0, acc, lane, wm, wn);
 }
 
 // Split-bf16 weight gradient (see igemm_fwd_split_kernel).  The reduction index of this GEMM is the pixel, and both
@@ -1592,6 +1478,33 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ s16x4 lds_tr_read(const unsigned char* ptr) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(ptr));
+}
+
+// Transposed-read addressing of one operand ([pixel][row] image, ROWB bytes per pixel) for wave coordinate w and its T
+// MFMA tiles: 16-lane group g = lane >> 4 -> (h = g >> 1, 16-row block g & 1); ad[i][f] is the byte offset inside a plane
+// and a 16-pixel k-step of the 4-pixel half fragment f of tile i.
+template <int T, int ROWB>
+__device__ __forceinline__ void wgrad_tr_addr(int lane, int w, int (&ad)[T][2]) {
+  constexpr int MASK = ROWB / 16 - 1;
+  const int gi = lane & 15, gq = gi >> 2, gp = gi & 3;
+  const int gh = lane >> 5, gcb = (lane >> 4) & 1;
+  const int sw0 = (gq << 2) | (2 * gh);              // swizzle of pixel rows 8h + q (+ 16 ks); rows + 4: sw0 | 1
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const int prow = 8 * gh + 4 * f + gq;
+#pragma unroll
+    for (int i = 0; i < T; ++i) {
+      const int ch = ((w * T + i) * 32 + 16 * gcb) / 8 + (gp >> 1);
+      ad[i][f] = prow * ROWB + 16 * ((ch ^ (sw0 | f)) & MASK) + 8 * (gp & 1);
+    }
+  }
+}
+
+// one MFMA fragment (8 consecutive pixels of this lane's row) = two transposed 4-pixel reads
+__device__ __forceinline__ bf16x8 lds_tr_frag(const unsigned char* kstep, const int (&ad)[2]) {
+  const s16x4 lo = lds_tr_read(kstep + ad[0]);
+  const s16x4 hi = lds_tr_read(kstep + ad[1]);
+  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int NP>
@@ -1609,19 +1522,12 @@ __global__ __launch_bounds__(256, 3) void igemm_wgrad_split_kernel(WgradP p) {
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
   const int k0 = blockIdx.x * BM, n0 = blockIdx.y * BN, split = blockIdx.z;
   int s, pad, kw;
-  geom(p.kind, s, pad, kw);
+  geom(p.kind, 1, 0, 1, s, pad, kw);
 
   const int acol4 = tid % (BM / 4), arow = tid / (BM / 4);
   const int bcol4 = tid % (BN / 4), brow = tid / (BN / 4);
-  const int kcol = k0 + acol4 * 4;
-  const bool kvalid = kcol < p.K;
-  int c = 0, dy = 0, dx = 0;
-  if (kvalid) {
-    const int t = kcol / p.Cin;
-    c = kcol - t * p.Cin;
-    dy = t / kw;
-    dx = t - dy * kw;
-  }
+  int c, dy, dx;
+  const bool kvalid = wgrad_col(p, k0 + acol4 * 4, kw, c, dy, dx);
   const bool from_vec = c < p.Cc;
   const int nb = n0 + bcol4 * 4;
   const bool nvalid = nb < p.N;
@@ -1636,9 +1542,8 @@ __global__ __launch_bounds__(256, 3) void igemm_wgrad_split_kernel(WgradP p) {
 #pragma unroll
     for (int q = 0; q < APASS; ++q) {
       const int m = pc * 32 + arow + q * AROWS;
-      const int b = m >> p.lgHoWo;
-      const int r = m & ((1 << p.lgHoWo) - 1);
-      const int oy = r >> p.lgWo, ox = r & (p.Wo - 1);
+      int b, oy, ox;
+      row_pixel(p, m, b, oy, ox);
       const int iy = oy * s - pad + dy, ix = ox * s - pad + dx;
       const bool ok = kvalid && m < p.M && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
       if (from_vec) ra[q] = bload4(rc_rs, ok ? b * p.Cc * 4 + ccolb : S2I_OOB);
@@ -1652,32 +1557,11 @@ __global__ __launch_bounds__(256, 3) void igemm_wgrad_split_kernel(WgradP p) {
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
-  // transposed-read addressing of this lane (see header): group g = lane >> 4 -> (h = g >> 1, 16-row block g & 1)
-  const int gi = lane & 15, gq = gi >> 2, gp = gi & 3;
-  const int gh = lane >> 5, gcb = (lane >> 4) & 1;
-  const int sw0 = (gq << 2) | (2 * gh);              // swizzle of pixel rows 8h + q (+ 16 ks); rows + 4: sw0 | 1
-  int aad[TM][2], bad[TN][2];                        // byte offsets inside a plane for the two 4-pixel half fragments
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    const int prow = 8 * gh + 4 * f + gq;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int ch = ((wm * TM + i) * 32 + 16 * gcb) / 8 + (gp >> 1);
-      aad[i][f] = prow * AROWB + 16 * ((ch ^ (sw0 | f)) & AMASK) + 8 * (gp & 1);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int ch = ((wn * TN + j) * 32 + 16 * gcb) / 8 + (gp >> 1);
-      bad[j][f] = prow * BROWB + 16 * ((ch ^ (sw0 | f)) & BMASK) + 8 * (gp & 1);
-    }
-  }
+  int aad[TM][2], bad[TN][2];
+  wgrad_tr_addr<TM, AROWB>(lane, wm, aad);
+  wgrad_tr_addr<TN, BROWB>(lane, wn, bad);
 
   const int c_begin = split * p.cps;
   const int c_end = min(p.nchunks, c_begin + p.cps);
@@ -1711,20 +1595,13 @@ __global__ __launch_bounds__(256, 3) void igemm_wgrad_split_kernel(WgradP p) {
 #pragma unroll
       for (int pl = 0; pl < NP; ++pl)
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          const s16x4 lo = lds_tr_read(As + pl * APLANE + ks * 16 * AROWB + aad[i][0]);
-          const s16x4 hi = lds_tr_read(As + pl * APLANE + ks * 16 * AROWB + aad[i][1]);
-          a[pl][i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
+        for (int i = 0; i < TM; ++i)
+          a[pl][i] = lds_tr_frag(As + pl * APLANE + ks * 16 * AROWB, aad[i]);
 #pragma unroll
       for (int pb = NP - 1; pb >= 0; --pb) {
         bf16x8 b[TN];
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const s16x4 lo = lds_tr_read(Bs + pb * BPLANE + ks * 16 * BROWB + bad[j][0]);
-          const s16x4 hi = lds_tr_read(Bs + pb * BPLANE + ks * 16 * BROWB + bad[j][1]);
-          b[j] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-        }
+        for (int j = 0; j < TN; ++j) b[j] = lds_tr_frag(Bs + pb * BPLANE + ks * 16 * BROWB, bad[j]);
 #pragma unroll
         for (int pa = NP - 1 - pb; pa >= 0; --pa)
 #pragma unroll
@@ -1737,20 +1614,7 @@ __global__ __launch_bounds__(256, 3) void igemm_wgrad_split_kernel(WgradP p) {
     __syncthreads();
   }
 
-  const int l31 = lane & 31, lh = lane >> 5;
-  float* outp = p.slab + (size_t)split * p.K * p.N;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int krow = k0 + wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      if (krow >= p.K) continue;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * TN * 32 + j * 32 + l31;
-        if (n < p.N) outp[(size_t)krow * p.N + n] = acc[i][j][r];
-      }
-    }
+  store_wgrad_slab<TM, TN>(p, split, k0, n0, acc, lane, wm, wn);
 }
 
 // Weight gradient with BOTH operands stored as bf16 (bf16 activation mode): the structure of igemm_wgrad_split_kernel
@@ -1780,22 +1644,16 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N > 4 ? 4 
   unsigned char* Bs = smem + PC * AROWB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-  int tile_, split;
-  wgrad_block_map(tile_, split);
+  // XCD-aware block order: the (k, n) tiles of ONE pixel-range split read the same pixels of both operands and are siblings
+  int split, tile_;
+  xcd_block_map(gridDim.z, gridDim.x * gridDim.y, split, tile_);
   const int k0 = (tile_ % gridDim.x) * BM, n0 = (tile_ / gridDim.x) * BN;
   int s, pad, kw;
-  geom(p.kind, s, pad, kw);
+  geom(p.kind, 1, 0, 1, s, pad, kw);
   const int acol8 = tid % ATPR, arow = tid / ATPR;
   const int bcol8 = tid % BTPR, brow = tid / BTPR;
-  const int kcol = k0 + acol8 * 8;
-  const bool kvalid = kcol < p.K;
-  int c = 0, dy = 0, dx = 0;
-  if (kvalid) {
-    const int t = kcol / p.Cin;
-    c = kcol - t * p.Cin;
-    dy = t / kw;
-    dx = t - dy * kw;
-  }
+  int c, dy, dx;
+  const bool kvalid = wgrad_col(p, k0 + acol8 * 8, kw, c, dy, dx);
   const int nb = n0 + bcol8 * 8;
   const bool nvalid = nb < p.N;
   const __amdgpu_buffer_rsrc_t ra_rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, 0, p.a_bytes, 0x00020000);
@@ -1805,9 +1663,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N > 4 ? 4 
 #pragma unroll
     for (int q = 0; q < APASS; ++q) {
       const int m = pc * PC + arow + q * AROWS;
-      const int b = m >> p.lgHoWo;
-      const int r = m & ((1 << p.lgHoWo) - 1);
-      const int oy = r >> p.lgWo, ox = r & (p.Wo - 1);
+      int b, oy, ox;
+      row_pixel(p, m, b, oy, ox);
       const int iy = oy * s - pad + dy, ix = ox * s - pad + dx;
       if constexpr (A32) {
         const bool rowok = kvalid && m < p.M && iy >= 0 && iy < p.H;
@@ -1830,31 +1687,11 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N > 4 ? 4 
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
-  const int gi = lane & 15, gq = gi >> 2, gp = gi & 3;
-  const int gh = lane >> 5, gcb = (lane >> 4) & 1;
-  const int sw0 = (gq << 2) | (2 * gh);
   int aad[TM][2], bad[TN][2];
-#pragma unroll
-  for (int f = 0; f < 2; ++f) {
-    const int prow = 8 * gh + 4 * f + gq;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int ch = ((wm * TM + i) * 32 + 16 * gcb) / 8 + (gp >> 1);
-      aad[i][f] = prow * AROWB + 16 * ((ch ^ (sw0 | f)) & AMASK) + 8 * (gp & 1);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int ch = ((wn * TN + j) * 32 + 16 * gcb) / 8 + (gp >> 1);
-      bad[j][f] = prow * BROWB + 16 * ((ch ^ (sw0 | f)) & BMASK) + 8 * (gp & 1);
-    }
-  }
+  wgrad_tr_addr<TM, AROWB>(lane, wm, aad);
+  wgrad_tr_addr<TN, BROWB>(lane, wn, bad);
 
   const int c_begin = split * p.cps;
   const int c_end = min(p.nchunks, c_begin + p.cps);
@@ -1877,17 +1714,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N > 4 ? 4 
     for (int ks = 0; ks < PC / 16; ++ks) {
       bf16x8 a[TM], b[TN];
 #pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const s16x4 lo = lds_tr_read(A_ + ks * 16 * AROWB + aad[i][0]);
-        const s16x4 hi = lds_tr_read(A_ + ks * 16 * AROWB + aad[i][1]);
-        a[i] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-      }
+      for (int i = 0; i < TM; ++i) a[i] = lds_tr_frag(A_ + ks * 16 * AROWB, aad[i]);
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const s16x4 lo = lds_tr_read(B_ + ks * 16 * BROWB + bad[j][0]);
-        const s16x4 hi = lds_tr_read(B_ + ks * 16 * BROWB + bad[j][1]);
-        b[j] = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-      }
+      for (int j = 0; j < TN; ++j) b[j] = lds_tr_frag(B_ + ks * 16 * BROWB, bad[j]);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1904,20 +1733,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (WAVES_M * WAVES_N > 4 ? 4 
     __syncthreads();
   }
 
-  const int l31 = lane & 31, lh = lane >> 5;
-  float* outp = p.slab + (size_t)split * p.K * p.N;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int krow = k0 + wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      if (krow >= p.K) continue;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * TN * 32 + j * 32 + l31;
-        if (n < p.N) outp[(size_t)krow * p.N + n] = acc[i][j][r];
-      }
-    }
+  store_wgrad_slab<TM, TN>(p, split, k0, n0, acc, lane, wm, wn);
 }
 
 // Weight gradient of a 3x3 stride-1 convolution over a wide map with few channels (the generator at 64x64 and
@@ -1975,12 +1791,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 3) void wgrad_k3_rows_kerne
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   const int l31 = lane & 31, lh = lane >> 5;
   int aoff[TM];  // row tile -> (horizontal tap, channel half) -> offset inside the halo row segment
@@ -2042,18 +1853,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, 3) void wgrad_k3_rows_kerne
     __syncthreads();
   }
 
-  float* outp = p.slab + (size_t)split * p.K * p.N;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int krow = dy0 * 3 * CIN + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;  // (dy*3 + dx) * CIN + c
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * TN * 32 + j * 32 + l31;
-        if (n < p.N) outp[(size_t)krow * p.N + n] = acc[i][j][r];
-      }
-    }
+  // slab row (dy*3 + dx) * CIN + c; the block's 3 * CIN * DYS rows all exist
+  store_slab<TM, TN>(p.slab + (size_t)split * p.K * p.N, p.N, acc, lane, wm, wn, n0,
+                     [&](int r, long long& row) { row = dy0 * 3 * CIN + r; return true; });
 }
 
 // Weight gradient of a 3x3 convolution with at most 4 output channels (GET_IMAGE_G's conv3x3 -> RGB, model.py:287-298):
@@ -3257,12 +3059,7 @@ __global__ __launch_bounds__(256, 3) void conv2d_fwd_kernel(Conv2dP p) {
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   fetch(0);
   for (int kc = 0; kc < p.nchunks; ++kc) {
@@ -3279,26 +3076,8 @@ __global__ __launch_bounds__(256, 3) void conv2d_fwd_kernel(Conv2dP p) {
     __syncthreads();
   }
 
-  const int l31 = lane & 31, lh = lane >> 5;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      if (m >= p.M) continue;
-      float* yr = p.y + (size_t)m * p.ldy + p.coff;
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = n0 + wn * TN * 32 + j * 32 + l31;
-        if (n < p.N) {
-          float v = acc[i][j][r];
-          if (p.bias) v += p.bias[n];
-          if (p.relu) v = fmaxf(v, 0.f);
-          yr[n] = v;
-        }
-      }
-    }
-  }
+  store_tile<TM, TN>(p.y + p.coff, p.ldy, p.N, false, p.bias, p.relu ? S2I_ACT_RELU : S2I_ACT_NONE, 0, acc, lane, wm, wn, n0,
+                     [&](int r, long long& row) { row = m0 + r; return m0 + r < p.M; });
 }
 
 // Block tile from a round model: blocks are issued in rounds of 3 per CU; a round's time grows with the tile's work over
