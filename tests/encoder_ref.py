@@ -1,0 +1,145 @@
+"""Plain fp64 restatement of the speech encoder's launches (tests/test_encoder_launches_gpu.py).
+
+One function per launch kind of speech_encoder.CNNRNN._encode, taking exactly the operands the kernel sees: activations
+NHWC [B, 1, W, C], BatchNorm-folded weights (O, I, taps) and biases as CNNRNN._prepare() produces them, the LSTM's input
+projections for all steps and directions as one [B, L, D*4*Hd] tensor, W_hh per direction in torch's (4*Hd, Hd) layout
+with the gate order i, f, g, o.  Stock torch ops only (pad, slicing, matmul, max_pool2d, sigmoid, tanh), float64, on
+whatever device the operands live on.  fold() restates _prepare()'s BatchNorm folding from the module's own layers, and
+encode() composes everything into the whole network; tests/test_encoder_ref.py pins that composition to the oracle."""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+BN_EPS = 1e-5
+
+
+# ---- launches --------------------------------------------------------------------------------------------------------
+def conv1d_pre(x, w, bias, k, stride, pad):
+    """Temporal convolution before its activation.  x [B, 1, W, C], w (O, C, k), bias (O,) or None -> [B, 1, Wo, O],
+    Wo = (W + 2 pad - k) // stride + 1: out[b, ox, o] = bias[o] + sum_t sum_c x[b, ox*stride - pad + t, c] w[o, c, t],
+    positions outside [0, W) contributing nothing."""
+    B, H, W, C = x.shape
+    assert H == 1 and tuple(w.shape[1:]) == (C, k), (tuple(x.shape), tuple(w.shape), k)
+    Wo = (W + 2 * pad - k) // stride + 1
+    xp = F.pad(x[:, 0], (0, 0, pad, pad))                                  # [B, W + 2 pad, C]
+    y = x.new_zeros((B, Wo, w.shape[0]))
+    for t in range(k):
+        y += xp[:, t:t + stride * (Wo - 1) + 1:stride] @ w[:, :, t].t()
+    if bias is not None:
+        y = y + bias
+    return y.unsqueeze(1)
+
+
+def conv1d(x, w, bias, k, stride, pad):
+    """S2I_CONV_1D with its fused bias + ReLU."""
+    return torch.relu(conv1d_pre(x, w, bias, k, stride, pad))
+
+
+def k1(x, w, bias=None, relu=False):
+    """S2I_CONV_K1: x [..., C] times w (N, C) transposed, plus bias (N,), optionally ReLU."""
+    y = x @ w.t()
+    if bias is not None:
+        y = y + bias
+    return torch.relu(y) if relu else y
+
+
+def maxpool_w3s2(x):
+    """MaxPool2d((1, 3), (1, 2), (0, 1)) on NHWC [B, H, W, C] -> [B, H, W / 2, C]; the padding never wins."""
+    return F.max_pool2d(x.permute(0, 3, 1, 2), (1, 3), (1, 2), (0, 1)).permute(0, 2, 3, 1).contiguous()
+
+
+def lstm_step(xproj_t, h, c, w_hh):
+    """One LSTM cell update of one direction from a GIVEN state.  xproj_t (B, 4*Hd) = W_ih x_t + b_ih + b_hh, h and c
+    (B, Hd), w_hh (4*Hd, Hd), gates in torch's order i, f, g, o -> (h', c')."""
+    Hd = h.shape[1]
+    z = xproj_t + h @ w_hh.t()
+    i, f, g, o = z[:, :Hd], z[:, Hd:2 * Hd], z[:, 2 * Hd:3 * Hd], z[:, 3 * Hd:]
+    c2 = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+    return torch.sigmoid(o) * torch.tanh(c2), c2
+
+
+def time_index(step, length, reverse):
+    """Packed-sequence rule: the time position a sequence of `length` valid steps visits at recurrence step `step`
+    (forward: step; reverse: length - 1 - step), or None once it has finished (step >= length)."""
+    if step >= length:
+        return None
+    return length - 1 - step if reverse else step
+
+
+def lstm_sequence(xproj, lens, w_hh, Hd):
+    """All steps, all directions.  xproj [B, L, D*4*Hd] (direction d in columns [d*4*Hd, (d+1)*4*Hd)), lens B ints,
+    w_hh a list of D matrices (direction 1 is the reverse one) -> out [B, L, D*Hd], zero at positions >= len.  A
+    finished sequence's state is simply not touched any more."""
+    B, L, _ = xproj.shape
+    D = len(w_hh)
+    lens = [int(v) for v in lens]
+    out = xproj.new_zeros((B, L, D * Hd))
+    for d in range(D):
+        h = xproj.new_zeros((B, Hd))
+        c = xproj.new_zeros((B, Hd))
+        for step in range(max(lens)):
+            live = [b for b in range(B) if time_index(step, lens[b], d == 1) is not None]
+            ts = [time_index(step, lens[b], d == 1) for b in live]
+            h2, c2 = lstm_step(xproj[live, ts, d * 4 * Hd:(d + 1) * 4 * Hd], h[live], c[live], w_hh[d])
+            h[live], c[live] = h2, c2
+            out[live, ts, d * Hd:(d + 1) * Hd] = h2
+    return out
+
+
+def time_mean(x):
+    """x [B, T, C] -> [B, C], the mean over ALL T positions (the zeros of the padded ones included)."""
+    return x.mean(1)
+
+
+# ---- BatchNorm folding and the whole network -------------------------------------------------------------------------
+def fold(net):
+    """CNNRNN._prepare() in fp64 from the module's own layers: eval-mode BatchNorms folded into the convolution that
+    precedes them, the leading scalar BatchNorm2d(1) into the first one.  Returns dict(layers, w_ih, b_ih, w_hh) with
+    layers a list of ("k1", w (O, C), bias), ("c1d", w (O, C, k), bias, (k, stride, pad)) and ("pool",)."""
+    d = lambda t: t.detach().double()
+    bn0 = net.Conv[0]
+    a0 = (d(bn0.weight) / torch.sqrt(d(bn0.running_var) + BN_EPS)).reshape(())
+    b0 = (d(bn0.bias) - d(bn0.running_mean) * a0).reshape(())
+    layers = []
+    for m in list(net.Conv)[1:]:
+        if isinstance(m, nn.MaxPool2d):
+            assert (m.kernel_size, m.stride, m.padding) == ((1, 3), (1, 2), (0, 1)), m
+            layers.append(("pool",))
+            continue
+        conv, bn = m[0], m[1]
+        s = d(bn.weight) / torch.sqrt(d(bn.running_var) + BN_EPS)
+        w = d(conv.weight) * s.view(-1, 1, 1, 1)
+        bias = d(bn.bias) - d(bn.running_mean) * s
+        if not layers:      # conv(a0 x + b0) = a0 conv(x) + b0 sum(w); the (n_mels x 1) kernel spans the mel axis
+            assert conv.kernel_size[1] == 1 and conv.in_channels == 1, conv
+            bias = bias + b0 * w.sum(dim=(1, 2, 3))
+            layers.append(("k1", (w * a0).reshape(w.shape[0], w.shape[2]), bias))
+        else:
+            assert conv.kernel_size[0] == 1, conv
+            layers.append(("c1d", w[:, :, 0, :], bias, (conv.kernel_size[1], conv.stride[1], conv.padding[1])))
+    sfx = ["", "_reverse"][:net.num_direction]
+    rnn = net.RNN
+    return dict(layers=layers,
+                w_ih=torch.cat([d(getattr(rnn, "weight_ih_l0" + s_)) for s_ in sfx], 0),
+                b_ih=torch.cat([d(getattr(rnn, "bias_ih_l0" + s_)) + d(getattr(rnn, "bias_hh_l0" + s_)) for s_ in sfx], 0),
+                w_hh=[d(getattr(rnn, "weight_hh_l0" + s_)) for s_ in sfx])
+
+
+def conv_stack(prep, x):
+    """x [B, 1, T, n_mels] -> [B, 1, T / 64, 1024] through prep["layers"]."""
+    for layer in prep["layers"]:
+        if layer[0] == "pool":
+            x = maxpool_w3s2(x)
+        elif layer[0] == "k1":
+            x = k1(x, layer[1], layer[2], relu=True)
+        else:
+            x = conv1d(x, layer[1], layer[2], *layer[3])
+    return x
+
+
+def encode(prep, x, lens):
+    """The whole encoder on folded operands: x [B, 1, T, n_mels] float64 -> (words (B, D*Hd, L), sent (B, D*Hd))."""
+    feat = conv_stack(prep, x)[:, 0]                                           # [B, L, 1024]
+    Hd = prep["w_hh"][0].shape[1]
+    out = lstm_sequence(k1(feat, prep["w_ih"], prep["b_ih"]), lens, prep["w_hh"], Hd)
+    return out.transpose(1, 2), time_mean(out)
