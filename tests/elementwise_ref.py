@@ -50,6 +50,14 @@ def bn_finalize(part, G, count, gamma, beta, rm=None, rv=None, nbt=None, momentu
     return coef, rm, rv, nbt
 
 
+def bn_eval_coeffs(gamma, beta, running_mean, running_var, eps=1e-5):
+    """-> coef [1][4][C] of nn.BatchNorm in eval mode: mean = running_mean, invstd = 1 / sqrt(running_var + eps),
+    scale = gamma * invstd, shift = beta - mean * scale (one group: every row of the launch)."""
+    invstd = 1.0 / torch.sqrt(running_var + eps)
+    scale = gamma * invstd
+    return torch.stack((running_mean, invstd, scale, beta - running_mean * scale)).unsqueeze(0)
+
+
 def bn_bwd_finalize(part, G, count, dgamma=None, dbeta=None, accumulate=False):
     """-> (red2 [G][2][C], dgamma, dbeta): means per group and totals over the groups, added to the given values when
     accumulating."""

@@ -68,6 +68,33 @@ def test_bn_act_chain_matches_autograd(act, residual, G):
         torch.testing.assert_close(R.bn_act_bwd_reduce(y, wide, G, coef, act, nparts), part)
 
 
+@pytest.mark.parametrize("act,residual", [(ACT_GLU, False), (ACT_LRELU, False), (ACT_NONE, False), (ACT_NONE, True),
+                                          (ACT_LRELU, True)])
+def test_bn_eval_chain_matches_batch_norm_eval(act, residual):
+    """bn_eval_coeffs + the apply = F.batch_norm(training=False) on running statistics with small variances (1e-3 .. 2)
+    and means of both signs, + GLU / LeakyReLU(0.2) / identity (+ residual); the wrong restatements the GPU replay must
+    reject (eps left out, a batch statistic for the running one) differ from it."""
+    g = torch.Generator().manual_seed(31 + act)
+    B, C, H, W = 3, 8, 5, 4
+    x = torch.randn(B, C, H, W, generator=g, dtype=D64)
+    gamma, beta = torch.randn(C, generator=g, dtype=D64), torch.randn(C, generator=g, dtype=D64)
+    rm = torch.randn(C, generator=g, dtype=D64)
+    rv = torch.exp(torch.rand(C, generator=g, dtype=D64) * (torch.log(torch.tensor(2000.0, dtype=D64)))) * 1e-3
+    assert float(rv.min()) >= 1e-3 and float(rv.max()) <= 2.0 and bool((rm < 0).any()) and bool((rm > 0).any())
+    z = F.batch_norm(x, rm.clone(), rv.clone(), gamma, beta, training=False, eps=1e-5)
+    want = F.glu(z, dim=1) if act == ACT_GLU else (F.leaky_relu(z, 0.2) if act == ACT_LRELU else z)
+    res = torch.randn(want.shape, generator=g, dtype=D64) if residual else None
+    if residual:
+        want = want + res
+    coef = R.bn_eval_coeffs(gamma, beta, rm, rv, 1e-5)
+    assert coef.shape == (1, 4, C) and torch.equal(coef[0, 0], rm)
+    got = R.bn_act_forward(_rows(x), 1, coef, act, None if res is None else _rows(res))
+    assert torch.allclose(got, _rows(want), rtol=1e-12, atol=1e-12)
+    assert not torch.allclose(R.bn_act_forward(_rows(x), 1, R.bn_eval_coeffs(gamma, beta, rm, rv, 0.0), act), _rows(z if act == ACT_NONE else want), rtol=1e-6, atol=1e-6) or residual
+    zt = F.batch_norm(x, None, None, gamma, beta, training=True, eps=1e-5)
+    assert not torch.allclose(z, zt, rtol=1e-3, atol=1e-3)
+
+
 @pytest.mark.parametrize("G", [1, 2, 3])
 def test_bn_finalize_matches_batchnorm2d(G):
     """Finalize + apply = nn.BatchNorm2d (momentum 0.1, eps 1e-5) in training mode run on the G stacked batches one after

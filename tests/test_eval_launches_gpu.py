@@ -1,0 +1,997 @@
+"""Every launch of the three inference pipelines, at its production shape, against a plain fp64 reference.
+
+The pipelines whose numbers end up in a results table run shapes no training test reaches: the generator in .eval() under
+gan_metrics.score_generator (launches of 96, 48 and 50 stacked images, stats=False, one BatchNorm group, running
+statistics), the Inception-v3 scorer (chunks of 48, 24, 5 and 2 images) and the GoogLeNet feature extractor (480 and 10
+views).  s2i_conv2d_plan picks the block tile from M = B * Ho * Wo, so these launches are tested at these batches:
+
+  * census: score_generator on a synthetic loader of full-width nets (24 items x 10 sentences, then 5 x 10, uint8 real
+    images, PNG output on) with a GeneratorScorer on a seeded Inception-v3, and GoogLeNetFeatures on 49 ragged images
+    (chunks of 48 and 1), with the dispatchers of ops.py wrapped (as tests/test_step_launches_gpu.py does) and every s2i_*
+    library call recorded (as tests/test_step_elementwise_gpu.py does; s2i_conv2d_forward descriptors field by field).
+    The deduplicated records are tests/eval_launches.json; test_census_matches_committed_file fails on any new or vanished
+    record.  Regenerate it with `python tests/test_eval_launches_gpu.py`.  The convolutions of both classifier networks
+    must also equal the table derived from architecture() and the map sizes; every dispatcher record has stats=False and
+    the recorder refuses in_src / a_src / conv1d.
+  * replay: every record re-run through the same entry point on fresh seeded operands; EVERY output element of every
+    image is compared (the fp64 reference is computed in chunks of images).  Channels outside [coff, coff + N) and the
+    rows after the last pixel carry a sentinel and must be bit-identical afterwards.
+  * bounds: convolutions |out - ref| <= 2^-20 * absref (GAMMA["fp32/conv"] of the train-step replay, taken over, not
+    re-measured); s2i_bn_eval_coeffs GAMMA["bn_finalize"], the eval BatchNorm apply GAMMA["bn_forward"]; max pools
+    bit-identical; average pools 2e-6 (tests/test_inception_gpu.py) and (n + 2) * 2^-24 * absref for the n-term mean;
+    LRN, the input stages and softmax the bounds of tests/test_inception_gpu.py / tests/test_googlenet_gpu.py; moments the
+    bound of tests/test_gan_metrics_gpu.py; uint8 conversions bit-identical.
+  * power, per convolution record: the comparison must FAIL against a reference with (a) the last input channel removed,
+    (b) tap (kh-1, kw-1) removed, (c) replicate instead of zero padding where there is padding, (d) the bias removed where
+    there is one, (e) the last image's input zeroed.  Pools: the right column / bottom row dropped, the floor output rule
+    for the ceil-rule pools.  BatchNorm: eps left out, a batch-size correction of the variance, the mean's sign flipped,
+    GLU halves swapped.
+  * composition: rows of a 96-image Inception run, a 48-image GoogLeNet chunk and a 96-image eval G launch against
+    single-image runs of the same inputs (first, middle, last image), and eval G at full width against the fp64 oracle.
+
+Measured on one MI355X, default planner (the module prints these at the end of a run):
+  records: generator 110 distinct of 252 calls (51 dispatcher launches at 96, 48 and 50 images), Inception 280 of 999,
+  GoogLeNet 132 of 144; 522 replays, 3 scalar-gather edges.
+  worst ratio per family, bound in use beside it: generator convolutions 4.7e-7 (2^-20 = 9.5e-7), Inception conv2d
+  4.2e-7, GoogLeNet conv2d 4.1e-7, 3-channel edges 3.3e-7 (all 2^-20); average pools 3.0e-7 absolute (2e-6) and 2.7e-7 of
+  absref ((n + 2) 2^-24 = 6.6e-7 at n = 9); LRN + pool 1.9e-7 (2e-6); Inception input stage 7.4e-5 (1.0e-4 at 256 px);
+  GoogLeNet input stage 4.2e-5 (7.5e-5); softmax 2.1e-7 (1e-6); max pools, uint8 conversions bit-identical; BatchNorm
+  eval coefficients and apply inside GAMMA["bn_finalize"] / GAMMA["bn_forward"].
+  tiles planned by s2i_conv2d_plan for the recorded launches: Inception 128x128: 4, 128x64: 32, 64x64: 192; GoogLeNet
+  128x128: 19, 128x64: 31, 64x64: 58, all on the VEC gather (the production image is NHWC4); the scalar gather is
+  reached only by EDGE_CONV2D (tiles 128x64 and 64x64).
+  composition: Inception rows and GoogLeNet features of a full batch are bit-identical to single-image runs; eval G is
+  not (7.5e-7, split-K of the train-step forward planner, see test_eval_generator_images_do_not_depend_on_the_batch) and
+  is held to rtol 1e-3 / atol 1e-4 against the fp64 oracle instead: measured max |err| 2.2e-6 at 96 images.
+  No kernel bug was found.  With `(ix0[i] + kx) < W` loosened to `<= W` in the VEC gather of conv2d_fwd_kernel (tried
+  once, then reverted) 100 of the 339 conv2d replays fail.  Wall time 17 s for the replays plus 8 s for the census; the three existing launch-replay
+  modules take 21 + 10 + 3 s on the same machine.
+"""
+import ctypes
+import json
+import os
+import sys
+import time
+import zlib
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for _p in (ROOT, HERE):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import elementwise_ref as ER  # noqa: E402
+import googlenet_ref as GR  # noqa: E402
+import launch_ref as LR  # noqa: E402
+import test_step_elementwise_gpu as E  # noqa: E402
+import test_step_launches_gpu as S  # noqa: E402
+from helpers import CASES, build_nets  # noqa: E402
+from test_encoder_launches_gpu import _ModSpy  # noqa: E402
+from test_inception_cpu import random_state_dict  # noqa: E402
+from speech_to_image_translation_without_text_amd import _lib  # noqa: E402
+from speech_to_image_translation_without_text_amd._lib import (ACT_GLU, ACT_LRELU, ACT_NONE, DT_F32,  # noqa: E402
+                                                                LRN_THEN_POOL, POOL_AVG3S1, POOL_GLOBAL, POOL_MAX3S2,
+                                                                POOL_THEN_LRN)
+
+pytestmark = pytest.mark.gpu
+
+CENSUS_FILE = os.path.join(HERE, "eval_launches.json")
+PIPELINES = ("generator", "inception", "googlenet")
+GAMMA_CONV = S.GAMMA["fp32/conv"]                  # 2^-20: the same mma_chunk fp32 MFMA accumulation, held at K up to 8192
+U = 2.0 ** -24
+SENTINEL = 1234.5
+GUARD = 4096                                       # sentinel floats after the last output pixel
+CHUNK_ELEMS = 1 << 25                              # elements of the larger of a reference chunk's input and output
+
+# entry points of the inference pipelines that the train step does not call (include/s2i_hip.h order, stream left out)
+ARGS = dict(E.ARGS, **{
+    "s2i_conv2d_forward": "d x w bias y",
+    "s2i_pool2d": "mode x B H W C ldx y ldy coff",
+    "s2i_maxpool3": "x B H W C ldx stride pad y ldy coff",
+    "s2i_lrn_maxpool3": "order x B H W C ldx y ldy coff size alpha beta k",
+    "s2i_inception_prep": "img B Hin Win sb sc sh sw y S Cy",
+    "s2i_googlenet_prep": "img nbytes offsets hs ws B mean_b mean_g mean_r y",
+    "s2i_softmax_rows": "x rows cols ldx y ldy",
+    "s2i_bn_eval_coeffs": "C gamma beta running_mean running_var eps out",
+    "s2i_moments_accumulate": "x rows D ldx colsum gram",
+    "s2i_image_to_u8": "src lds dst npix",
+    "s2i_u8_to_image": "src dst B H W",
+})
+INCEPTION_FNS = ("s2i_conv2d_forward", "s2i_pool2d", "s2i_inception_prep", "s2i_softmax_rows")
+
+_WORST = {}
+_REJECTED = {}
+_TILES = {}
+
+
+def _note(fam, ratio, what, bound):
+    if fam not in _WORST or ratio > _WORST[fam][0]:
+        _WORST[fam] = (ratio, bound, what)
+
+
+def _rejected(fam, name):
+    _REJECTED["%s: %s" % (fam, name)] = _REJECTED.get("%s: %s" % (fam, name), 0) + 1
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report():
+    t0 = time.time()
+    yield
+    print("\neval launch replay, %.0f s: worst measured value per family (bound in use)" % (time.time() - t0))
+    for fam in sorted(_WORST):
+        print("  %-22s %.3e  (%.3e)  %s" % ((fam,) + _WORST[fam]))
+    print("conv2d tiles planned (pipeline, tile, VEC): launches")
+    for k in sorted(_TILES):
+        print("  %-34s %d" % (k, _TILES[k]))
+    print("mutations rejected (family: mutation, cases):")
+    for k in sorted(_REJECTED):
+        print("  %-64s %d" % (k, _REJECTED[k]))
+
+
+def _canon(rec):
+    return json.dumps(rec, sort_keys=True)
+
+
+# ---- the production inputs -------------------------------------------------------------------------------------------
+SENTENCES = 10
+LOADER_ITEMS = (24, 5)
+
+
+def _full_case():
+    return CASES["full3_fwd"]
+
+
+def _eval_generator(gpu):
+    """The full-width generator, seeded, with non-trivial running statistics, in .eval() on the GPU."""
+    netG, _ = build_nets(_full_case())
+    g = torch.Generator().manual_seed(3)
+    for k, v in netG.state_dict().items():
+        if k.endswith("running_mean"):
+            v.copy_(0.1 * torch.randn(v.shape, generator=g))
+        elif k.endswith("running_var"):
+            v.copy_(0.5 + torch.rand(v.shape, generator=g))
+    return netG.to(gpu).eval()
+
+
+def _loader(case):
+    g = torch.Generator().manual_seed(11)
+    out, k = [], 0
+    for B in LOADER_ITEMS:
+        imgs = [torch.randint(0, 256, (B, 64 << i, 64 << i, 3), generator=g, dtype=torch.uint8) for i in range(3)]
+        emb = torch.randn(B, SENTENCES, case["t"], generator=g)
+        out.append((imgs, emb, ["bird%d/img%d" % (j % 2, j) for j in range(k, k + B)]))
+        k += B
+    return out
+
+
+def _inception_weights():
+    sd = random_state_dict(seed=5)
+    sd["fc.weight"] = sd["fc.weight"] * 0.01
+    return sd
+
+
+def _ragged49():
+    """49 uint8 RGB images of differing extents, smaller and larger than 227 on either side."""
+    rng = np.random.default_rng(49)
+    out = []
+    for i in range(49):
+        h, w = 150 + (37 * i) % 211, 160 + (53 * i) % 301
+        out.append(rng.integers(0, 256, (h, w, 3)).astype(np.uint8))
+    return out
+
+
+# ---- census ----------------------------------------------------------------------------------------------------------
+def _spy(recs, mp, *modules):
+    from speech_to_image_translation_without_text_amd import ops
+    proxy = E._Recorder(_lib.load(), recs, ARGS)
+    mp.setattr(ops, "_lib_ready", lambda: (_lib.require_device(), proxy)[1])
+    for m in modules:
+        mp.setattr(m, "_lib", _ModSpy(proxy))
+
+
+def _record_score(gpu, mp, tmp):
+    from speech_to_image_translation_without_text_amd import gan_metrics as GM, inception as I, model
+    recs = []
+    netG = _eval_generator(gpu)
+    S.wrap_dispatchers(mp, recs)
+    _spy(recs, mp, GM, I)
+    scorer = GM.GeneratorScorer(model.INCEPTION_V3(weights=_inception_weights()), sum(LOADER_ITEMS) * SENTENCES, gpu)
+    n = GM.score_generator(netG, _loader(_full_case()), scorer, seed=4, save_images=tmp)
+    torch.cuda.synchronize()
+    assert n == sum(LOADER_ITEMS) and scorer.n_fake == n * SENTENCES and scorer.real.n == n
+    return recs
+
+
+def _record_googlenet(gpu, mp):
+    from speech_to_image_translation_without_text_amd import googlenet as G
+    recs = []
+    net = G.GoogLeNetFeatures(GR.random_weights(0), gpu)
+    _spy(recs, mp, G)
+    out = net(_ragged49())
+    torch.cuda.synchronize()
+    assert tuple(out.shape) == (49, 10, 1024)
+    return recs
+
+
+def take_census(gpu, tmp):
+    from speech_to_image_translation_without_text_amd import ops
+    assert ops.TILE_ROWS == 0 and ops.MATH_PLANES == 0 and not ops.DEFER_ACT and not ops.ACT_BF16, "default paths"
+    raw = {}
+    with pytest.MonkeyPatch.context() as mp, torch.no_grad():
+        score = _record_score(gpu, mp, tmp)
+    raw["inception"] = [r for r in score if r["fn"] in INCEPTION_FNS]
+    raw["generator"] = [r for r in score if r["fn"] not in INCEPTION_FNS]
+    torch.cuda.empty_cache()
+    with pytest.MonkeyPatch.context() as mp, torch.no_grad():
+        raw["googlenet"] = _record_googlenet(gpu, mp)
+    torch.cuda.empty_cache()
+    calls = {k: len(v) for k, v in raw.items()}
+    return {k: [json.loads(s) for s in sorted({_canon(r) for r in raw[k]})] for k in PIPELINES}, calls
+
+
+def _load_census():
+    if not os.path.exists(CENSUS_FILE):
+        return {}
+    with open(CENSUS_FILE) as fp:
+        return json.load(fp)
+
+
+@pytest.fixture(scope="module")
+def live_census(gpu, tmp_path_factory):
+    return take_census(gpu, str(tmp_path_factory.mktemp("png")))
+
+
+def test_census_matches_committed_file(live_census):
+    live, calls = live_census
+    committed = _load_census()
+    for p in PIPELINES:
+        print("census %s: %d calls, %d distinct records" % (p, calls[p], len(live[p])))
+        have = {_canon(r) for r in committed.get(p, [])}
+        now = {_canon(r) for r in live[p]}
+        assert now == have, "%s: records not in tests/eval_launches.json: %s; listed but not launched: %s" % (
+            p, sorted(now - have)[:5], sorted(have - now)[:5])
+
+
+def test_eval_dispatcher_records_are_eval_mode(live_census):
+    """stats=False, one group, fp32, and (by the recorder's own assertions) no in_src / a_src / conv1d launch."""
+    recs = [r for r in live_census[0]["generator"] if not r["fn"].startswith("s2i_")]
+    assert recs and all(r["fn"] in ("conv_raw", "conv_any") for r in recs), sorted({r["fn"] for r in recs})
+    bad = [r for r in recs if r["stats"] or r["groups"] != 1 or r["out_dtype"] != "f32" or r["fast"]]
+    assert not bad, bad[:3]
+    assert {r["x"][0][0] for r in recs} == {96, 48, 50}, "G launches at %s images" % sorted({r["x"][0][0] for r in recs})
+    fwd = [r for r in live_census[0]["generator"] if r["fn"] == "s2i_bn_act_forward_dt"]
+    assert fwd and all(r["groups"] == 1 and r["dtype"] == DT_F32 for r in fwd)
+    assert not [r for r in live_census[0]["generator"] if r["fn"] == "s2i_bn_finalize"], "training statistics in eval"
+
+
+_GEOM = ("B", "H", "W", "C", "N", "kh", "kw", "sh", "sw", "ph", "pw", "Ho", "Wo", "relu")
+
+
+def _geom_set(recs):
+    return {tuple(r["d"][k] for k in _GEOM) for r in recs if r["fn"] == "s2i_conv2d_forward"}
+
+
+def expected_inception(B):
+    from speech_to_image_translation_without_text_amd import inception as I
+    size = {"Conv2d_1a_3x3": 299, "Conv2d_2a_3x3": 149, "Conv2d_2b_3x3": 147, "Conv2d_3b_1x1": 73, "Conv2d_4a_3x3": 73,
+            "Mixed_5": 35, "Mixed_6a": 35, "Mixed_6": 17, "Mixed_7a": 17, "Mixed_7": 8}
+    out = set()
+    for name, (cin, cout, kh, kw, sh, sw, ph, pw) in I.architecture(aux_logits=False).items():
+        blk = name.split(".")[0]
+        H = size.get(blk, size.get(blk[:7]))
+        Ho, Wo = (H + 2 * ph - kh) // sh + 1, (H + 2 * pw - kw) // sw + 1
+        out.add((B, H, H, 4 if name == "Conv2d_1a_3x3" else cin, cout, kh, kw, sh, sw, ph, pw, Ho, Wo, 1))
+    out.add((B, 1, 1, I.POOL3, I.CLASSES, 1, 1, 1, 1, 0, 0, 1, 1, 0))
+    return out
+
+
+def expected_googlenet(V):
+    from speech_to_image_translation_without_text_amd import googlenet as G
+    out = set()
+    for name, (cin, cout, k, s, p) in G.architecture().items():
+        Ho = G.layer_extent(name)
+        H = G.VIEW if name == "conv1/7x7_s2" else Ho
+        assert (H + 2 * p - k) // s + 1 == Ho, name
+        out.add((V, H, H, 4 if name == "conv1/7x7_s2" else cin, cout, k, k, s, s, p, p, Ho, Ho, 1))
+    return out
+
+
+def test_recorded_convolutions_equal_the_architecture_tables(live_census):
+    from speech_to_image_translation_without_text_amd import inception as I
+    live = live_census[0]
+    # Inception runs at 96, 48, 50, 24 and 5 images are chunks of at most MAX_BATCH: 48, 2 (= 50 - 48), 24 and 5
+    chunks = set()
+    for n in (96, 48, 50, 24, 5):
+        chunks |= {min(I.MAX_BATCH, n - c0) for c0 in range(0, n, I.MAX_BATCH)}
+    want = set().union(*[expected_inception(B) for B in sorted(chunks)])
+    got = _geom_set(live["inception"])
+    assert got == want, "launched, not derived: %s; derived, not launched: %s" % (sorted(got - want)[:4], sorted(want - got)[:4])
+    want = expected_googlenet(480) | expected_googlenet(10)
+    got = _geom_set(live["googlenet"])
+    assert got == want, "launched, not derived: %s; derived, not launched: %s" % (sorted(got - want)[:4], sorted(want - got)[:4])
+
+
+# ---- comparison ------------------------------------------------------------------------------------------------------
+def _gen(gpu, *key):
+    return torch.Generator(device=gpu).manual_seed(zlib.crc32(repr(key).encode()))
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1)
+
+
+def _call(name, *args):
+    _lib.check(getattr(_lib.load(), name)(*args, _lib.stream()), name)
+    torch.cuda.synchronize()
+
+
+def P(t):
+    return None if t is None else t.data_ptr()
+
+
+def _out_buffer(B, Ho, Wo, ldy, dev, dtype=torch.float32):
+    n = B * Ho * Wo * ldy
+    buf = torch.full((n + GUARD,), SENTINEL, device=dev, dtype=dtype)
+    return buf, buf[:n].view(B, Ho, Wo, ldy)
+
+
+def _sentinels_intact(buf, y, coff, N):
+    bad = []
+    if not bool((y[..., :coff] == SENTINEL).all()) or not bool((y[..., coff + N:] == SENTINEL).all()):
+        bad.append("channels outside [%d, %d) written" % (coff, coff + N))
+    if not bool((buf[y.numel():] == SENTINEL).all()):
+        bad.append("rows after the last pixel written")
+    return bad
+
+
+# ---- s2i_conv2d_forward ----------------------------------------------------------------------------------------------
+# edge cases beyond the census: the 3-channel image without the NHWC4 padding (C % 4 != 0: the scalar gather, K = 27 and
+# K = 147 ragged against the 32-deep chunk), the smallest recorded shapes that reach the non-VEC kernel
+def _d(B, H, C, ldx, N, k, s, p, relu=1, coff=0, extra=0):
+    Ho = (H + 2 * p - k) // s + 1
+    return dict(fn="s2i_conv2d_forward", bias=True, x=True, w=True, y=True,
+                d=dict(B=B, H=H, W=H, C=C, ldx=ldx, N=N, kh=k, kw=k, sh=s, sw=s, ph=p, pw=p, Ho=Ho, Wo=Ho,
+                       ldy=coff + N + extra, coff=coff, relu=relu, tile=0))
+
+
+EDGE_CONV2D = [_d(2, 299, 3, 3, 32, 3, 2, 0), _d(10, 224, 3, 3, 64, 7, 2, 3), _d(2, 299, 3, 4, 32, 3, 2, 0, coff=4, extra=4)]
+
+
+def _image_chunk(d):
+    per = max(d["H"] * d["W"] * d["C"] * d["kh"] * d["kw"] // (d["sh"] * d["sw"]), d["Ho"] * d["Wo"] * d["N"],
+              d["H"] * d["W"] * d["C"])
+    return max(1, min(d["B"], CHUNK_ELEMS // per))
+
+
+def replay_conv2d(rec, pipeline, gpu, what):
+    from speech_to_image_translation_without_text_amd import inception as I
+    d = rec["d"]
+    B, H, W, C, N = d["B"], d["H"], d["W"], d["C"], d["N"]
+    kh, kw, sh, sw, ph, pw, Ho, Wo = (d[k] for k in ("kh", "kw", "sh", "sw", "ph", "pw", "Ho", "Wo"))
+    ldx, ldy, coff = d["ldx"] or C, d["ldy"], d["coff"]
+    gen = _gen(gpu, "conv2d", _canon(rec))
+    x = torch.randn((B, H, W, ldx), generator=gen, device=gpu)
+    w = S._dyadic((N, C, kh, kw), gen, gpu)
+    bias = torch.randn((N,), generator=gen, device=gpu) if rec["bias"] else None
+    packed = I.pack_weight(w)
+    desc = _lib.Conv2dDesc(*[d[f] for f, _ in _lib.Conv2dDesc._fields_])
+    lib = _lib.load()
+    assert packed.numel() == lib.s2i_conv2d_weight_elems(ctypes.byref(desc)), what
+    tile = lib.s2i_conv2d_plan(ctypes.byref(desc))
+    vec = C % 4 == 0 and ldx % 4 == 0
+    key = "%s tile %d %s" % (pipeline, tile, "VEC" if vec else "scalar")
+    _TILES[key] = _TILES.get(key, 0) + 1
+    buf, y = _out_buffer(B, Ho, Wo, ldy, gpu)
+    _call("s2i_conv2d_forward", ctypes.byref(desc), P(x), P(packed), P(bias), P(y))
+    bad = _sentinels_intact(buf, y, coff, N)
+    wd = w.double()
+    bd = None if bias is None else bias.double()
+    act = torch.relu if d["relu"] else (lambda t: t)
+    worst, ok = 0.0, True
+    seen = dict.fromkeys(["last input channel removed", "tap (kh-1, kw-1) removed", "last image's input zeroed"]
+                         + (["replicate padding"] if ph or pw else []) + (["bias removed"] if bias is not None else []), False)
+    step = _image_chunk(d)
+    for b0 in range(0, B, step):
+        b1 = min(B, b0 + step)
+        xs = _nchw(x[b0:b1, :, :, :C]).double()
+        out = _nchw(y[b0:b1, :, :, coff:coff + N]).double()
+        pre = F.conv2d(xs, wd, bd, (sh, sw), (ph, pw))
+        absref = F.conv2d(xs.abs(), wd.abs(), None if bd is None else bd.abs(), (sh, sw), (ph, pw))
+        ratio, good = S._compare(out, act(pre), absref, 0.0, GAMMA_CONV)
+        worst, ok = max(worst, ratio), ok and good
+
+        def fails(name, mref):
+            if S._fails(out, act(mref), absref, 0.0, GAMMA_CONV):
+                seen[name] = True
+
+        fails("last input channel removed", pre - F.conv2d(xs[:, -1:], wd[:, -1:], None, (sh, sw), (ph, pw)))
+        xp = F.pad(xs, (pw, pw, ph, ph))
+        tap = xp[:, :, kh - 1:kh - 1 + sh * (Ho - 1) + 1:sh, kw - 1:kw - 1 + sw * (Wo - 1) + 1:sw]
+        fails("tap (kh-1, kw-1) removed", pre - torch.einsum("bchw,oc->bohw", tap, wd[:, :, kh - 1, kw - 1]))
+        del xp, tap
+        if ph or pw:
+            fails("replicate padding", F.conv2d(F.pad(xs, (pw, pw, ph, ph), mode="replicate"), wd, bd, (sh, sw)))
+        if bd is not None:
+            fails("bias removed", pre - bd.view(1, -1, 1, 1))
+        if b1 == B:
+            m = pre.clone()
+            m[-1] = 0 if bd is None else bd.view(-1, 1, 1)
+            fails("last image's input zeroed", m)
+            del m
+        del xs, out, pre, absref
+    fam = "conv2d/" + pipeline
+    _note(fam, worst, what, GAMMA_CONV)
+    print("%s: tile %d %s, ratio %.3e (gamma %.3e)" % (what, tile, "VEC" if vec else "scalar", worst, GAMMA_CONV))
+    if not ok:
+        bad.append("element error %.3e x absref > gamma %.3e" % (worst, GAMMA_CONV))
+    for name, hit in seen.items():
+        if hit:
+            _rejected("conv2d", name)
+        else:
+            bad.append("the bound cannot see: %s" % name)
+    assert not bad, "%s: %s" % (what, "; ".join(bad))
+
+
+# ---- conv_raw / conv_any of the eval generator --------------------------------------------------------------------------
+def _fwd_replicate(layer, x, w):
+    w = LR._w4(w)
+    if layer == "k1":
+        return LR.fwd(layer, x, w)
+    if layer == "up":
+        x = LR._up(x)
+    return F.conv2d(F.pad(x, (1, 1, 1, 1), mode="replicate"), w, stride=2 if layer == "k4s2" else 1)
+
+
+def _g_power(ctx):
+    """Power checks (b) - (e) of one dispatcher replay ((a) is asserted by test_step_launches_gpu._replay_conv itself)."""
+    rec, op, layer = ctx["rec"], ctx["op"], ctx["layer"]
+    x, cvec, W, Op, table, bias = (ctx[k] for k in ("x", "cvec", "W", "Op", "table", "bias"))
+    _note("conv/generator", ctx["ratio"], "%s %s B=%d" % (op, layer, x.shape[0]), ctx["gamma"])
+    bad = []
+
+    def check(name, *operands, **kw):
+        _, y = S._conv_ref(rec, op, layer, *operands, **kw)
+        if S._fails(ctx["out"], LR.act(y, rec["act"]), ctx["absref"], ctx["rnd"], ctx["gamma"]):
+            _rejected("conv generator", name)
+        else:
+            bad.append("the bound cannot see: %s" % name)
+
+    if op == "fwd" and W.dim() == 4 and W.shape[2] * W.shape[3] > 1:
+        W2 = W.clone()
+        W2[:, :, -1, -1] = 0
+        check("tap (kh-1, kw-1) removed", x, cvec, W2, Op, table, bias)
+        del W2
+    if op == "fwd" and layer != "k1":
+        with pytest.MonkeyPatch.context() as mp:
+            mp.setattr(LR, "fwd", _fwd_replicate)
+            check("replicate padding", x, cvec, W, Op, table, bias)
+    if bias is not None:
+        check("bias removed", x, cvec, W, Op, table, None)
+    x2 = x.clone()
+    x2[-1] = 0
+    z = lambda t: None if t is None else torch.cat((t[:-1], torch.zeros_like(t[-1:])))
+    check("last image's input zeroed", x2, z(cvec), W, Op, z(table), bias)
+    return bad
+
+
+# ---- BatchNorm on running statistics ----------------------------------------------------------------------------------
+def _running_stats(o, C):
+    gamma, beta = o.randn((C,)), o.randn((C,))
+    rm = o.randn((C,), scale=0.5)                                     # both signs
+    rv = torch.exp(o.rand((C,), float(np.log(1e-3)), float(np.log(2.0))))   # 1e-3 .. 2, log-uniform
+    return gamma, beta, rm, rv
+
+
+def _eval_coef(o, C, eps):
+    gamma, beta, rm, rv = _running_stats(o, C)
+    out = o.full((1, 4, C))
+    _call("s2i_bn_eval_coeffs", C, P(gamma), P(beta), P(rm), P(rv), eps, P(out))
+    return (gamma, beta, rm, rv), out
+
+
+def replay_bn_eval_coeffs(rec, o, chk):
+    C, eps = rec["C"], rec["eps"]
+    (gamma, beta, rm, rv), out = _eval_coef(o, C, eps)
+    g, b, m, v = (t.double() for t in (gamma, beta, rm, rv))
+    ref = ER.bn_eval_coeffs(g, b, m, v, eps)
+    cabs = torch.stack((m.abs(), ref[0, 1], ref[0, 2].abs(), b.abs() + (m * ref[0, 2]).abs())).unsqueeze(0)
+    mut = {"eps left out": ER.bn_eval_coeffs(g, b, m, v, 0.0),
+           "variance with a training batch's n / (n - 1) correction, n = 4096": ER.bn_eval_coeffs(g, b, m, v * 4096 / 4095, eps),
+           "sign of the running mean flipped": ER.bn_eval_coeffs(g, b, -m, v, eps)}
+    sh = ref.clone()
+    sh[0, 3] = b + m * ref[0, 2]
+    mut["sign of mean * scale in the shift flipped"] = sh
+    chk.close("bn_finalize", "eval coef", out, ref, cabs, 0.0, mut)
+
+
+def replay_bn_eval_apply(rec, o, chk):
+    """s2i_bn_eval_coeffs -> s2i_bn_act_forward_dt as ops.ConvBnAct.forward chains them in eval: the apply is held to
+    GAMMA["bn_forward"] given the coefficients the first kernel produced, whose own error replay_bn_eval_coeffs bounds."""
+    M, C, act = rec["M"], rec["C"], rec["act"]
+    assert rec["groups"] == 1 and rec["dtype"] == DT_F32
+    _, coef = _eval_coef(o, C, float(ctypes.c_float(1e-5).value))
+    y = o.randn((M, C))
+    cout = C // 2 if act == ACT_GLU else C
+    res = o.randn((M, C)) if rec["residual"] else None
+    out = o.full((M, cout))
+    _call("s2i_bn_act_forward_dt", rec["dtype"], P(y), M, 1, C, P(coef), act, P(res), P(out))
+    yd, cd = y.double(), coef.double()
+    rd = None if res is None else res.double()
+    ref = ER.bn_act_forward(yd, 1, cd, act, rd)
+    zabs = yd.abs() * cd[0, 2].abs() + cd[0, 3].abs()
+    if act == ACT_GLU:
+        h = C // 2
+        absref = zabs[:, :h] * (1 + zabs[:, h:])
+    else:
+        absref = zabs + (0 if rd is None else rd.abs())
+    flipped = cd.clone()
+    flipped[0, 3] = -flipped[0, 3]
+    mut = {"last row missing": E._drop_last_row(ref), "sign of the shift flipped": ER.bn_act_forward(yd, 1, flipped, act, rd)}
+    if act == ACT_GLU:
+        mut["GLU value and gate halves swapped"] = ER.bn_act_forward(E._swap_halves(yd), 1, E._swap_halves(cd), act)
+    chk.close("bn_forward", "eval out", out, ref, absref, 0.0, mut)
+
+
+# ---- pools -------------------------------------------------------------------------------------------------------------
+def _masked(x, right, bottom, value):
+    m = x.clone()
+    if right:
+        m[:, :, :, -1] = value
+    if bottom:
+        m[:, :, -1, :] = value
+    return m
+
+
+def _check_close(chk_bad, fam, what, got, ref, absref, bound_abs, n_terms):
+    err = (got - ref).abs()
+    rel = float((err / absref.clamp_min(1e-300)).max())
+    _note(fam + " |err|", float(err.max()), what, bound_abs)
+    _note(fam + " err / absref", rel, what, (n_terms + 2) * U)
+    if not float(err.max()) <= bound_abs:
+        chk_bad.append("max |err| %.3e > %.1e" % (float(err.max()), bound_abs))
+    if not bool((err <= (n_terms + 2) * U * absref).all()):
+        chk_bad.append("err %.3e x absref > (n + 2) 2^-24 = %.3e" % (rel, (n_terms + 2) * U))
+    return lambda mref: not (float((got - mref).abs().max()) <= bound_abs and bool(((got - mref).abs() <= (n_terms + 2) * U * absref).all()))
+
+
+def replay_pool2d(rec, gpu, what):
+    mode, B, H, W, C, ldx, ldy, coff = (rec[k] for k in ("mode", "B", "H", "W", "C", "ldx", "ldy", "coff"))
+    gen = _gen(gpu, "pool2d", _canon(rec))
+    x = torch.randn((B, H, W, ldx), generator=gen, device=gpu)
+    xn = _nchw(x[..., :C]).double()
+    if mode == POOL_MAX3S2:
+        f = lambda t: F.max_pool2d(t, 3, 2)
+    elif mode == POOL_AVG3S1:
+        f = lambda t: F.avg_pool2d(t, 3, 1, 1, count_include_pad=True)
+    else:
+        f = lambda t: t.mean((2, 3), keepdim=True)
+    ref = f(xn)
+    Ho, Wo = ref.shape[2:]
+    buf, y = _out_buffer(B, Ho, Wo, ldy, gpu)
+    _call("s2i_pool2d", mode, P(x), B, H, W, C, ldx, P(y), ldy, coff)
+    bad = _sentinels_intact(buf, y, coff, C)
+    got = _nchw(y[..., coff:coff + C]).double()
+    if mode == POOL_MAX3S2:
+        if not torch.equal(got, ref):
+            bad.append("max pool not bit-identical (%d elements)" % int((got != ref).sum()))
+        for name, (r, b) in (("right column dropped", (True, False)), ("bottom row dropped", (False, True))):
+            if (W - 3) % 2 == 0 if r else (H - 3) % 2 == 0:        # the last column / row is read by the last window
+                if torch.equal(got, f(_masked(xn, r, b, float("-inf")))):
+                    bad.append("cannot see: " + name)
+                else:
+                    _rejected("max pool", name)
+    else:
+        n = 9 if mode == POOL_AVG3S1 else H * W
+        rejects = _check_close(bad, "avg pool", what, got, ref, f(xn.abs()), 2e-6, n)
+        for name, (r, b) in (("right column dropped", (True, False)), ("bottom row dropped", (False, True))):
+            if rejects(f(_masked(xn, r, b, 0.0))):
+                _rejected("avg pool", name)
+            else:
+                bad.append("cannot see: " + name)
+    assert not bad, "%s: %s" % (what, "; ".join(bad))
+
+
+def replay_maxpool3(rec, gpu, what):
+    B, H, W, C, ldx, stride, pad, ldy, coff = (rec[k] for k in ("B", "H", "W", "C", "ldx", "stride", "pad", "ldy", "coff"))
+    gen = _gen(gpu, "maxpool3", _canon(rec))
+    x = torch.randn((B, H, W, ldx), generator=gen, device=gpu)
+    x[..., ::3] = -1.0 - x[..., ::3].abs()                 # strictly negative channels: a zero padding would win
+    xn = _nchw(x[..., :C]).double()
+    f = lambda t, ceil=True: F.max_pool2d(t, 3, stride, pad, ceil_mode=ceil)
+    ref = f(xn)
+    Ho, Wo = ref.shape[2:]
+    buf, y = _out_buffer(B, Ho, Wo, ldy, gpu)
+    _call("s2i_maxpool3", P(x), B, H, W, C, ldx, stride, pad, P(y), ldy, coff)
+    bad = _sentinels_intact(buf, y, coff, C)
+    got = _nchw(y[..., coff:coff + C]).double()
+    if not torch.equal(got, ref):
+        bad.append("max pool not bit-identical (%d elements)" % int((got != ref).sum()))
+    for name, (r, b) in (("right column dropped", (True, False)), ("bottom row dropped", (False, True))):
+        if torch.equal(got, f(_masked(xn, r, b, float("-inf")))):
+            bad.append("cannot see: " + name)
+        else:
+            _rejected("max pool", name)
+    if pad:
+        if torch.equal(got, F.max_pool2d(F.pad(xn, (1, 1, 1, 1)), 3, stride)):
+            bad.append("cannot see: zero instead of -inf padding")
+        else:
+            _rejected("max pool", "zero instead of -inf padding")
+    floor = f(xn, False)
+    if stride == 2:
+        if floor.shape == ref.shape:
+            bad.append("the ceil and the floor rule agree at H = %d: the record cannot tell them apart" % H)
+        else:
+            _rejected("max pool", "floor-rule output extent")
+    assert not bad, "%s: %s" % (what, "; ".join(bad))
+
+
+def replay_lrn_maxpool3(rec, gpu, what):
+    order, B, H, W, C, ldx, ldy, coff = (rec[k] for k in ("order", "B", "H", "W", "C", "ldx", "ldy", "coff"))
+    assert (rec["size"], rec["k"]) == (5, 1.0) and abs(rec["alpha"] - 1e-4) < 1e-9 and abs(rec["beta"] - 0.75) < 1e-7
+    gen = _gen(gpu, "lrn", _canon(rec))
+    bad = []
+    x = torch.relu(torch.randn((B, H, W, ldx), generator=gen, device=gpu) * 40.0)     # post-ReLU magnitudes
+    Ho, Wo = -(-(H - 3) // 2) + 1, -(-(W - 3) // 2) + 1
+    buf, y = _out_buffer(B, Ho, Wo, ldy, gpu)
+    _call("s2i_lrn_maxpool3", order, P(x), B, H, W, C, ldx, P(y), ldy, coff, rec["size"], rec["alpha"], rec["beta"], rec["k"])
+    bad += _sentinels_intact(buf, y, coff, C)
+    worst = 0.0
+    seen = {"right column dropped": False, "bottom row dropped": False}
+    step = max(1, min(B, CHUNK_ELEMS // (H * W * C)))
+    for b0 in range(0, B, step):
+        xn = _nchw(x[b0:b0 + step, :, :, :C]).double()
+        got = _nchw(y[b0:b0 + step, :, :, coff:coff + C]).double()
+
+        def f(right=False, bottom=False):
+            if order == POOL_THEN_LRN:
+                return GR.lrn(GR.pool_s2(_masked(xn, right, bottom, float("-inf"))))
+            return GR.pool_s2(_masked(GR.lrn(xn), right, bottom, float("-inf")))
+
+        ref = f()
+        assert ref.shape == got.shape, (what, tuple(ref.shape), tuple(got.shape))
+        worst = max(worst, float(((got - ref).abs() / (1.0 + ref.abs())).max()))
+        for name, args in (("right column dropped", (True, False)), ("bottom row dropped", (False, True))):
+            if float(((got - f(*args)).abs() / (1.0 + ref.abs())).max()) >= 2e-6:
+                seen[name] = True
+        del xn, got, ref
+    _note("lrn + pool", worst, what, 2e-6)
+    if not worst < 2e-6:
+        bad.append("|err| / (1 + |ref|) = %.3e >= 2e-6" % worst)
+    for name, hit in seen.items():
+        if hit:
+            _rejected("lrn + pool", name)
+        else:
+            bad.append("cannot see: " + name)
+    floor_h = (H - 3) // 2 + 1
+    if floor_h == Ho:
+        bad.append("the ceil and the floor rule agree at H = %d" % H)
+    else:
+        _rejected("lrn + pool", "floor-rule output extent")
+    assert not bad, "%s: %s" % (what, "; ".join(bad))
+
+
+# ---- input stages, softmax, moments, uint8 conversions ------------------------------------------------------------------
+def replay_inception_prep(rec, gpu, what):
+    B, Hin, Win, S_, Cy = rec["B"], rec["Hin"], rec["Win"], rec["S"], rec["Cy"]
+    strides = (rec["sb"], rec["sc"], rec["sh"], rec["sw"])
+    gen = _gen(gpu, "iprep", _canon(rec))
+    extent = 1 + sum((n - 1) * s for n, s in zip((B, 3, Hin, Win), strides))
+    store = torch.rand((extent,), generator=gen, device=gpu) * 2 - 1
+    img = torch.as_strided(store, (B, 3, Hin, Win), strides)
+    buf, y = _out_buffer(B, S_, S_, Cy, gpu)
+    _call("s2i_inception_prep", P(img), B, Hin, Win, *strides, P(y), S_, Cy)
+    bad = [] if bool((buf[y.numel():] == SENTINEL).all()) else ["rows after the last pixel written"]
+    if Cy == 4 and not bool((y[..., 3] == 0).all()):
+        bad.append("the 4th channel is not zero")
+    worst, wrong = 0.0, False
+    bound = 2.5e-5 * max(Hin, Win) / 64                     # tests/test_inception_gpu.py: grows with the input extent
+    for b0 in range(0, B, 16):
+        got = y[b0:b0 + 16, ..., :3].double()
+        src = img[b0:b0 + 16].double()
+        x64 = (src * 0.5 + 0.5 - torch.tensor([0.485, 0.456, 0.406], dtype=torch.float64, device=gpu)[None, :, None, None]) / \
+            torch.tensor([0.229, 0.224, 0.225], dtype=torch.float64, device=gpu)[None, :, None, None]
+        ref = _nhwc(F.interpolate(x64, size=(S_, S_), mode="bilinear", align_corners=False))
+        worst = max(worst, float((got - ref).abs().max()))
+        wrong = wrong or float((got - _nhwc(F.interpolate(x64, size=(S_, S_), mode="bilinear", align_corners=True))).abs().max()) > bound
+    _note("inception prep |err|", worst, what, bound)
+    if not worst <= bound:
+        bad.append("max |err| %.3e > %.3e" % (worst, bound))
+    if wrong:
+        _rejected("inception prep", "align_corners=True")
+    else:
+        bad.append("cannot see: align_corners=True")
+    assert not bad, "%s: %s" % (what, "; ".join(bad))
+
+
+def replay_googlenet_prep(rec, gpu, what):
+    from speech_to_image_translation_without_text_amd import googlenet as G
+    from test_googlenet_gpu import PREP_BOUND
+    imgs = _ragged49()
+    imgs = imgs[:48] if rec["B"] == 48 else imgs[48:]
+    assert len(imgs) == rec["B"] and sum(im.size for im in imgs) == rec["nbytes"], "the census images changed"
+    net = G.GoogLeNetFeatures.__new__(G.GoogLeNetFeatures)
+    net.device, net.mean_bgr = gpu, (rec["mean_b"], rec["mean_g"], rec["mean_r"])
+    buf, y = _out_buffer(10 * len(imgs), 224, 224, 4, gpu)
+    keep = net.prep(imgs, y)
+    torch.cuda.synchronize()
+    del keep
+    bad = [] if bool((buf[y.numel():] == SENTINEL).all()) else ["rows after the last view written"]
+    if not bool((y[..., 3] == 0).all()):
+        bad.append("the 4th channel is not zero")
+    worst, sees_flip = 0.0, True
+    for i, im in enumerate(imgs):
+        ref = torch.from_numpy(GR.views(im, net.mean_bgr)).permute(0, 2, 3, 1).to(gpu)
+        got = y[10 * i:10 * i + 10, ..., :3].double()
+        worst = max(worst, float((got - ref).abs().max()))
+        sees_flip = sees_flip and float((got[5:] - ref[:5]).abs().max()) > PREP_BOUND      # flipped views taken unflipped
+    _note("googlenet prep |err|", worst, what, PREP_BOUND)
+    if not worst <= PREP_BOUND:
+        bad.append("max |err| %.3e > %.1e" % (worst, PREP_BOUND))
+    if sees_flip:
+        _rejected("googlenet prep", "views 5..9 not flipped")
+    else:
+        bad.append("cannot see: views 5..9 not flipped")
+    assert not bad, "%s: %s" % (what, "; ".join(bad))
+
+
+def replay_softmax(rec, gpu, what):
+    rows, cols, ldx, ldy = rec["rows"], rec["cols"], rec["ldx"], rec["ldy"]
+    gen = _gen(gpu, "softmax", _canon(rec))
+    x = torch.randn((rows, ldx), generator=gen, device=gpu) * 6
+    x[-1, cols - 1] = 15.0                                   # the last logit carries weight in the last row
+    buf, y = _out_buffer(1, 1, rows, ldy, gpu)
+    y = y.view(rows, ldy)
+    _call("s2i_softmax_rows", P(x), rows, cols, ldx, P(y), ldy)
+    bad = _sentinels_intact(buf, y, 0, cols)
+    ref = torch.softmax(x[:, :cols].double(), 1)
+    err = float((y[:, :cols].double() - ref).abs().max())
+    _note("softmax |err|", err, what, 1e-6)
+    if not err <= 1e-6:
+        bad.append("max |err| %.3e > 1e-6" % err)
+    short = torch.softmax(x[:, :cols - 1].double(), 1)
+    if float((y[:, :cols - 1].double() - short).abs().max()) <= 1e-6:
+        bad.append("cannot see: the last logit left out")
+    else:
+        _rejected("softmax", "last logit left out")
+    assert not bad, "%s: %s" % (what, "; ".join(bad))
+
+
+def replay_moments(rec, gpu, what):
+    from test_gan_metrics_gpu import check_against_fp64, moments
+    rows, D, ldx = rec["rows"], rec["D"], rec["ldx"]
+    gen = _gen(gpu, "moments", _canon(rec))
+    x = (torch.randn((rows, ldx), generator=gen, device=gpu).abs_() * 3 - 1)[:, :D]
+    colsum, gram = moments(gpu, x, D)
+    torch.cuda.synchronize()
+    check_against_fp64(x.double().cpu().numpy(), colsum, gram, what)
+    if rows > 1:
+        with pytest.raises(AssertionError):
+            check_against_fp64(x[:-1].double().cpu().numpy(), colsum, gram, what + " (last row missing)")
+        _rejected("moments", "last row missing")
+
+
+def replay_image_to_u8(rec, gpu, what):
+    lds, npix = rec["lds"], rec["npix"]
+    gen = _gen(gpu, "to_u8", _canon(rec))
+    src = torch.randn((npix, lds), generator=gen, device=gpu) * 0.7          # some values beyond [-1, 1]: the clamp
+    dst = torch.full((npix * 3 + GUARD,), 77, dtype=torch.uint8, device=gpu)
+    _call("s2i_image_to_u8", P(src), lds, P(dst), npix)
+    ref = src[:, :3].add(1).div(2).mul(255).clamp(0, 255).byte()
+    assert torch.equal(dst[:npix * 3].view(npix, 3), ref), "%s: %d bytes differ" % (what, int((dst[:npix * 3].view(npix, 3) != ref).sum()))
+    assert bool((dst[npix * 3:] == 77).all()), what + ": written past the last pixel"
+    assert not torch.equal(ref, src[:, :3].add(1).div(2).mul(255).clamp(0, 255).round().byte()), "rounding would pass too"
+    _rejected("image_to_u8", "round instead of truncate")
+
+
+def replay_u8_to_image(rec, gpu, what):
+    B, H, W = rec["B"], rec["H"], rec["W"]
+    gen = _gen(gpu, "from_u8", _canon(rec))
+    u8 = torch.randint(0, 256, (B, H, W, 3), generator=gen, device=gpu, dtype=torch.uint8)
+    buf, y = _out_buffer(B, 3, H, W, gpu)
+    _call("s2i_u8_to_image", P(u8), P(y), B, H, W)
+    ref = ((u8.cpu().permute(0, 3, 1, 2).float() / 255 - 0.5) / 0.5).to(gpu)     # the CPU's true divisions
+    assert torch.equal(y, ref), "%s: %d elements differ" % (what, int((y != ref).sum()))
+    assert bool((buf[y.numel():] == SENTINEL).all()), what + ": written past the last image"
+    assert not torch.equal(y, ref.flip(1))
+    _rejected("u8_to_image", "BGR instead of RGB")
+
+
+# ---- dispatch ----------------------------------------------------------------------------------------------------------
+def _rec_id(p, i, rec):
+    fn = rec["fn"]
+    if fn == "s2i_conv2d_forward":
+        d = rec["d"]
+        return "%s-%03d-conv2d-B%d-%dx%d-C%d-N%d-k%dx%d-s%d-c%d" % (p, i, d["B"], d["H"], d["W"], d["C"], d["N"], d["kh"],
+                                                                   d["kw"], d["sh"], d["coff"])
+    if fn in ("conv_raw", "conv_any"):
+        return "%s-%03d-%s-%s-%s-B%d" % ((p, i, fn) + LR.layer_op(rec) + (rec["x"][0][0],))
+    return "%s-%03d-%s" % (p, i, fn[4:])
+
+
+def _cases():
+    return [pytest.param(p, i, id=_rec_id(p, i, rec)) for p, recs in _load_census().items() for i, rec in enumerate(recs)]
+
+
+def _replay(rec, pipeline, gpu, what):
+    fn = rec["fn"]
+    if fn in ("conv_raw", "conv_any"):
+        gen = torch.Generator(device=gpu).manual_seed(zlib.crc32(_canon(rec).encode()))
+        S._replay_conv(rec, gen, gpu, what, extra=_g_power)
+    elif fn == "s2i_conv2d_forward":
+        replay_conv2d(rec, pipeline, gpu, what)
+    elif fn == "s2i_pool2d":
+        replay_pool2d(rec, gpu, what)
+    elif fn == "s2i_maxpool3":
+        replay_maxpool3(rec, gpu, what)
+    elif fn == "s2i_lrn_maxpool3":
+        replay_lrn_maxpool3(rec, gpu, what)
+    elif fn == "s2i_inception_prep":
+        replay_inception_prep(rec, gpu, what)
+    elif fn == "s2i_googlenet_prep":
+        replay_googlenet_prep(rec, gpu, what)
+    elif fn == "s2i_softmax_rows":
+        replay_softmax(rec, gpu, what)
+    elif fn == "s2i_moments_accumulate":
+        replay_moments(rec, gpu, what)
+    elif fn == "s2i_image_to_u8":
+        replay_image_to_u8(rec, gpu, what)
+    elif fn == "s2i_u8_to_image":
+        replay_u8_to_image(rec, gpu, what)
+    elif fn == "s2i_bn_eval_coeffs":
+        E._run(rec, what, replay_bn_eval_coeffs)
+    else:
+        assert fn in E.REPLAY, "%s: entry point %s has no replay" % (what, fn)
+        E._run(rec, what)                                  # the train-step replay of the same entry point
+        if fn == "s2i_bn_act_forward_dt":
+            E._run(rec, what + " (after eval_coeffs)", replay_bn_eval_apply)
+
+
+@pytest.mark.parametrize("pipeline,index", _cases())
+def test_eval_launch_replay_matches_fp64(gpu, pipeline, index):
+    from speech_to_image_translation_without_text_amd import ops
+    assert ops.TILE_ROWS == 0 and ops.MATH_PLANES == 0 and os.environ.get("S2I_TUNE", "") == "", "default planner"
+    rec = _load_census()[pipeline][index]
+    with torch.no_grad():
+        _replay(rec, pipeline, gpu, "%s[%d] %s" % (pipeline, index, rec["fn"]))
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("rec", EDGE_CONV2D, ids=lambda r: "B%d-%d-C%d-ldx%d-k%d" % (
+    r["d"]["B"], r["d"]["H"], r["d"]["C"], r["d"]["ldx"], r["d"]["kh"]))
+def test_scalar_gather_edge_matches_fp64(gpu, rec):
+    """The 3-channel stems (K = 27 and K = 147): the 4-byte gather that the NHWC4 production input never takes."""
+    with torch.no_grad():
+        replay_conv2d(rec, "edge", gpu, "edge %s" % _canon(rec["d"]))
+    torch.cuda.empty_cache()
+
+
+def test_every_tile_and_both_gathers_are_reached(gpu):
+    """All three block tiles and the VEC gather are planned for recorded launches; the scalar gather only by the edges."""
+    lib = _lib.load()
+    tiles = {}
+    for p in ("inception", "googlenet"):
+        for rec in _load_census().get(p, []):
+            if rec["fn"] == "s2i_conv2d_forward":
+                desc = _lib.Conv2dDesc(*[rec["d"][f] for f, _ in _lib.Conv2dDesc._fields_])
+                tiles.setdefault(lib.s2i_conv2d_plan(ctypes.byref(desc)), []).append(p)
+                assert rec["d"]["C"] % 4 == 0 and (rec["d"]["ldx"] or 4) % 4 == 0, "a production launch on the scalar gather"
+    print("tiles planned for the recorded conv2d launches: %s" % {t: len(v) for t, v in sorted(tiles.items())})
+    assert set(tiles) == {1, 2, 3}, sorted(tiles)
+    assert all(r["d"]["C"] % 4 for r in EDGE_CONV2D)
+
+
+# ---- composition at production batch ------------------------------------------------------------------------------------
+def test_inception_rows_do_not_depend_on_the_batch(gpu):
+    from speech_to_image_translation_without_text_amd import model
+    net = model.INCEPTION_V3(weights=_inception_weights()).net(gpu)
+    img = torch.rand((96, 3, 256, 256), generator=_gen(gpu, "inception96"), device=gpu) * 2 - 1
+    soft, pool3 = torch.empty(96, 1000, device=gpu), torch.empty(96, 2048, device=gpu)
+    with torch.no_grad():
+        net.run([img], soft, pool3)
+        for i in (0, 50, 95):
+            s1, p1 = torch.empty(1, 1000, device=gpu), torch.empty(1, 2048, device=gpu)
+            net.run([img[i:i + 1]], s1, p1)
+            assert torch.equal(p1[0], pool3[i]), "pool3 row %d: max diff %.3e" % (i, float((p1[0] - pool3[i]).abs().max()))
+            assert torch.equal(s1[0], soft[i]), "softmax row %d: max diff %.3e" % (i, float((s1[0] - soft[i]).abs().max()))
+
+
+def test_googlenet_features_do_not_depend_on_the_batch(gpu):
+    from speech_to_image_translation_without_text_amd import googlenet as G
+    net = G.GoogLeNetFeatures(GR.random_weights(0), gpu)
+    imgs = _ragged49()[:48]
+    with torch.no_grad():
+        full = net(imgs)
+        for i in (0, 24, 47):
+            one = net([imgs[i]])
+            assert torch.equal(one[0], full[i]), "image %d: max diff %.3e" % (i, float((one[0] - full[i]).abs().max()))
+
+
+def _g_inputs(case, B, gpu):
+    g = _gen(gpu, "g96", B)
+    return (torch.randn((B, case["z"]), generator=g, device=gpu), torch.randn((B, case["t"]), generator=g, device=gpu),
+            torch.randn((B, case["ef"]), generator=g, device=gpu))
+
+
+def _oracle_fp64(netG, z, c, eps):
+    """The oracle's eval-mode generator run in fp64 on the device, on the parameters netG holds."""
+    from oracle import stackgan_oracle as orc
+    from helpers import oracle_dims
+    p = {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in netG.state_dict().items()}
+    return orc.g_forward(p, z.double(), c.double(), eps.double(), oracle_dims(_full_case()), training=False)[0]
+
+
+def test_eval_generator_images_do_not_depend_on_the_batch(gpu):
+    """A row of a 96-image launch against the single-image run of the same inputs.  These are NOT bit-identical: the
+    generator's convolutions are the train step's igemm_fwd kernels, whose planner (plan_fwd / fwd_splitk in
+    csrc/s2i_igemm.hip) splits K over several blocks when a launch has fewer than 768 blocks and sums the slabs in
+    splitk_reduce_kernel, so the summation order of a single-image launch differs from the 96-image one (measured:
+    7.5e-7 on the last-stage image).  Equality is therefore replaced by the whole-network bound that exists
+    for eval G, rtol 1e-3 / atol 1e-4 against the oracle (here run in fp64), for the row of the 96-image launch and for
+    the single-image run alike; the difference between the two is printed."""
+    netG = _eval_generator(gpu)
+    z, c, eps = _g_inputs(_full_case(), 96, gpu)
+    with torch.no_grad():
+        full = netG(z, c, eps, True)[0][-1]
+        for i in (0, 50, 95):
+            sl = slice(i, i + 1)
+            one = netG(z[sl].contiguous(), c[sl].contiguous(), eps[sl].contiguous(), True)[0][-1]
+            ref = _oracle_fp64(netG, z[sl], c[sl], eps[sl])[-1].permute(0, 2, 3, 1)
+            print("eval G image %d: 96-image launch vs single-image run max diff %.3e" % (i, float((one[0] - full[i]).abs().max())))
+            for name, got in (("single-image run", one[0]), ("row of the 96-image launch", full[i])):
+                err = (got[..., :3].double() - ref[0]).abs()
+                rel = float((err / (1e-4 + 1e-3 * ref[0].abs())).max())
+                _note("eval G batch rows |err|", float(err.max()), "image %d %s" % (i, name), 1e-4)
+                assert rel <= 1.0, "image %d, %s: %.3e of rtol 1e-3 / atol 1e-4" % (i, name, rel)
+
+
+def test_eval_generator_full_width_against_fp64(gpu):
+    """Eval G at full width, 96 images, non-trivial running statistics, against the oracle run in fp64 on the same
+    operands: the measured error is printed next to the rtol 1e-3 / atol 1e-4 of test_eval_mode_generator_matches_oracle,
+    which is what is asserted (no new constant)."""
+    from oracle import stackgan_oracle as orc
+    from helpers import oracle_dims
+    case = _full_case()
+    netG = _eval_generator(gpu)
+    z, c, eps = _g_inputs(case, 96, gpu)
+    p = {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in netG.state_dict().items()}
+    with torch.no_grad():
+        fakes = netG(z, c, eps)[0]
+        worst = 0.0
+        refs = [[] for _ in fakes]
+        for b0 in range(0, 96, 8):
+            of, _, _ = orc.g_forward(p, z[b0:b0 + 8].double(), c[b0:b0 + 8].double(), eps[b0:b0 + 8].double(),
+                                     oracle_dims(case), training=False)
+            for i, t in enumerate(of):
+                refs[i].append(t)
+        for i, got in enumerate(fakes):
+            ref = torch.cat(refs[i])
+            err = (got.double() - ref).abs()
+            rel = float((err / (1e-4 + 1e-3 * ref.abs())).max())
+            worst = max(worst, float(err.max()))
+            print("eval G full width, 96 images, stage %d: max |err| %.3e, %.3e of rtol 1e-3 / atol 1e-4" % (i, float(err.max()), rel))
+            _note("eval G 96 images |err|", float(err.max()), "stage %d" % i, 1e-4)
+            assert rel <= 1.0, "stage %d: %.3e of the bound" % (i, rel)
+
+
+if __name__ == "__main__":
+    # regenerate tests/eval_launches.json (or the path given) from the three pipelines
+    import tempfile
+    _lib.load()
+    _lib.require_device()
+    with tempfile.TemporaryDirectory() as tmp:
+        census, calls = take_census(torch.device("cuda:0"), tmp)
+    path = sys.argv[1] if len(sys.argv) > 1 else CENSUS_FILE
+    with open(path, "w") as fp:
+        fp.write("{\n" + ",\n".join('  "%s": [\n%s\n  ]' % (m, ",\n".join("    " + _canon(r) for r in recs))
+                                    for m, recs in census.items()) + "\n}\n")
+    for p, recs in census.items():
+        print("census %s: %d calls, %d distinct records -> %s" % (p, calls[p], len(recs), path))

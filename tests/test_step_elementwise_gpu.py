@@ -139,15 +139,15 @@ def _is_matrix(name):
 class _Recorder:
     """Stands in for the ctypes library: s2i_* entry points that are not matrix launches are wrapped and recorded."""
 
-    def __init__(self, lib, recs):
-        self._lib, self._recs = lib, recs
+    def __init__(self, lib, recs, args=None):
+        self._lib, self._recs, self._args = lib, recs, ARGS if args is None else args
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
         if not name.startswith("s2i_") or _is_matrix(name):
             return fn
-        assert name in ARGS, "entry point %s has no argument list in ARGS (and no replay)" % name
-        names = ARGS[name].split()
+        assert name in self._args, "entry point %s has no argument list in ARGS (and no replay)" % name
+        names = self._args[name].split()
         types = _lib._SIGNATURES[name][1]
         recs = self._recs
 
@@ -159,6 +159,8 @@ class _Recorder:
                     continue
                 if t is ctypes.c_void_p:
                     rec[n] = not (v is None or (isinstance(v, int) and v == 0))
+                elif hasattr(v, "_obj"):                 # byref(descriptor): field by field
+                    rec[n] = {f: int(getattr(v._obj, f)) for f, _ in v._obj._fields_}
                 elif t is ctypes.c_float:
                     rec[n] = float(ctypes.c_float(v).value)
                 else:

@@ -71,10 +71,10 @@ def _desc(t):
 
 
 # ---- census ----------------------------------------------------------------------------------------------------------
-def _record_step(gpu, case, bf16, mp):
-    """One eager train_step (the pattern of test_bf16_gpu._run_steps) with the dispatchers wrapped -> list of records."""
-    from speech_to_image_translation_without_text_amd import ops, trainer as T
-    recs = []
+def wrap_dispatchers(mp, recs):
+    """Wrap the dispatchers of ops.py so that every call appends its full argument description to recs (also used by
+    tests/test_eval_launches_gpu.py for the eval-mode generator)."""
+    from speech_to_image_translation_without_text_amd import ops
     orig = {k: getattr(ops, k) for k in ("conv_any", "conv_raw", "wgrad_any", "wgrad_raw", "packed_weight", "bf16_weight")}
     fast = [False]
 
@@ -134,6 +134,13 @@ def _record_step(gpu, case, bf16, mp):
     for name, fn in (("packed_weight", packed_weight), ("bf16_weight", bf16_weight), ("conv_any", conv_any),
                      ("conv_raw", conv_raw), ("wgrad_any", wgrad_any), ("wgrad_raw", wgrad_raw)):
         mp.setattr(ops, name, fn)
+
+
+def _record_step(gpu, case, bf16, mp):
+    """One eager train_step (the pattern of test_bf16_gpu._run_steps) with the dispatchers wrapped -> list of records."""
+    from speech_to_image_translation_without_text_amd import ops, trainer as T
+    recs = []
+    wrap_dispatchers(mp, recs)
     mp.setattr(ops, "ACT_BF16", bf16)
     netG, netsD = build_nets(case)
     batch = make_batch(case)
@@ -269,7 +276,9 @@ def _conv_ref(rec, op, layer, x, cvec, W, Op, table, bias, mutate=False):
     return pre, y
 
 
-def _replay_conv(rec, gen, dev, what):
+def _replay_conv(rec, gen, dev, what, extra=None):
+    """extra(ctx), if given, runs before the assertions with the operands, the output and the bound of this replay
+    (tests/test_eval_launches_gpu.py adds its power checks there) and returns a list of failure messages."""
     from speech_to_image_translation_without_text_amd import ops
     op, layer = R.layer_op(rec)
     x = _operand(rec["x"], gen, dev)
@@ -341,8 +350,12 @@ def _replay_conv(rec, gen, dev, what):
         sratio, stats_ok = _compare(got, sref, den, 0.0, GAMMA_STATS)
         _note("stats", sratio, what)
         print("%s: stats ratio %.3e (gamma %.3e)" % (what, sratio, GAMMA_STATS))
+    more = [] if extra is None else extra(dict(rec=rec, op=op, layer=layer, x=xd, cvec=d(cvec), W=W, Op=Op, table=d(table),
+                                               bias=d(bias), out=out, ref=ref, absref=absref, rnd=rnd, gamma=gamma,
+                                               ratio=ratio, cls=cls))
     assert ok, "%s: element error %.3e x absref > gamma %.3e" % (what, ratio, gamma)
     assert stats_ok, "%s: BatchNorm partial sums off" % what
+    assert not more, "%s: %s" % (what, "; ".join(more))
     assert sees_channel, "%s: the bound cannot see one input channel's contribution" % what
 
 
