@@ -9,7 +9,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import elementwise_ref as R
-import test_step_elementwise_gpu as E
+import elementwise_replay as E
+import launch_harness as LH
 from speech_to_image_translation_without_text_amd._lib import ACT_GLU, ACT_LRELU, ACT_NONE
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -247,14 +248,14 @@ def test_census_file_is_well_formed():
     path = os.path.join(HERE, "step_elementwise_launches.json")
     with open(path) as fp:
         census = json.load(fp)
-    assert set(census) == set(E.MODES)
+    assert set(census) == set(LH.STEP_MODES)
     for mode, recs in census.items():
         assert recs, mode
         assert [json.dumps(r, sort_keys=True) for r in recs] == sorted({json.dumps(r, sort_keys=True) for r in recs}), \
             "%s: records not deduplicated and sorted" % mode
         for rec in recs:
             fn = rec["fn"]
-            assert not E._is_matrix(fn), "%s: matrix entry point %s belongs to tests/step_launches.json" % (mode, fn)
+            assert not E.is_matrix(fn), "%s: matrix entry point %s belongs to tests/step_launches.json" % (mode, fn)
             assert fn in R.RESTATES, "%s: %s has no fp64 restatement" % (mode, fn)
             assert fn in E.REPLAY, "%s: %s has no replay" % (mode, fn)
             names = set(E.ARGS[fn].split()) - set(E.NOT_RECORDED)

@@ -9,7 +9,7 @@ kernel and the choice between the fused step kernel and the GEMM + cell fallback
     wrapped and requires the recorded set to equal it: a changed layer or a new launch fails here first.
   * matrix launches (the 40-channel K1, the seven CONV_1D layers, the input projection, the fallback's recurrent GEMM):
     replayed on fresh operands of both signs with dyadic weights, |out - ref| <= 2^-20 * absref as the train step's
-    replay (GAMMA["fp32/conv"] of tests/test_step_launches_gpu.py).  Power: the bound rejects a reference without the
+    replay (GAMMA["fp32/conv"] of tests/conv_replay.py).  Power: the bound rejects a reference without the
     last input channel, without the last tap, and with one border tap missing in the first and the last output column.
   * s2i_maxpool_w3s2: bit-identical to max_pool2d, nothing written past the output; rejects zero padding and a dropped
     right tap in the last column.
@@ -32,14 +32,10 @@ reverted) the four max-pool replays, the twelve D = 2 step replays, two recurren
 module runs in about 6 s.
 """
 import copy
-import ctypes
 import functools
-import json
 import math
 import os
 import sys
-import time
-import zlib
 
 import pytest
 import torch
@@ -53,8 +49,9 @@ for _p in (ROOT, HERE):
         sys.path.insert(0, _p)
 
 import encoder_ref as E  # noqa: E402
-from test_encoder import _small_encoder  # noqa: E402
-from test_step_launches_gpu import GAMMA, _compare, _dyadic, _fails  # noqa: E402
+import launch_harness as LH  # noqa: E402
+from conv_replay import GAMMA  # noqa: E402
+from launch_harness import U  # noqa: E402
 from speech_to_image_translation_without_text_amd import _lib  # noqa: E402
 from speech_to_image_translation_without_text_amd._lib import (ACT_NONE, ACT_RELU, CONV_1D, CONV_K1,  # noqa: E402
                                                                 PACK_PLAIN)
@@ -64,7 +61,6 @@ pytestmark = pytest.mark.gpu
 T_FRAMES = 2048                                     # audio.TARGET_LENGTH
 PRODUCTION = [(bi, B) for bi in (True, False) for B in (1, 24, 37, 240)]
 GAMMA_CONV = GAMMA["fp32/conv"]                     # 2^-20: same kernel family, same fp32 MFMA accumulation
-U = 2.0 ** -24                                      # fp32 unit roundoff
 SENTINEL = -12345.0
 
 # Measured on one MI355X against the fp64 reference; the value in use is 2x the worst value measured.
@@ -83,44 +79,27 @@ ENCODER_TOL = 2 * ENCODER_MEASURED
 # BatchNorm folding in fp32 against fp64: fewer than 64 roundings (a 40-term sum, one sqrt, two divisions, five products)
 FOLD_TOL = 64 * U
 
-_WORST = {}
-_REJECTED = set()
-
-
-def _note(key, value, what=""):
-    if value > _WORST.get(key, (-1.0, ""))[0]:
-        _WORST[key] = (value, what)
+LEDGER = LH.Ledger()
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _report():
-    t0 = time.time()
+    LEDGER.start()
     yield
-    print("\nencoder launch replay, %.0f s" % (time.time() - t0))
-    for key in sorted(_WORST):
-        print("  %-28s %.3e  %s" % (key, _WORST[key][0], _WORST[key][1]))
+    LEDGER.report("encoder launch replay")
     print("  constants in use: gamma conv %.3e; LSTM function error %.3e (measured %.3e); recurrence %.3e (measured "
           "%.3e); encoder %.3e (measured %.3e)" % (GAMMA_CONV, LSTM_FN_TOL, LSTM_FN_MEASURED, RECURRENCE_TOL,
                                                    RECURRENCE_MEASURED, ENCODER_TOL, ENCODER_MEASURED))
-    print("  mutants rejected: %s" % ", ".join(sorted(_REJECTED)))
 
 
 @functools.lru_cache(maxsize=None)
 def _cpu_net(bidirectional):
     """The CLIs' encoder (nhidden = nsent = 1024), seeded, with non-trivial running statistics, on the CPU."""
-    return _small_encoder(bidirectional, 1024)
+    return E.small_encoder(bidirectional, 1024)
 
 
 def _gpu_net(bidirectional, gpu):
     return copy.deepcopy(_cpu_net(bidirectional)).to(gpu)
-
-
-def _canon(rec):
-    return json.dumps(rec, sort_keys=True)
-
-
-def _gen(gpu, *key):
-    return torch.Generator(device=gpu).manual_seed(zlib.crc32(repr(key).encode()))
 
 
 def _roundup4(v):
@@ -166,7 +145,7 @@ def launch_table(net, B, T=T_FRAMES):
         for d in range(D):
             recs.append(dict(fn="s2i_lstm_cell", ldx=D * 4 * Hd, B=B, T=L, Hd=Hd, reverse=d, ldo=D * Hd))
     recs.append(dict(fn="s2i_time_mean", B=B, T=L, C=D * Hd))
-    return [json.loads(s) for s in sorted({_canon(r) for r in recs})]
+    return LH.dedup(recs)
 
 
 # scalar arguments recorded per entry point (include/s2i_hip.h order, the step index and the stream left out)
@@ -178,42 +157,8 @@ _ARGS = {
 }
 
 
-class _LibSpy:
-    def __init__(self, lib, recs):
-        self._lib, self._recs = lib, recs
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if name not in _ARGS:
-            assert not name.startswith("s2i_") or name in ("s2i_last_error", "s2i_check_device"), \
-                "entry point %s launched by the encoder has no place in the table" % name
-            return fn
-        names, types = _ARGS[name].split(), _lib._SIGNATURES[name][1]
-
-        def call(*args):
-            assert len(args) == len(names) + 1, (name, len(args))
-            rec = {"fn": name}
-            for n, t, v in zip(names, types, args):
-                if t is ctypes.c_void_p:
-                    assert v, "%s: NULL %s" % (name, n)
-                elif n != "step":
-                    rec[n] = int(v)
-            self._recs.append(rec)
-            return fn(*args)
-        return call
-
-
-class _ModSpy:
-    """speech_encoder's view of the _lib module, with load() handing out the recording library."""
-
-    def __init__(self, lib):
-        self._spy = lib
-
-    def load(self):
-        return self._spy
-
-    def __getattr__(self, name):
-        return getattr(_lib, name)
+def _passed(name):
+    return name in ("s2i_last_error", "s2i_check_device")
 
 
 def _record_forward(net, x, lens, mp):
@@ -229,7 +174,9 @@ def _record_forward(net, x, lens, mp):
         return orig(kind, x_, cvec, packed, N, wR=wR, ldw=ldw, bias=bias, act=act, conv1d=conv1d)
 
     mp.setattr(ops, "conv_raw", conv_raw)
-    mp.setattr(se, "_lib", _ModSpy(_LibSpy(_lib.load(), recs)))
+    spy = LH.LibRecorder(_lib.load(), recs, _ARGS, _passed, skip=("step",), null_ok=False,
+                        unlisted="entry point %s launched by the encoder has no place in the table")
+    mp.setattr(se, "_lib", LH.ModuleSpy(spy))
     res = net.forward_nhwc(x, lens)
     torch.cuda.synchronize()
     return recs, res
@@ -247,13 +194,13 @@ def _lens(B, gen, gpu):
 @pytest.mark.parametrize("bidirectional,B", PRODUCTION)
 def test_recorded_launches_equal_the_table(gpu, bidirectional, B):
     net = _gpu_net(bidirectional, gpu)
-    gen = _gen(gpu, "table", bidirectional, B)
+    gen = LH.gen_key(gpu, "table", bidirectional, B)
     with pytest.MonkeyPatch.context() as mp, torch.no_grad():
         recs, (words, sent) = _record_forward(net, _mel(B, gen, gpu), _lens(B, gen, gpu), mp)
     D, Hd = net.num_direction, net.nhidden
     assert words.shape == (B, D * Hd, T_FRAMES // 64) and sent.shape == (B, D * Hd)
-    now = {_canon(r) for r in recs}
-    table = {_canon(r) for r in launch_table(_cpu_net(bidirectional), B)}
+    now = {LH.canon(r) for r in recs}
+    table = {LH.canon(r) for r in launch_table(_cpu_net(bidirectional), B)}
     print("bidirectional=%s B=%d: %d library calls, %d distinct launches" % (bidirectional, B, len(recs), len(now)))
     assert now == table, "launched but not in the table: %s; in the table but not launched: %s" % (
         sorted(now - table), sorted(table - now))
@@ -265,7 +212,7 @@ def _matrix_launches():
     for bi, B in PRODUCTION:
         for rec in launch_table(_cpu_net(bi), B):
             if rec["fn"] == "conv_raw":
-                seen.setdefault(_canon(rec), rec)
+                seen.setdefault(LH.canon(rec), rec)
     return [seen[k] for k in sorted(seen)]
 
 
@@ -289,13 +236,13 @@ def test_matrix_launch_replay_matches_fp64(gpu, index):
     assert ops.TILE_ROWS == 0 and ops.MATH_PLANES == 0 and os.environ.get("S2I_TUNE", "") == "", "default planner"
     rec = MATRIX[index]
     what = _matrix_id(rec)
-    gen = _gen(gpu, "matrix", _canon(rec))
+    gen = LH.gen_key(gpu, "matrix", LH.canon(rec))
     B, H, W, Cx = rec["x"]
     N = rec["N"]
     k, st, pd = rec["conv1d"] if rec["conv1d"] is not None else (1, 1, 0)
     with torch.no_grad():
         x = torch.randn((B, H, W, Cx), generator=gen, device=gpu)                   # both signs
-        w = _dyadic((N, Cx, 1, k), gen, gpu)
+        w = LH.dyadic((N, Cx, 1, k), gen, gpu)
         bias = torch.randn((N,), generator=gen, device=gpu) if rec["bias"] else None
         packed = ops.pack_weight(w if rec["conv1d"] is not None else w.view(N, Cx), PACK_PLAIN)
         assert (packed.shape[1], packed.shape[2]) == (rec["wR"], rec["ldw"]), (what, tuple(packed.shape))
@@ -314,16 +261,16 @@ def test_matrix_launch_replay_matches_fp64(gpu, index):
         assert tuple(y.shape) == tuple(pre.shape), (what, tuple(y.shape), tuple(pre.shape))
         act = torch.relu if rec["act"] == ACT_RELU else (lambda t: t)
         out = y.double()
-        ratio, ok = _compare(out, act(pre), absref, 0.0, GAMMA_CONV)
-        _note("matrix ratio (gamma 2^-20)", ratio, what)
+        ratio, ok = LH.compare(out, act(pre), absref, 0.0, GAMMA_CONV)
+        LEDGER.note("matrix ratio (gamma 2^-20)", ratio, what)
         print("%s: ratio %.3e (gamma %.3e)" % (what, ratio, GAMMA_CONV))
         # power (a): the last input channel's contribution removed
         chan = E.conv1d_pre(xd[..., -1:].contiguous(), wd[:, -1:, :].contiguous(), None, k, st, pd)
-        sees_channel = _fails(out, act(pre - chan), absref, 0.0, GAMMA_CONV)
+        sees_channel = LH.fails(out, act(pre - chan), absref, 0.0, GAMMA_CONV)
         sees_tap = sees_border = True
         if rec["conv1d"] is not None:
             # (b) the last tap removed
-            sees_tap = _fails(out, act(pre - _tap_term(xd, wd, k - 1, st, pd, Wo)), absref, 0.0, GAMMA_CONV)
+            sees_tap = LH.fails(out, act(pre - _tap_term(xd, wd, k - 1, st, pd, Wo)), absref, 0.0, GAMMA_CONV)
             # (c) only the first in-bounds tap of output column 0 and the last in-bounds tap of the last column removed
             assert pd > 0
             m = pre.clone()
@@ -333,13 +280,14 @@ def test_matrix_launch_replay_matches_fp64(gpu, index):
             m[:, 0, Wo - 1] -= xd[:, 0, start + t1] @ wd[:, :, t1].t()
             first_only, last_only = pre.clone(), pre.clone()
             first_only[:, 0, 0], last_only[:, 0, Wo - 1] = m[:, 0, 0], m[:, 0, Wo - 1]
-            sees_border = all(_fails(out, act(r), absref, 0.0, GAMMA_CONV) for r in (m, first_only, last_only))
+            sees_border = all(LH.fails(out, act(r), absref, 0.0, GAMMA_CONV) for r in (m, first_only, last_only))
     assert ok, "%s: element error %.3e x absref > gamma %.3e" % (what, ratio, GAMMA_CONV)
     assert sees_channel, "%s: the bound cannot see one input channel's contribution" % what
     assert sees_tap, "%s: the bound cannot see the last tap" % what
     assert sees_border, "%s: the bound cannot see a border tap of the first / last output column" % what
-    _REJECTED.update(["matrix: last input channel removed"] + (["CONV_1D: last tap removed",
-                     "CONV_1D: border tap of column 0 / of the last column removed"] if rec["conv1d"] is not None else []))
+    for m in ["matrix: last input channel removed"] + (["CONV_1D: last tap removed",
+              "CONV_1D: border tap of column 0 / of the last column removed"] if rec["conv1d"] is not None else []):
+        LEDGER.reject(m)
     torch.cuda.empty_cache()
 
 
@@ -371,7 +319,7 @@ def test_fp64_reference_gpu_equals_cpu(gpu):
 @pytest.mark.parametrize("W,C", [(2048, 64), (128, 512)])
 def test_maxpool_replay_is_bit_identical(gpu, W, C, B):
     lib = _lib.load()
-    gen = _gen(gpu, "pool", W, C, B)
+    gen = LH.gen_key(gpu, "pool", W, C, B)
     x = torch.randn((B, 1, W, C), generator=gen, device=gpu)
     x[..., ::3] = -1.0 - x[..., ::3].abs()              # strictly negative channels: a zero padding would win at the borders
     x[:, :, -1, 1] = 9.0                                 # and the last position holds the maximum of the last window
@@ -388,7 +336,8 @@ def test_maxpool_replay_is_bit_identical(gpu, W, C, B):
     short = ref.clone()
     short[:, :, -1] = torch.maximum(x[:, :, W - 3], x[:, :, W - 2])
     assert not torch.equal(y, zero_pad) and not torch.equal(y, short)
-    _REJECTED.update(["maxpool: zero instead of -inf padding", "maxpool: right tap of the last column dropped"])
+    LEDGER.reject("maxpool: zero instead of -inf padding")
+    LEDGER.reject("maxpool: right tap of the last column dropped")
 
 
 # ---- one LSTM step ---------------------------------------------------------------------------------------------------
@@ -450,7 +399,7 @@ def _check_step(got_h, got_c, out, xproj, h_in, c_in, w, lens, step, d, Hd, ez_f
     if lv.any():
         for key in errs:
             excess = max(excess, float((errs[key] - bounds[key])[lv].max()))
-            _note("lstm err / propagated bound", float((errs[key] / bounds[key])[lv].max()), what)
+            LEDGER.note("lstm err / propagated bound", float((errs[key] / bounds[key])[lv].max()), what)
         assert torch.equal(got_o[lv], got_h.double()[lv]), "%s: out row differs from h'" % what
     # finished sequences: the cell state is carried bit-identically
     assert torch.equal(got_c[~lv], c_in[~lv]), "%s: c of a finished sequence changed" % what
@@ -465,13 +414,14 @@ def _check_step(got_h, got_c, out, xproj, h_in, c_in, w, lens, step, d, Hd, ez_f
         xs = torch.cat((xp[:, Hd:2 * Hd], xp[:, :Hd], xp[:, 2 * Hd:]), 1)
         ws = torch.cat((wd[Hd:2 * Hd], wd[:Hd], wd[2 * Hd:]), 0)
         assert rejected(*E.lstm_step(xs, hd_, cd_, ws)), "%s: cannot see gates f and i swapped" % what
-        _REJECTED.update(["lstm: one k term of the recurrent dot removed", "lstm: gates f and i swapped"])
+        LEDGER.reject("lstm: one k term of the recurrent dot removed")
+        LEDGER.reject("lstm: gates f and i swapped")
         L = xproj.shape[1]
         if d == 1 and any(lv_ and n < L for lv_, n in zip(live, lens)):
             mt = torch.tensor(_t_index(lens, step, True, L)[0], device=dev)
             assert rejected(*E.lstm_step(xproj[idx, mt][:, cols].double(), hd_, cd_, wd)), \
                 "%s: cannot see the reverse index taken as L - 1 - step" % what
-            _REJECTED.add("lstm: reverse time index L - 1 - step")
+            LEDGER.reject("lstm: reverse time index L - 1 - step")
     return max(excess, 0.0), ts, live, lv
 
 
@@ -496,7 +446,7 @@ def test_lstm_step_single_step(gpu, Hd, B, D):
         for wide in (False, True):
             for rot in (0, 2):
                 what = "lstm_step Hd=%d B=%d D=%d step=%d wide=%s rot=%d" % (Hd, B, D, step, wide, rot)
-                gen = _gen(gpu, what)
+                gen = LH.gen_key(gpu, what)
                 ldx, ldo = D * 4 * Hd + (8 if wide else 0), D * Hd + (4 if wide else 0)
                 lens = _lens_for(B, L, step, rot, gen, gpu)
                 xproj = torch.randn((B, L, ldx), generator=gen, device=gpu)
@@ -519,7 +469,7 @@ def test_lstm_step_single_step(gpu, Hd, B, D):
                     assert torch.equal(h_out[d][~lv], h_in[d][~lv]), "%s: h of a finished sequence not carried" % what
                     written += [(b, ts[b], d * Hd, (d + 1) * Hd) for b in range(B) if live[b]]
                 _untouched(out, written, what)
-    _note("lstm function error (step)", worst, "Hd=%d B=%d D=%d" % (Hd, B, D))
+    LEDGER.note("lstm function error (step)", worst, "Hd=%d B=%d D=%d" % (Hd, B, D))
     print("lstm_step Hd=%d B=%d D=%d: error beyond the propagated bound %.3e (allowed %.3e)" % (Hd, B, D, worst, LSTM_FN_TOL))
     assert worst <= LSTM_FN_TOL
 
@@ -539,7 +489,7 @@ def test_lstm_cell_single_step(gpu, Hd, B, D):
         for wide in (False, True):
             for rot in (0, 2):
                 what = "lstm_cell Hd=%d B=%d D=%d step=%d wide=%s rot=%d" % (Hd, B, D, step, wide, rot)
-                gen = _gen(gpu, what)
+                gen = LH.gen_key(gpu, what)
                 ldx, ldo = D * 4 * Hd + (8 if wide else 0), D * Hd + (4 if wide else 0)
                 lens = _lens_for(B, L, step, rot, gen, gpu)
                 xproj = torch.randn((B, L, ldx), generator=gen, device=gpu)
@@ -563,7 +513,7 @@ def test_lstm_cell_single_step(gpu, Hd, B, D):
                     assert torch.equal(hs.view(B, Hd)[~lv], h_in.view(B, Hd)[~lv]), "%s: h of a finished sequence touched" % what
                     written += [(b, ts[b], d * Hd, (d + 1) * Hd) for b in range(B) if live[b]]
                 _untouched(out, written, what)
-    _note("lstm function error (cell)", worst, "Hd=%d B=%d D=%d" % (Hd, B, D))
+    LEDGER.note("lstm function error (cell)", worst, "Hd=%d B=%d D=%d" % (Hd, B, D))
     print("lstm_cell Hd=%d B=%d D=%d: error beyond the propagated bound %.3e (allowed %.3e)" % (Hd, B, D, worst, LSTM_FN_TOL))
     assert worst <= LSTM_FN_TOL
 
@@ -612,7 +562,7 @@ def test_whole_recurrence_against_fp64(gpu, B, Hd, D):
     worst = 0.0
     for lens in ([_ragged(B, L)] if B > 1 else [[L], [19], [1]]):
         what = "recurrence B=%d Hd=%d D=%d lens=%d..%d" % (B, Hd, D, lens[0], lens[-1])
-        gen = _gen(gpu, what)
+        gen = LH.gen_key(gpu, what)
         xproj = torch.randn((B, L, D * 4 * Hd), generator=gen, device=gpu)
         raw = [(torch.rand((4 * Hd, Hd), generator=gen, device=gpu) * 2 - 1) / math.sqrt(Hd) for _ in range(D)]
         lens_dev = torch.tensor(lens, dtype=torch.int32, device=gpu)
@@ -633,14 +583,14 @@ def test_whole_recurrence_against_fp64(gpu, B, Hd, D):
             diff = float((got["step"] - got["fallback"]).abs().max())
             print("%s: step kernel vs fallback %.3e" % (what, diff))
             assert diff <= RECURRENCE_TOL, (what, diff)
-    _note("whole recurrence |got - ref|", worst, "B=%d Hd=%d D=%d" % (B, Hd, D))
+    LEDGER.note("whole recurrence |got - ref|", worst, "B=%d Hd=%d D=%d" % (B, Hd, D))
 
 
 # ---- time mean -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B,T,C", [(1, 32, 1024), (240, 32, 1024), (37, 32, 1024)])
 def test_time_mean_replay(gpu, B, T, C):
     lib = _lib.load()
-    gen = _gen(gpu, "mean", B, T, C)
+    gen = LH.gen_key(gpu, "mean", B, T, C)
     x = torch.randn((B, T, C), generator=gen, device=gpu)
     lens = torch.tensor(_ragged(B, T) if B > 1 else [T // 2], device=gpu)
     x[torch.arange(T, device=gpu).view(1, T) >= lens.view(B, 1)] = 0           # trailing zeros, as the LSTM leaves them
@@ -652,7 +602,7 @@ def test_time_mean_replay(gpu, B, T, C):
     bound = (T + 1) * U * xd.abs().mean(1)                                     # sequential fp32 sum, one division
     err = (got - E.time_mean(xd)).abs()
     ratio = float((err / bound.clamp_min(1e-300)).max())
-    _note("time_mean err / bound", ratio, "B=%d" % B)
+    LEDGER.note("time_mean err / bound", ratio, "B=%d" % B)
     print("time_mean B=%d: worst err / bound %.3f" % (B, ratio))
     assert bool((err <= bound).all()) and bool((buf[B * C:] == SENTINEL).all())
     over_len = xd.sum(1) / lens.view(B, 1).double()
@@ -660,7 +610,8 @@ def test_time_mean_replay(gpu, B, T, C):
     assert not bool(((got - over_len).abs() <= bound).all()), "cannot see a mean over the valid positions only"
     if int(lens.max()) == T:
         assert not bool(((got - no_last).abs() <= bound).all()), "cannot see the last position dropped"
-    _REJECTED.update(["time_mean: mean over len instead of T", "time_mean: last position dropped"])
+    LEDGER.reject("time_mean: mean over len instead of T")
+    LEDGER.reject("time_mean: last position dropped")
 
 
 # ---- the whole encoder -----------------------------------------------------------------------------------------------
@@ -706,7 +657,7 @@ def test_prepare_folds_as_the_reference_does(gpu, bidirectional):
 def test_whole_encoder_at_production_batches(gpu, bidirectional, B):
     net = _gpu_net(bidirectional, gpu)
     what = "encoder bidirectional=%s B=%d" % (bidirectional, B)
-    gen = _gen(gpu, what)
+    gen = LH.gen_key(gpu, what)
     with torch.no_grad():
         mel, lens = _mel(B, gen, gpu), _lens(B, gen, gpu)
         words, sent = net.forward_nhwc(mel, lens)
@@ -719,8 +670,8 @@ def test_whole_encoder_at_production_batches(gpu, bidirectional, B):
             rs.append(s_)
         rw, rs = torch.cat(rw), torch.cat(rs)
         ew, es = _hybrid(words, rw), _hybrid(sent, rs)
-        _note("whole encoder words", ew, what)
-        _note("whole encoder sent", es, what)
+        LEDGER.note("whole encoder words", ew, what)
+        LEDGER.note("whole encoder sent", es, what)
         print("%s: words %.3e, sent %.3e (allowed %.3e; max |words| %.3f)" % (what, ew, es, ENCODER_TOL, float(rw.abs().max())))
         assert ew <= ENCODER_TOL and es <= ENCODER_TOL, (what, ew, es)
         for b in range(B):
@@ -733,6 +684,6 @@ def test_whole_encoder_at_production_batches(gpu, bidirectional, B):
                 w1, s1 = net.forward_nhwc(mel[b:b + 1].contiguous(), lens[b:b + 1])
                 dw = float(((w1[0].double() - words[b].double()).abs() / (rw[b].abs() + scale_w)).max())
                 ds = float(((s1[0].double() - sent[b].double()).abs() / (rs[b].abs() + scale_s)).max())
-                _note("batch independence", max(dw, ds), what + " row %d" % b)
+                LEDGER.note("batch independence", max(dw, ds), what + " row %d" % b)
                 assert dw <= ENCODER_TOL and ds <= ENCODER_TOL, (what, b, dw, ds)
     torch.cuda.empty_cache()

@@ -18,7 +18,6 @@ if HERE not in sys.path:
 
 import encoder_ref as E  # noqa: E402
 from helpers import GOLDEN  # noqa: E402
-from test_encoder import _small_encoder, build_encoder, mge  # noqa: E402
 
 ORACLE_TOL = 2e-5
 
@@ -46,8 +45,8 @@ def _against_oracle(net, x, lens, hd, bidirectional, what):
 
 def test_composition_reproduces_the_oracle_on_the_golden_inputs():
     gold = np.load(os.path.join(GOLDEN, "encoder.npz"), allow_pickle=False)
-    x, lens = mge.make_inputs()
-    words, sent = _against_oracle(build_encoder(), x, lens, 512, True, "golden B=3 bidirectional")
+    x, lens = E.mge.make_inputs()
+    words, sent = _against_oracle(E.build_encoder(), x, lens, 512, True, "golden B=3 bidirectional")
     # and with it the reference's own outputs, at the tolerance the oracle is pinned with
     assert torch.allclose(words.float(), torch.from_numpy(gold["words"]), rtol=1e-3, atol=1e-5)
     assert torch.allclose(sent.float(), torch.from_numpy(gold["sent"]), rtol=1e-3, atol=1e-6)
@@ -57,7 +56,7 @@ def test_composition_reproduces_the_oracle_unidirectional():
     """The CLIs' default: one direction, Hd = 1024; ragged lengths including 1 and the full 8 steps."""
     g = torch.Generator().manual_seed(13)
     x = torch.randn(4, 40, 512, generator=g) * 20 - 40
-    _against_oracle(_small_encoder(False, 1024), x, torch.tensor([8, 5, 2, 1]), 1024, False, "B=4 unidirectional")
+    _against_oracle(E.small_encoder(False, 1024), x, torch.tensor([8, 5, 2, 1]), 1024, False, "B=4 unidirectional")
 
 
 def test_single_pieces_against_stock_modules():

@@ -48,11 +48,8 @@ Measured on one MI355X, default planner (the module prints these at the end of a
   modules take 21 + 10 + 3 s on the same machine.
 """
 import ctypes
-import json
 import os
 import sys
-import time
-import zlib
 
 import numpy as np
 import pytest
@@ -65,14 +62,14 @@ for _p in (ROOT, HERE):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import conv_replay as S  # noqa: E402
 import elementwise_ref as ER  # noqa: E402
+import elementwise_replay as E  # noqa: E402
 import googlenet_ref as GR  # noqa: E402
+import launch_harness as LH  # noqa: E402
 import launch_ref as LR  # noqa: E402
-import test_step_elementwise_gpu as E  # noqa: E402
-import test_step_launches_gpu as S  # noqa: E402
-from helpers import CASES, build_nets  # noqa: E402
-from test_encoder_launches_gpu import _ModSpy  # noqa: E402
-from test_inception_cpu import random_state_dict  # noqa: E402
+from helpers import CASES, build_nets, check_against_fp64, moments, random_state_dict  # noqa: E402
+from launch_harness import P, U  # noqa: E402
 from speech_to_image_translation_without_text_amd import _lib  # noqa: E402
 from speech_to_image_translation_without_text_amd._lib import (ACT_GLU, ACT_LRELU, ACT_NONE, DT_F32,  # noqa: E402
                                                                 LRN_THEN_POOL, POOL_AVG3S1, POOL_GLOBAL, POOL_MAX3S2,
@@ -83,7 +80,6 @@ pytestmark = pytest.mark.gpu
 CENSUS_FILE = os.path.join(HERE, "eval_launches.json")
 PIPELINES = ("generator", "inception", "googlenet")
 GAMMA_CONV = S.GAMMA["fp32/conv"]                  # 2^-20: the same mma_chunk fp32 MFMA accumulation, held at K up to 8192
-U = 2.0 ** -24
 SENTINEL = 1234.5
 GUARD = 4096                                       # sentinel floats after the last output pixel
 CHUNK_ELEMS = 1 << 25                              # elements of the larger of a reference chunk's input and output
@@ -104,37 +100,22 @@ ARGS = dict(E.ARGS, **{
 })
 INCEPTION_FNS = ("s2i_conv2d_forward", "s2i_pool2d", "s2i_inception_prep", "s2i_softmax_rows")
 
-_WORST = {}
-_REJECTED = {}
+LEDGER = LH.Ledger()
 _TILES = {}
-
-
-def _note(fam, ratio, what, bound):
-    if fam not in _WORST or ratio > _WORST[fam][0]:
-        _WORST[fam] = (ratio, bound, what)
-
-
-def _rejected(fam, name):
-    _REJECTED["%s: %s" % (fam, name)] = _REJECTED.get("%s: %s" % (fam, name), 0) + 1
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _report():
-    t0 = time.time()
+    LEDGER.start()
     yield
-    print("\neval launch replay, %.0f s: worst measured value per family (bound in use)" % (time.time() - t0))
-    for fam in sorted(_WORST):
-        print("  %-22s %.3e  (%.3e)  %s" % ((fam,) + _WORST[fam]))
+    LEDGER.report("eval launch replay")
     print("conv2d tiles planned (pipeline, tile, VEC): launches")
     for k in sorted(_TILES):
         print("  %-34s %d" % (k, _TILES[k]))
-    print("mutations rejected (family: mutation, cases):")
-    for k in sorted(_REJECTED):
-        print("  %-64s %d" % (k, _REJECTED[k]))
 
 
-def _canon(rec):
-    return json.dumps(rec, sort_keys=True)
+def _rejected(fam, name):
+    LEDGER.reject("%s: %s" % (fam, name))
 
 
 # ---- the production inputs -------------------------------------------------------------------------------------------
@@ -187,11 +168,7 @@ def _ragged49():
 
 # ---- census ----------------------------------------------------------------------------------------------------------
 def _spy(recs, mp, *modules):
-    from speech_to_image_translation_without_text_amd import ops
-    proxy = E._Recorder(_lib.load(), recs, ARGS)
-    mp.setattr(ops, "_lib_ready", lambda: (_lib.require_device(), proxy)[1])
-    for m in modules:
-        mp.setattr(m, "_lib", _ModSpy(proxy))
+    LH.install(mp, LH.LibRecorder(_lib.load(), recs, ARGS, E.is_matrix, skip=E.NOT_RECORDED), *modules)
 
 
 def _record_score(gpu, mp, tmp):
@@ -231,14 +208,7 @@ def take_census(gpu, tmp):
         raw["googlenet"] = _record_googlenet(gpu, mp)
     torch.cuda.empty_cache()
     calls = {k: len(v) for k, v in raw.items()}
-    return {k: [json.loads(s) for s in sorted({_canon(r) for r in raw[k]})] for k in PIPELINES}, calls
-
-
-def _load_census():
-    if not os.path.exists(CENSUS_FILE):
-        return {}
-    with open(CENSUS_FILE) as fp:
-        return json.load(fp)
+    return {k: LH.dedup(raw[k]) for k in PIPELINES}, calls
 
 
 @pytest.fixture(scope="module")
@@ -248,13 +218,9 @@ def live_census(gpu, tmp_path_factory):
 
 def test_census_matches_committed_file(live_census):
     live, calls = live_census
-    committed = _load_census()
     for p in PIPELINES:
         print("census %s: %d calls, %d distinct records" % (p, calls[p], len(live[p])))
-        have = {_canon(r) for r in committed.get(p, [])}
-        now = {_canon(r) for r in live[p]}
-        assert now == have, "%s: records not in tests/eval_launches.json: %s; listed but not launched: %s" % (
-            p, sorted(now - have)[:5], sorted(have - now)[:5])
+    LH.assert_census_equal(live, LH.load_census(CENSUS_FILE), PIPELINES, "eval_launches.json")
 
 
 def test_eval_dispatcher_records_are_eval_mode(live_census):
@@ -317,25 +283,8 @@ def test_recorded_convolutions_equal_the_architecture_tables(live_census):
 
 
 # ---- comparison ------------------------------------------------------------------------------------------------------
-def _gen(gpu, *key):
-    return torch.Generator(device=gpu).manual_seed(zlib.crc32(repr(key).encode()))
-
-
-def _nchw(t):
-    return t.permute(0, 3, 1, 2)
-
-
 def _nhwc(t):
     return t.permute(0, 2, 3, 1)
-
-
-def _call(name, *args):
-    _lib.check(getattr(_lib.load(), name)(*args, _lib.stream()), name)
-    torch.cuda.synchronize()
-
-
-def P(t):
-    return None if t is None else t.data_ptr()
 
 
 def _out_buffer(B, Ho, Wo, ldy, dev, dtype=torch.float32):
@@ -378,9 +327,9 @@ def replay_conv2d(rec, pipeline, gpu, what):
     B, H, W, C, N = d["B"], d["H"], d["W"], d["C"], d["N"]
     kh, kw, sh, sw, ph, pw, Ho, Wo = (d[k] for k in ("kh", "kw", "sh", "sw", "ph", "pw", "Ho", "Wo"))
     ldx, ldy, coff = d["ldx"] or C, d["ldy"], d["coff"]
-    gen = _gen(gpu, "conv2d", _canon(rec))
+    gen = LH.gen_key(gpu, "conv2d", LH.canon(rec))
     x = torch.randn((B, H, W, ldx), generator=gen, device=gpu)
-    w = S._dyadic((N, C, kh, kw), gen, gpu)
+    w = LH.dyadic((N, C, kh, kw), gen, gpu)
     bias = torch.randn((N,), generator=gen, device=gpu) if rec["bias"] else None
     packed = I.pack_weight(w)
     desc = _lib.Conv2dDesc(*[d[f] for f, _ in _lib.Conv2dDesc._fields_])
@@ -391,7 +340,7 @@ def replay_conv2d(rec, pipeline, gpu, what):
     key = "%s tile %d %s" % (pipeline, tile, "VEC" if vec else "scalar")
     _TILES[key] = _TILES.get(key, 0) + 1
     buf, y = _out_buffer(B, Ho, Wo, ldy, gpu)
-    _call("s2i_conv2d_forward", ctypes.byref(desc), P(x), P(packed), P(bias), P(y))
+    LH.call("s2i_conv2d_forward", ctypes.byref(desc), P(x), P(packed), P(bias), P(y))
     bad = _sentinels_intact(buf, y, coff, N)
     wd = w.double()
     bd = None if bias is None else bias.double()
@@ -402,15 +351,15 @@ def replay_conv2d(rec, pipeline, gpu, what):
     step = _image_chunk(d)
     for b0 in range(0, B, step):
         b1 = min(B, b0 + step)
-        xs = _nchw(x[b0:b1, :, :, :C]).double()
-        out = _nchw(y[b0:b1, :, :, coff:coff + N]).double()
+        xs = LH.nchw(x[b0:b1, :, :, :C]).double()
+        out = LH.nchw(y[b0:b1, :, :, coff:coff + N]).double()
         pre = F.conv2d(xs, wd, bd, (sh, sw), (ph, pw))
         absref = F.conv2d(xs.abs(), wd.abs(), None if bd is None else bd.abs(), (sh, sw), (ph, pw))
-        ratio, good = S._compare(out, act(pre), absref, 0.0, GAMMA_CONV)
+        ratio, good = LH.compare(out, act(pre), absref, 0.0, GAMMA_CONV)
         worst, ok = max(worst, ratio), ok and good
 
         def fails(name, mref):
-            if S._fails(out, act(mref), absref, 0.0, GAMMA_CONV):
+            if LH.fails(out, act(mref), absref, 0.0, GAMMA_CONV):
                 seen[name] = True
 
         fails("last input channel removed", pre - F.conv2d(xs[:, -1:], wd[:, -1:], None, (sh, sw), (ph, pw)))
@@ -429,7 +378,7 @@ def replay_conv2d(rec, pipeline, gpu, what):
             del m
         del xs, out, pre, absref
     fam = "conv2d/" + pipeline
-    _note(fam, worst, what, GAMMA_CONV)
+    LEDGER.note(fam, worst, what, GAMMA_CONV)
     print("%s: tile %d %s, ratio %.3e (gamma %.3e)" % (what, tile, "VEC" if vec else "scalar", worst, GAMMA_CONV))
     if not ok:
         bad.append("element error %.3e x absref > gamma %.3e" % (worst, GAMMA_CONV))
@@ -452,15 +401,15 @@ def _fwd_replicate(layer, x, w):
 
 
 def _g_power(ctx):
-    """Power checks (b) - (e) of one dispatcher replay ((a) is asserted by test_step_launches_gpu._replay_conv itself)."""
+    """Power checks (b) - (e) of one dispatcher replay ((a) is asserted by conv_replay.replay_conv itself)."""
     rec, op, layer = ctx["rec"], ctx["op"], ctx["layer"]
     x, cvec, W, Op, table, bias = (ctx[k] for k in ("x", "cvec", "W", "Op", "table", "bias"))
-    _note("conv/generator", ctx["ratio"], "%s %s B=%d" % (op, layer, x.shape[0]), ctx["gamma"])
+    LEDGER.note("conv/generator", ctx["ratio"], "%s %s B=%d" % (op, layer, x.shape[0]), ctx["gamma"])
     bad = []
 
     def check(name, *operands, **kw):
-        _, y = S._conv_ref(rec, op, layer, *operands, **kw)
-        if S._fails(ctx["out"], LR.act(y, rec["act"]), ctx["absref"], ctx["rnd"], ctx["gamma"]):
+        _, y = S.conv_ref(rec, op, layer, *operands, **kw)
+        if LH.fails(ctx["out"], LR.act(y, rec["act"]), ctx["absref"], ctx["rnd"], ctx["gamma"]):
             _rejected("conv generator", name)
         else:
             bad.append("the bound cannot see: %s" % name)
@@ -494,7 +443,7 @@ def _running_stats(o, C):
 def _eval_coef(o, C, eps):
     gamma, beta, rm, rv = _running_stats(o, C)
     out = o.full((1, 4, C))
-    _call("s2i_bn_eval_coeffs", C, P(gamma), P(beta), P(rm), P(rv), eps, P(out))
+    LH.call("s2i_bn_eval_coeffs", C, P(gamma), P(beta), P(rm), P(rv), eps, P(out))
     return (gamma, beta, rm, rv), out
 
 
@@ -523,7 +472,7 @@ def replay_bn_eval_apply(rec, o, chk):
     cout = C // 2 if act == ACT_GLU else C
     res = o.randn((M, C)) if rec["residual"] else None
     out = o.full((M, cout))
-    _call("s2i_bn_act_forward_dt", rec["dtype"], P(y), M, 1, C, P(coef), act, P(res), P(out))
+    LH.call("s2i_bn_act_forward_dt", rec["dtype"], P(y), M, 1, C, P(coef), act, P(res), P(out))
     yd, cd = y.double(), coef.double()
     rd = None if res is None else res.double()
     ref = ER.bn_act_forward(yd, 1, cd, act, rd)
@@ -535,9 +484,9 @@ def replay_bn_eval_apply(rec, o, chk):
         absref = zabs + (0 if rd is None else rd.abs())
     flipped = cd.clone()
     flipped[0, 3] = -flipped[0, 3]
-    mut = {"last row missing": E._drop_last_row(ref), "sign of the shift flipped": ER.bn_act_forward(yd, 1, flipped, act, rd)}
+    mut = {"last row missing": E.drop_last_row(ref), "sign of the shift flipped": ER.bn_act_forward(yd, 1, flipped, act, rd)}
     if act == ACT_GLU:
-        mut["GLU value and gate halves swapped"] = ER.bn_act_forward(E._swap_halves(yd), 1, E._swap_halves(cd), act)
+        mut["GLU value and gate halves swapped"] = ER.bn_act_forward(E.swap_halves(yd), 1, E.swap_halves(cd), act)
     chk.close("bn_forward", "eval out", out, ref, absref, 0.0, mut)
 
 
@@ -554,8 +503,8 @@ def _masked(x, right, bottom, value):
 def _check_close(chk_bad, fam, what, got, ref, absref, bound_abs, n_terms):
     err = (got - ref).abs()
     rel = float((err / absref.clamp_min(1e-300)).max())
-    _note(fam + " |err|", float(err.max()), what, bound_abs)
-    _note(fam + " err / absref", rel, what, (n_terms + 2) * U)
+    LEDGER.note(fam + " |err|", float(err.max()), what, bound_abs)
+    LEDGER.note(fam + " err / absref", rel, what, (n_terms + 2) * U)
     if not float(err.max()) <= bound_abs:
         chk_bad.append("max |err| %.3e > %.1e" % (float(err.max()), bound_abs))
     if not bool((err <= (n_terms + 2) * U * absref).all()):
@@ -565,9 +514,9 @@ def _check_close(chk_bad, fam, what, got, ref, absref, bound_abs, n_terms):
 
 def replay_pool2d(rec, gpu, what):
     mode, B, H, W, C, ldx, ldy, coff = (rec[k] for k in ("mode", "B", "H", "W", "C", "ldx", "ldy", "coff"))
-    gen = _gen(gpu, "pool2d", _canon(rec))
+    gen = LH.gen_key(gpu, "pool2d", LH.canon(rec))
     x = torch.randn((B, H, W, ldx), generator=gen, device=gpu)
-    xn = _nchw(x[..., :C]).double()
+    xn = LH.nchw(x[..., :C]).double()
     if mode == POOL_MAX3S2:
         f = lambda t: F.max_pool2d(t, 3, 2)
     elif mode == POOL_AVG3S1:
@@ -577,9 +526,9 @@ def replay_pool2d(rec, gpu, what):
     ref = f(xn)
     Ho, Wo = ref.shape[2:]
     buf, y = _out_buffer(B, Ho, Wo, ldy, gpu)
-    _call("s2i_pool2d", mode, P(x), B, H, W, C, ldx, P(y), ldy, coff)
+    LH.call("s2i_pool2d", mode, P(x), B, H, W, C, ldx, P(y), ldy, coff)
     bad = _sentinels_intact(buf, y, coff, C)
-    got = _nchw(y[..., coff:coff + C]).double()
+    got = LH.nchw(y[..., coff:coff + C]).double()
     if mode == POOL_MAX3S2:
         if not torch.equal(got, ref):
             bad.append("max pool not bit-identical (%d elements)" % int((got != ref).sum()))
@@ -602,17 +551,17 @@ def replay_pool2d(rec, gpu, what):
 
 def replay_maxpool3(rec, gpu, what):
     B, H, W, C, ldx, stride, pad, ldy, coff = (rec[k] for k in ("B", "H", "W", "C", "ldx", "stride", "pad", "ldy", "coff"))
-    gen = _gen(gpu, "maxpool3", _canon(rec))
+    gen = LH.gen_key(gpu, "maxpool3", LH.canon(rec))
     x = torch.randn((B, H, W, ldx), generator=gen, device=gpu)
     x[..., ::3] = -1.0 - x[..., ::3].abs()                 # strictly negative channels: a zero padding would win
-    xn = _nchw(x[..., :C]).double()
+    xn = LH.nchw(x[..., :C]).double()
     f = lambda t, ceil=True: F.max_pool2d(t, 3, stride, pad, ceil_mode=ceil)
     ref = f(xn)
     Ho, Wo = ref.shape[2:]
     buf, y = _out_buffer(B, Ho, Wo, ldy, gpu)
-    _call("s2i_maxpool3", P(x), B, H, W, C, ldx, stride, pad, P(y), ldy, coff)
+    LH.call("s2i_maxpool3", P(x), B, H, W, C, ldx, stride, pad, P(y), ldy, coff)
     bad = _sentinels_intact(buf, y, coff, C)
-    got = _nchw(y[..., coff:coff + C]).double()
+    got = LH.nchw(y[..., coff:coff + C]).double()
     if not torch.equal(got, ref):
         bad.append("max pool not bit-identical (%d elements)" % int((got != ref).sum()))
     for name, (r, b) in (("right column dropped", (True, False)), ("bottom row dropped", (False, True))):
@@ -637,19 +586,19 @@ def replay_maxpool3(rec, gpu, what):
 def replay_lrn_maxpool3(rec, gpu, what):
     order, B, H, W, C, ldx, ldy, coff = (rec[k] for k in ("order", "B", "H", "W", "C", "ldx", "ldy", "coff"))
     assert (rec["size"], rec["k"]) == (5, 1.0) and abs(rec["alpha"] - 1e-4) < 1e-9 and abs(rec["beta"] - 0.75) < 1e-7
-    gen = _gen(gpu, "lrn", _canon(rec))
+    gen = LH.gen_key(gpu, "lrn", LH.canon(rec))
     bad = []
     x = torch.relu(torch.randn((B, H, W, ldx), generator=gen, device=gpu) * 40.0)     # post-ReLU magnitudes
     Ho, Wo = -(-(H - 3) // 2) + 1, -(-(W - 3) // 2) + 1
     buf, y = _out_buffer(B, Ho, Wo, ldy, gpu)
-    _call("s2i_lrn_maxpool3", order, P(x), B, H, W, C, ldx, P(y), ldy, coff, rec["size"], rec["alpha"], rec["beta"], rec["k"])
+    LH.call("s2i_lrn_maxpool3", order, P(x), B, H, W, C, ldx, P(y), ldy, coff, rec["size"], rec["alpha"], rec["beta"], rec["k"])
     bad += _sentinels_intact(buf, y, coff, C)
     worst = 0.0
     seen = {"right column dropped": False, "bottom row dropped": False}
     step = max(1, min(B, CHUNK_ELEMS // (H * W * C)))
     for b0 in range(0, B, step):
-        xn = _nchw(x[b0:b0 + step, :, :, :C]).double()
-        got = _nchw(y[b0:b0 + step, :, :, coff:coff + C]).double()
+        xn = LH.nchw(x[b0:b0 + step, :, :, :C]).double()
+        got = LH.nchw(y[b0:b0 + step, :, :, coff:coff + C]).double()
 
         def f(right=False, bottom=False):
             if order == POOL_THEN_LRN:
@@ -663,7 +612,7 @@ def replay_lrn_maxpool3(rec, gpu, what):
             if float(((got - f(*args)).abs() / (1.0 + ref.abs())).max()) >= 2e-6:
                 seen[name] = True
         del xn, got, ref
-    _note("lrn + pool", worst, what, 2e-6)
+    LEDGER.note("lrn + pool", worst, what, 2e-6)
     if not worst < 2e-6:
         bad.append("|err| / (1 + |ref|) = %.3e >= 2e-6" % worst)
     for name, hit in seen.items():
@@ -683,12 +632,12 @@ def replay_lrn_maxpool3(rec, gpu, what):
 def replay_inception_prep(rec, gpu, what):
     B, Hin, Win, S_, Cy = rec["B"], rec["Hin"], rec["Win"], rec["S"], rec["Cy"]
     strides = (rec["sb"], rec["sc"], rec["sh"], rec["sw"])
-    gen = _gen(gpu, "iprep", _canon(rec))
+    gen = LH.gen_key(gpu, "iprep", LH.canon(rec))
     extent = 1 + sum((n - 1) * s for n, s in zip((B, 3, Hin, Win), strides))
     store = torch.rand((extent,), generator=gen, device=gpu) * 2 - 1
     img = torch.as_strided(store, (B, 3, Hin, Win), strides)
     buf, y = _out_buffer(B, S_, S_, Cy, gpu)
-    _call("s2i_inception_prep", P(img), B, Hin, Win, *strides, P(y), S_, Cy)
+    LH.call("s2i_inception_prep", P(img), B, Hin, Win, *strides, P(y), S_, Cy)
     bad = [] if bool((buf[y.numel():] == SENTINEL).all()) else ["rows after the last pixel written"]
     if Cy == 4 and not bool((y[..., 3] == 0).all()):
         bad.append("the 4th channel is not zero")
@@ -702,7 +651,7 @@ def replay_inception_prep(rec, gpu, what):
         ref = _nhwc(F.interpolate(x64, size=(S_, S_), mode="bilinear", align_corners=False))
         worst = max(worst, float((got - ref).abs().max()))
         wrong = wrong or float((got - _nhwc(F.interpolate(x64, size=(S_, S_), mode="bilinear", align_corners=True))).abs().max()) > bound
-    _note("inception prep |err|", worst, what, bound)
+    LEDGER.note("inception prep |err|", worst, what, bound)
     if not worst <= bound:
         bad.append("max |err| %.3e > %.3e" % (worst, bound))
     if wrong:
@@ -714,7 +663,6 @@ def replay_inception_prep(rec, gpu, what):
 
 def replay_googlenet_prep(rec, gpu, what):
     from speech_to_image_translation_without_text_amd import googlenet as G
-    from test_googlenet_gpu import PREP_BOUND
     imgs = _ragged49()
     imgs = imgs[:48] if rec["B"] == 48 else imgs[48:]
     assert len(imgs) == rec["B"] and sum(im.size for im in imgs) == rec["nbytes"], "the census images changed"
@@ -732,10 +680,10 @@ def replay_googlenet_prep(rec, gpu, what):
         ref = torch.from_numpy(GR.views(im, net.mean_bgr)).permute(0, 2, 3, 1).to(gpu)
         got = y[10 * i:10 * i + 10, ..., :3].double()
         worst = max(worst, float((got - ref).abs().max()))
-        sees_flip = sees_flip and float((got[5:] - ref[:5]).abs().max()) > PREP_BOUND      # flipped views taken unflipped
-    _note("googlenet prep |err|", worst, what, PREP_BOUND)
-    if not worst <= PREP_BOUND:
-        bad.append("max |err| %.3e > %.1e" % (worst, PREP_BOUND))
+        sees_flip = sees_flip and float((got[5:] - ref[:5]).abs().max()) > GR.PREP_BOUND      # flipped views taken unflipped
+    LEDGER.note("googlenet prep |err|", worst, what, GR.PREP_BOUND)
+    if not worst <= GR.PREP_BOUND:
+        bad.append("max |err| %.3e > %.1e" % (worst, GR.PREP_BOUND))
     if sees_flip:
         _rejected("googlenet prep", "views 5..9 not flipped")
     else:
@@ -745,16 +693,16 @@ def replay_googlenet_prep(rec, gpu, what):
 
 def replay_softmax(rec, gpu, what):
     rows, cols, ldx, ldy = rec["rows"], rec["cols"], rec["ldx"], rec["ldy"]
-    gen = _gen(gpu, "softmax", _canon(rec))
+    gen = LH.gen_key(gpu, "softmax", LH.canon(rec))
     x = torch.randn((rows, ldx), generator=gen, device=gpu) * 6
     x[-1, cols - 1] = 15.0                                   # the last logit carries weight in the last row
     buf, y = _out_buffer(1, 1, rows, ldy, gpu)
     y = y.view(rows, ldy)
-    _call("s2i_softmax_rows", P(x), rows, cols, ldx, P(y), ldy)
+    LH.call("s2i_softmax_rows", P(x), rows, cols, ldx, P(y), ldy)
     bad = _sentinels_intact(buf, y, 0, cols)
     ref = torch.softmax(x[:, :cols].double(), 1)
     err = float((y[:, :cols].double() - ref).abs().max())
-    _note("softmax |err|", err, what, 1e-6)
+    LEDGER.note("softmax |err|", err, what, 1e-6)
     if not err <= 1e-6:
         bad.append("max |err| %.3e > 1e-6" % err)
     short = torch.softmax(x[:, :cols - 1].double(), 1)
@@ -766,9 +714,8 @@ def replay_softmax(rec, gpu, what):
 
 
 def replay_moments(rec, gpu, what):
-    from test_gan_metrics_gpu import check_against_fp64, moments
     rows, D, ldx = rec["rows"], rec["D"], rec["ldx"]
-    gen = _gen(gpu, "moments", _canon(rec))
+    gen = LH.gen_key(gpu, "moments", LH.canon(rec))
     x = (torch.randn((rows, ldx), generator=gen, device=gpu).abs_() * 3 - 1)[:, :D]
     colsum, gram = moments(gpu, x, D)
     torch.cuda.synchronize()
@@ -781,10 +728,10 @@ def replay_moments(rec, gpu, what):
 
 def replay_image_to_u8(rec, gpu, what):
     lds, npix = rec["lds"], rec["npix"]
-    gen = _gen(gpu, "to_u8", _canon(rec))
+    gen = LH.gen_key(gpu, "to_u8", LH.canon(rec))
     src = torch.randn((npix, lds), generator=gen, device=gpu) * 0.7          # some values beyond [-1, 1]: the clamp
     dst = torch.full((npix * 3 + GUARD,), 77, dtype=torch.uint8, device=gpu)
-    _call("s2i_image_to_u8", P(src), lds, P(dst), npix)
+    LH.call("s2i_image_to_u8", P(src), lds, P(dst), npix)
     ref = src[:, :3].add(1).div(2).mul(255).clamp(0, 255).byte()
     assert torch.equal(dst[:npix * 3].view(npix, 3), ref), "%s: %d bytes differ" % (what, int((dst[:npix * 3].view(npix, 3) != ref).sum()))
     assert bool((dst[npix * 3:] == 77).all()), what + ": written past the last pixel"
@@ -794,10 +741,10 @@ def replay_image_to_u8(rec, gpu, what):
 
 def replay_u8_to_image(rec, gpu, what):
     B, H, W = rec["B"], rec["H"], rec["W"]
-    gen = _gen(gpu, "from_u8", _canon(rec))
+    gen = LH.gen_key(gpu, "from_u8", LH.canon(rec))
     u8 = torch.randint(0, 256, (B, H, W, 3), generator=gen, device=gpu, dtype=torch.uint8)
     buf, y = _out_buffer(B, 3, H, W, gpu)
-    _call("s2i_u8_to_image", P(u8), P(y), B, H, W)
+    LH.call("s2i_u8_to_image", P(u8), P(y), B, H, W)
     ref = ((u8.cpu().permute(0, 3, 1, 2).float() / 255 - 0.5) / 0.5).to(gpu)     # the CPU's true divisions
     assert torch.equal(y, ref), "%s: %d elements differ" % (what, int((y != ref).sum()))
     assert bool((buf[y.numel():] == SENTINEL).all()), what + ": written past the last image"
@@ -818,14 +765,13 @@ def _rec_id(p, i, rec):
 
 
 def _cases():
-    return [pytest.param(p, i, id=_rec_id(p, i, rec)) for p, recs in _load_census().items() for i, rec in enumerate(recs)]
+    return [pytest.param(p, i, id=_rec_id(p, i, rec)) for p, recs in LH.load_census(CENSUS_FILE).items() for i, rec in enumerate(recs)]
 
 
 def _replay(rec, pipeline, gpu, what):
     fn = rec["fn"]
     if fn in ("conv_raw", "conv_any"):
-        gen = torch.Generator(device=gpu).manual_seed(zlib.crc32(_canon(rec).encode()))
-        S._replay_conv(rec, gen, gpu, what, extra=_g_power)
+        S.replay_conv(rec, LH.gen_rec(gpu, rec), gpu, what, LEDGER, extra=_g_power)
     elif fn == "s2i_conv2d_forward":
         replay_conv2d(rec, pipeline, gpu, what)
     elif fn == "s2i_pool2d":
@@ -847,19 +793,19 @@ def _replay(rec, pipeline, gpu, what):
     elif fn == "s2i_u8_to_image":
         replay_u8_to_image(rec, gpu, what)
     elif fn == "s2i_bn_eval_coeffs":
-        E._run(rec, what, replay_bn_eval_coeffs)
+        E.run(rec, what, LEDGER, replay_bn_eval_coeffs)
     else:
         assert fn in E.REPLAY, "%s: entry point %s has no replay" % (what, fn)
-        E._run(rec, what)                                  # the train-step replay of the same entry point
+        E.run(rec, what, LEDGER)                                # the train-step replay of the same entry point
         if fn == "s2i_bn_act_forward_dt":
-            E._run(rec, what + " (after eval_coeffs)", replay_bn_eval_apply)
+            E.run(rec, what + " (after eval_coeffs)", LEDGER, replay_bn_eval_apply)
 
 
 @pytest.mark.parametrize("pipeline,index", _cases())
 def test_eval_launch_replay_matches_fp64(gpu, pipeline, index):
     from speech_to_image_translation_without_text_amd import ops
     assert ops.TILE_ROWS == 0 and ops.MATH_PLANES == 0 and os.environ.get("S2I_TUNE", "") == "", "default planner"
-    rec = _load_census()[pipeline][index]
+    rec = LH.load_census(CENSUS_FILE)[pipeline][index]
     with torch.no_grad():
         _replay(rec, pipeline, gpu, "%s[%d] %s" % (pipeline, index, rec["fn"]))
     torch.cuda.empty_cache()
@@ -870,7 +816,7 @@ def test_eval_launch_replay_matches_fp64(gpu, pipeline, index):
 def test_scalar_gather_edge_matches_fp64(gpu, rec):
     """The 3-channel stems (K = 27 and K = 147): the 4-byte gather that the NHWC4 production input never takes."""
     with torch.no_grad():
-        replay_conv2d(rec, "edge", gpu, "edge %s" % _canon(rec["d"]))
+        replay_conv2d(rec, "edge", gpu, "edge %s" % LH.canon(rec["d"]))
     torch.cuda.empty_cache()
 
 
@@ -879,7 +825,7 @@ def test_every_tile_and_both_gathers_are_reached(gpu):
     lib = _lib.load()
     tiles = {}
     for p in ("inception", "googlenet"):
-        for rec in _load_census().get(p, []):
+        for rec in LH.load_census(CENSUS_FILE).get(p, []):
             if rec["fn"] == "s2i_conv2d_forward":
                 desc = _lib.Conv2dDesc(*[rec["d"][f] for f, _ in _lib.Conv2dDesc._fields_])
                 tiles.setdefault(lib.s2i_conv2d_plan(ctypes.byref(desc)), []).append(p)
@@ -893,7 +839,7 @@ def test_every_tile_and_both_gathers_are_reached(gpu):
 def test_inception_rows_do_not_depend_on_the_batch(gpu):
     from speech_to_image_translation_without_text_amd import model
     net = model.INCEPTION_V3(weights=_inception_weights()).net(gpu)
-    img = torch.rand((96, 3, 256, 256), generator=_gen(gpu, "inception96"), device=gpu) * 2 - 1
+    img = torch.rand((96, 3, 256, 256), generator=LH.gen_key(gpu, "inception96"), device=gpu) * 2 - 1
     soft, pool3 = torch.empty(96, 1000, device=gpu), torch.empty(96, 2048, device=gpu)
     with torch.no_grad():
         net.run([img], soft, pool3)
@@ -916,7 +862,7 @@ def test_googlenet_features_do_not_depend_on_the_batch(gpu):
 
 
 def _g_inputs(case, B, gpu):
-    g = _gen(gpu, "g96", B)
+    g = LH.gen_key(gpu, "g96", B)
     return (torch.randn((B, case["z"]), generator=g, device=gpu), torch.randn((B, case["t"]), generator=g, device=gpu),
             torch.randn((B, case["ef"]), generator=g, device=gpu))
 
@@ -949,7 +895,7 @@ def test_eval_generator_images_do_not_depend_on_the_batch(gpu):
             for name, got in (("single-image run", one[0]), ("row of the 96-image launch", full[i])):
                 err = (got[..., :3].double() - ref[0]).abs()
                 rel = float((err / (1e-4 + 1e-3 * ref[0].abs())).max())
-                _note("eval G batch rows |err|", float(err.max()), "image %d %s" % (i, name), 1e-4)
+                LEDGER.note("eval G batch rows |err|", float(err.max()), "image %d %s" % (i, name), 1e-4)
                 assert rel <= 1.0, "image %d, %s: %.3e of rtol 1e-3 / atol 1e-4" % (i, name, rel)
 
 
@@ -978,7 +924,7 @@ def test_eval_generator_full_width_against_fp64(gpu):
             rel = float((err / (1e-4 + 1e-3 * ref.abs())).max())
             worst = max(worst, float(err.max()))
             print("eval G full width, 96 images, stage %d: max |err| %.3e, %.3e of rtol 1e-3 / atol 1e-4" % (i, float(err.max()), rel))
-            _note("eval G 96 images |err|", float(err.max()), "stage %d" % i, 1e-4)
+            LEDGER.note("eval G 96 images |err|", float(err.max()), "stage %d" % i, 1e-4)
             assert rel <= 1.0, "stage %d: %.3e of the bound" % (i, rel)
 
 
@@ -990,8 +936,6 @@ if __name__ == "__main__":
     with tempfile.TemporaryDirectory() as tmp:
         census, calls = take_census(torch.device("cuda:0"), tmp)
     path = sys.argv[1] if len(sys.argv) > 1 else CENSUS_FILE
-    with open(path, "w") as fp:
-        fp.write("{\n" + ",\n".join('  "%s": [\n%s\n  ]' % (m, ",\n".join("    " + _canon(r) for r in recs))
-                                    for m, recs in census.items()) + "\n}\n")
+    LH.write_census(path, census)
     for p, recs in census.items():
         print("census %s: %d calls, %d distinct records -> %s" % (p, calls[p], len(recs), path))

@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import CASES, GOLDEN, build_nets, configure, make_cub_tree, oracle_dims
-from test_inception_cpu import random_state_dict
+from helpers import CASES, GOLDEN, build_nets, configure, make_cub_tree, oracle_dims, random_state_dict
+from helpers import EPS64, check_against_fp64, mirrored, moments
 
 pytestmark = pytest.mark.gpu
 
@@ -19,37 +19,6 @@ _spec = importlib.util.spec_from_file_location("make_golden_inception_metrics",
                                                os.path.join(GOLDEN, "make_golden_inception_metrics.py"))
 mgm = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(mgm)
-
-EPS64 = 2.0 ** -53
-
-
-def moments(gpu, x, D, colsum=None, gram=None):
-    """One s2i_moments_accumulate launch on the fp32 device rows x (row stride x.stride(0)); returns (colsum, gram)."""
-    from speech_to_image_translation_without_text_amd import _lib
-    if colsum is None:
-        colsum = torch.zeros(D, dtype=torch.float64, device=gpu)
-        gram = torch.zeros(D, D, dtype=torch.float64, device=gpu)
-    _lib.check(_lib.load().s2i_moments_accumulate(_lib.ptr(x), x.shape[0], D, x.stride(0), _lib.ptr(colsum),
-                                                  _lib.ptr(gram), _lib.stream()), "s2i_moments_accumulate")
-    return colsum, gram
-
-
-def mirrored(gram):
-    g = np.triu(gram.cpu().numpy())
-    return g + np.triu(g, 1).T
-
-
-def check_against_fp64(x64, colsum, gram, what):
-    """|err| <= rows * 2^-53 * sum |x_i x_j| (the standard bound of an n-term fp64 sum of exact products; measured at
-    most 4.1e-15 against 1.1e-13 at 1000 rows, and the column sums exact)."""
-    n = x64.shape[0]
-    g_ref, s_ref = x64.T @ x64, x64.sum(0)
-    a = np.abs(x64)
-    g_err = np.abs(mirrored(gram) - g_ref) / (a.T @ a + 1e-300)
-    s_err = np.abs(colsum.cpu().numpy() - s_ref) / (a.sum(0) + 1e-300)
-    print("%s: gram max rel err %.3g, colsum %.3g (bound %.3g)" % (what, g_err.max(), s_err.max(), n * EPS64))
-    assert g_err.max() <= n * EPS64 and s_err.max() <= n * EPS64, what
-
 
 @pytest.mark.parametrize("D", [64, 100, 2048])
 @pytest.mark.parametrize("rows", [1, 3, 17, 48, 480, 1000])
@@ -171,7 +140,7 @@ def host_pipeline(gpu, netG, loader, incep, case, seed):
                 n_real=pr.shape[0])
 
 
-def compare(got, want, rtol, what):
+def assert_scores_close(got, want, rtol, what):
     for k in ("is_mean", "is_std", "nlpp_mean", "nlpp_std", "fid"):
         scale = abs(want[k.replace("_std", "_mean")])      # a spread is compared on the scale of its mean
         rel = abs(got[k] - want[k]) / max(scale, 1e-12)
@@ -201,8 +170,8 @@ def test_score_generator_matches_the_host_pipeline(gpu, tmp_path):
                                save_images=str(tmp_path / name) if name == "stacked" else None)
         assert n == 5
         res[name] = scorer.result(10)
-        compare(res[name], want, 1e-8, name)                      # 2x the measured 5.3e-9 (FID)
-    compare(res["per-sentence"], res["stacked"], 1e-10, "per-sentence vs stacked")   # measured: identical
+        assert_scores_close(res[name], want, 1e-8, name)                      # 2x the measured 5.3e-9 (FID)
+    assert_scores_close(res["per-sentence"], res["stacked"], 1e-10, "per-sentence vs stacked")   # measured: identical
     png = tmp_path / "stacked" / "single_samples" / "valid" / "bird0" / "img4_256_sentence2_0.png"
     assert png.exists(), png
     # max_items and a subset of sentences

@@ -11,7 +11,6 @@ import torch
 import torch.nn.functional as F
 
 import googlenet_ref as R
-from test_googlenet_cpu import encode_caffemodel, make_data_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -30,9 +29,6 @@ def ragged_images():
     return [smooth, small, np.asarray(gray), np.asarray(rgba)]
 
 
-# worst |kernel - float64| in 0..255 units measured on an MI355X: 3.56e-5 (exact integer taps, one rounded fraction, two
-# fp32 lerps); the bound is 2x that
-PREP_BOUND = 7.5e-5
 
 
 def test_prep_kernel_against_float64(gpu):
@@ -52,7 +48,7 @@ def test_prep_kernel_against_float64(gpu):
         err = float((got[10 * i:10 * i + 10, ..., :3] - ref).abs().max())
         worst = max(worst, err)
     print("prep worst abs error %.3g" % worst)
-    assert worst <= PREP_BOUND
+    assert worst <= R.PREP_BOUND
 
 
 def launch_pool(gpu, kind, x, C, coff=0, extra=0, stride=2, pad=0):
@@ -182,7 +178,7 @@ def test_cli_end_to_end(gpu, tmp_path, net_and_weights):
     from speech_to_image_translation_without_text_amd import (datasets, extract_image_feature as X, googlenet as G,
                                                               retrieval)
     net, w = net_and_weights
-    paths = make_data_dir(tmp_path, "birds", n=(5, 4))
+    paths = R.make_data_dir(tmp_path, "birds", n=(5, 4))
     rng = np.random.default_rng(3)
     for split, ps in paths.items():
         for i, p in enumerate(ps):
@@ -190,7 +186,7 @@ def test_cli_end_to_end(gpu, tmp_path, net_and_weights):
             a = rng.integers(0, 256, (180 + 17 * i, 240 - 9 * i, 3)).astype(np.uint8)
             Image.fromarray(a).save(p, quality=90) if p.endswith(".jpg") else Image.fromarray(a).save(p)
     model = tmp_path / "g.caffemodel"
-    model.write_bytes(encode_caffemodel({n: list(v) for n, v in w.items()}))
+    model.write_bytes(R.encode_caffemodel({n: list(v) for n, v in w.items()}))
     X.main(["--weights", str(model), "--dataset", "birds", "--data_dir", str(tmp_path), "--batch_size", "2"])
     for split, ps in paths.items():
         out = tmp_path / split / "image_features_googlenet_caffe.pickle"

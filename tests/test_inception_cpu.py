@@ -10,30 +10,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import GOLDEN
+from helpers import GOLDEN, random_state_dict
 
 _spec = importlib.util.spec_from_file_location("make_golden_inception_metrics",
                                                os.path.join(GOLDEN, "make_golden_inception_metrics.py"))
 mgm = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(mgm)
-
-
-def random_state_dict(seed=0, aux_logits=True, num_batches_tracked=True):
-    from speech_to_image_translation_without_text_amd import inception as I
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for k, shp in I.state_dict_shapes(aux_logits, num_batches_tracked).items():
-        if k.endswith("num_batches_tracked"):
-            sd[k] = torch.tensor(7)
-        elif k.endswith("running_var"):
-            sd[k] = torch.rand(shp, generator=g) + 0.5
-        elif k.endswith("conv.weight") or k.endswith("fc.weight"):
-            sd[k] = torch.randn(shp, generator=g) * (2.0 / (shp[1] * (shp[2] * shp[3] if len(shp) == 4 else 1))) ** 0.5
-        elif k.endswith("bn.weight"):
-            sd[k] = torch.rand(shp, generator=g) + 0.5
-        else:
-            sd[k] = torch.randn(shp, generator=g) * 0.1
-    return sd
 
 
 def test_metrics_match_the_reference_fixture():

@@ -9,8 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import CASES, build_nets, make_batch
-from test_inception_cpu import random_state_dict
+from helpers import CASES, build_nets, make_batch, random_state_dict
 
 pytestmark = pytest.mark.gpu
 
