@@ -331,6 +331,20 @@ int s2i_image_to_u8(const float* src, int lds, unsigned char* dst, long long npi
    `ToTensor()` (x / 255) followed by `Normalize((.5,.5,.5), (.5,.5,.5))` ((t - 0.5) / 0.5), datasets.py:440-442,
    applied on the device to the collated uint8 batch (same fp32 operations in the same order: bit-identical) */
 int s2i_u8_to_image(const unsigned char* src, float* dst, int B, int H, int W, void* stream);
+/* The per-step half of the training image transform on images that stay in device memory (StackGAN_v2/datasets.py:40-66
+   behind the transform of main.py:127-131): for each of the n plan rows (pool index, top, left, flip) the S x S
+   RandomCrop window of resident image `pool index`, mirrored when flip != 0 (RandomHorizontalFlip), normalised as
+   s2i_u8_to_image does, into out0 [n][3][S][S]; with L >= 2 also PIL's 8-bit bilinear resize of that window (not of the
+   previous level, datasets.py:57-64) to S/2 into out1 [n][3][S/2][S/2], and with L = 3 to S/4 into out2.
+   pool holds the uint8 HWC images back to back; image i starts at byte offsets[i] and is sizes[2i] rows of sizes[2i+1]
+   pixels.  tab1 [S/2][5] and tab2 [S/4][9] are PIL's resample coefficients of S -> S/2 and S -> S/4 computed on the
+   host: per output position the first input index, then 4 (8) taps in 22-bit fixed point, zero where PIL has fewer; the
+   same table serves both passes.  A tap sum is (1 << 21) + sum of pixel * tap, shifted right by 22 and clamped to
+   0..255; the horizontal pass writes a uint8 intermediate, as PIL does, so every plane is bit-identical to the host path.
+   S is a multiple of 4 up to 256; out0 is 16-byte aligned.  A plan row that does not fit its image is skipped. */
+int s2i_image_batch(const unsigned char* pool, long long pool_bytes, const long long* offsets, const int* sizes,
+                    int npool, const int* plan, int n, int S, int L, const int* tab1, const int* tab2, float* out0,
+                    float* out1, float* out2, void* stream);
 /* sum over the H*W rows of each image of the first C columns of a [B*HW][ld] tensor -> [B][C] */
 int s2i_spatial_sum(const float* src, int ld, int B, int HW, int C, float* dst, void* ws,
                     size_t ws_bytes, void* stream);

@@ -168,8 +168,11 @@ def refresh_packed(params):
             max_taps = max(max_taps, KH * KW)
         raw = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(entries[0][0].device)
         tab = (key, raw, len(entries), block0, max_taps)
-        if len(_pack_tables) > 64 and not _ws.pinned:   # a captured graph reads its table through a raw pointer
-            _pack_tables.clear()
+        # a captured graph reads its table through a raw pointer.  The oldest table goes, never all of them: a trainer's
+        # warm-up step files one table per network, and the recording that follows must find every one of them (a table
+        # built inside a recording would be a host-to-device copy on a capturing stream).
+        while len(_pack_tables) > 64 and not _ws.pinned:
+            del _pack_tables[next(iter(_pack_tables))]
         _pack_tables[key] = tab
     check(lib.s2i_pack_conv_weights_batched(ptr(tab[1]), tab[2], tab[3], tab[4], stream()), "s2i_pack_conv_weights_batched")
     for p, mode, out in entries:
@@ -1227,3 +1230,28 @@ def images_from_uint8_hwc(u8):
     out = torch.empty((B, 3, H, W), dtype=torch.float32, device=u8.device)
     check(lib.s2i_u8_to_image(ptr(u8), ptr(out), B, H, W, stream()), "s2i_u8_to_image")
     return out
+
+
+def image_batch(pool, offsets, sizes, plan, size, levels, tab1=None, tab2=None):
+    """Crop, mirror, pyramid and normalise a planned batch out of a resident uint8 image pool (device_loader.py) in one
+    launch: `plan` is the (n, 4) int32 device table (pool index, top, left, flip); returns `levels` float NCHW tensors
+    (n, 3, size >> i, size >> i), largest first -- what `images_from_uint8_hwc` gives for the host path's uint8 batches
+    (datasets.py:40-66 behind main.py:127-131), bit for bit.  `tab1` / `tab2` are `device_loader.coeff_table` of
+    size -> size / 2 and size -> size / 4 on the device."""
+    lib = _lib_ready()
+    assert pool.dtype == torch.uint8 and pool.dim() == 1 and pool.is_contiguous()
+    assert offsets.dtype == torch.int64 and sizes.dtype == torch.int32 and sizes.shape == (offsets.numel(), 2)
+    assert plan.dtype == torch.int32 and plan.dim() == 2 and plan.shape[1] == 4 and plan.is_contiguous()
+    assert offsets.is_contiguous() and sizes.is_contiguous()
+    n = plan.shape[0]
+    tabs = [None, tab1, tab2]
+    for i in range(1, levels):
+        want = (size >> i, 1 + (4 << (i - 1)))
+        assert tabs[i] is not None and tabs[i].dtype == torch.int32 and tuple(tabs[i].shape) == want, (i, want)
+        assert tabs[i].is_contiguous()
+    outs = [torch.empty((n, 3, size >> i, size >> i), dtype=torch.float32, device=pool.device) for i in range(levels)]
+    o = outs + [None] * (3 - len(outs))
+    check(lib.s2i_image_batch(ptr(pool), pool.numel(), ptr(offsets), ptr(sizes), offsets.numel(), ptr(plan), n, size,
+                              levels, ptr(tab1), ptr(tab2), ptr(o[0]), ptr(o[1]), ptr(o[2]), stream()),
+          "s2i_image_batch")
+    return outs
