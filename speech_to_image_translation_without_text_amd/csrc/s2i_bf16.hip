@@ -2,7 +2,7 @@
 // weights as bf16 (fp32 masters stay in the trainer's flat buffers), products on v_mfma_f32_32x32x16_bf16 with fp32
 // accumulation, BatchNorm statistics taken from the fp32 accumulators.
 //
-// What is different from the fp32 / split kernels of s2i_igemm.hip (which gather an im2col chunk per 32-deep K step
+// What is different from the fp32 / split kernels of s2i_conv_fwd.hip (which gather an im2col chunk per 32-deep K step
 // from global memory, i.e. pull every input pixel through L2 once per tap):
 //   * the block stages a 2-D input PATCH with its halo in LDS once per channel chunk -- the pixels of TB images x
 //     (TH-1)*s+KH rows x (TW-1)*s+KW columns -- and every tap reads its MFMA A-fragments from that patch at a

@@ -1,6 +1,6 @@
 // Memory-bound pieces of the BVLC GoogLeNet feature extractor (Audio_to_Image/prepare_image_feature.py:86-118, the
 // deploy network up to pool5/7x7_s1): the 10-view input stage, the two LRN + max-pool pairs of the stem and the 3x3 max
-// pools with Caffe's ceil rule.  The convolutions are s2i_conv2d_forward (s2i_igemm.hip).  NHWC fp32 throughout.
+// pools with Caffe's ceil rule.  The convolutions are s2i_conv2d_forward (s2i_conv2d.hip).  NHWC fp32 throughout.
 #include "s2i_common.h"
 
 namespace {

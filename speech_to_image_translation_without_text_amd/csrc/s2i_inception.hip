@@ -1,5 +1,5 @@
 // Memory-bound pieces of the Inception-v3 scorer (StackGAN_v2/model.py:17-109): the input stage, the pools and the
-// softmax.  The convolutions and the fc are s2i_conv2d_forward (s2i_igemm.hip).  NHWC fp32 throughout.
+// softmax.  The convolutions and the fc are s2i_conv2d_forward (s2i_conv2d.hip).  NHWC fp32 throughout.
 #include "s2i_common.h"
 
 namespace {

@@ -7,11 +7,13 @@
 // pointers (owned by the graph, which the caller keeps alive together with the memory pool the capture allocated from).
 // s2i_plan_replay then issues hipLaunchKernel / hipMemsetAsync / hipMemcpyAsync in that order on the stream it is given.
 //
-// Why not hipGraphLaunch: on ROCm 7.2 replaying these graphs costs more than the Python host path it was meant to replace
-// (38.6 vs 31.6 ms per fp32 step, 23.4 vs 17.2 ms in the bf16 mode, one graph per stream piece: profiles/r03_graph_replay.md);
-// a plain launch from C costs ~3 us of host time, and pieces on different streams stay concurrent because each
-// is launched on its own stream with ordinary stream waits between them (the reference's loop body, trainer.py:536-572, has
-// no such structure: this is host-side machinery of the MI355X build).
+// Beside hipGraphLaunch: profiles/r03_replay_and_stream_priority.md (sections 3 and 4).  The first measurement had both
+// executors at ~38.5 ms per fp32 step against 31.6 for the Python step (23.5 vs 17.3 in the bf16 mode), which was the
+// high-priority discriminator stream, not the replay; with that priority removed the Python step, this plan and
+// hipGraphLaunch per piece take the same time (31.84 / 31.82 / 31.78 ms fp32, 17.20 / 17.09 / 17.14 ms bf16: the step is
+// GPU-bound).  A plain launch from C costs ~3 us of host time (2.1 ms per step against 12.4 ms in Python), and pieces on
+// different streams stay concurrent because each is launched on its own stream with ordinary stream waits between them
+// (the reference's loop body, trainer.py:536-572, has no such structure: this is host-side machinery of the MI355X build).
 #include "s2i_common.h"
 #include <string.h>
 #include <vector>

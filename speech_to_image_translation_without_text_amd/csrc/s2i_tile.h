@@ -1,5 +1,6 @@
-// Tile pieces shared by the matrix kernels of s2i_igemm.hip and s2i_bf16.hip (internal).  Every kernel there keeps its
-// result as f32x16 acc[TM][TN]: a wave owns TM x TN MFMA tiles of 32 x 32, wave (wm, wn) of the block's WAVES_M x WAVES_N.
+// Tile pieces shared by the matrix kernels of the convolution units (s2i_conv_fwd.hip, s2i_wgrad.hip, s2i_conv2d.hip) and
+// s2i_bf16.hip (internal).  Every kernel there keeps its result as f32x16 acc[TM][TN]: a wave owns TM x TN MFMA tiles of
+// 32 x 32, wave (wm, wn) of the block's WAVES_M x WAVES_N.
 // The helpers take plain arguments, no kernel parameter struct, and the caller supplies what differs between kernels (how a
 // tile row becomes an output row) as a lambda.  All of them are __forceinline__: a kernel's accumulators stay in registers.
 #pragma once

@@ -33,7 +33,7 @@ MAX_BATCH = 48
 MEAN_BGR = (104.00698793, 116.66876762, 122.67891434)
 LRN_SIZE, LRN_ALPHA, LRN_BETA, LRN_K = 5, 1e-4, 0.75, 1.0
 
-# s2i_conv2d_forward addresses every tensor with 32-bit byte offsets below this bound (conv2d_validate, s2i_igemm.hip);
+# s2i_conv2d_forward addresses every tensor with 32-bit byte offsets below this bound (conv2d_validate, s2i_conv2d.hip);
 # the largest tensor of a chunk is conv1/7x7_s2's output, (10 B, 112, 112, 64) fp32
 CONV2D_BYTE_LIMIT = 0x7FFF0000
 assert MAX_BATCH * VIEWS * 112 * 112 * 64 * 4 < CONV2D_BYTE_LIMIT

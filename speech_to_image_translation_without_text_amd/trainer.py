@@ -345,8 +345,9 @@ class condGANTrainer(object):
         high HIP priority for 0.3 ms per step.  Round 3 found what that costs: while a high-priority queue holds PENDING
         packets -- the next step's discriminator work waiting on an event -- every other queue's kernels run slower, so a
         host that runs more than one step ahead made the step 20 % slower: 38.7 vs 31.6 ms, all of it in the generator's
-        single-stream pieces (tools/replay_pieces.py, profiles/r03_replay_regimes.txt).  That, not branch serialisation,
-        was also why hipGraph replay looked slow.)  The streams are shared by every trainer of the process."""
+        single-stream pieces (tools/replay_pieces.py, profiles/r03_replay_and_stream_priority.md section 3).  That, not
+        branch serialisation, was also why hipGraph replay looked slow: with the priority removed the Python step, the launch
+        plan and hipGraphLaunch take the same time (section 4 there).)  The streams are shared by every trainer of the process."""
         key = (torch.cuda.current_device(), self.num_Ds)
         if key not in _D_STREAMS:
             _D_STREAMS[key] = [torch.cuda.Stream() for i in range(self.num_Ds)]

@@ -878,7 +878,7 @@ def _oracle_fp64(netG, z, c, eps):
 def test_eval_generator_images_do_not_depend_on_the_batch(gpu):
     """A row of a 96-image launch against the single-image run of the same inputs.  These are NOT bit-identical: the
     generator's convolutions are the train step's igemm_fwd kernels, whose planner (plan_fwd / fwd_splitk in
-    csrc/s2i_igemm.hip) splits K over several blocks when a launch has fewer than 768 blocks and sums the slabs in
+    csrc/s2i_conv.hip) splits K over several blocks when a launch has fewer than 768 blocks and sums the slabs in
     splitk_reduce_kernel, so the summation order of a single-image launch differs from the 96-image one (measured:
     7.5e-7 on the last-stage image).  Equality is therefore replaced by the whole-network bound that exists
     for eval G, rtol 1e-3 / atol 1e-4 against the oracle (here run in fp64), for the row of the 96-image launch and for

@@ -157,7 +157,7 @@ def test_tuning_knobs_roundtrip_without_a_gpu():
 
 
 def test_weight_gradient_planner_tile_heights_without_a_gpu():
-    """The weight-gradient planner's three bf16 tile shapes and two fp32 ones (s2i_igemm.hip::plan_wgrad) through the
+    """The weight-gradient planner's three bf16 tile shapes and two fp32 ones (s2i_wgrad_plan.hip::plan_wgrad) through the
     workspace query: every plan asks for a whole number of K x N fp32 slabs, a forced shape is honoured only where 256
     divides the taps x channels rows (and, for 256 x 256, the output channels), and the cost model picks the large tiles on
     D_NET256's stacked stride-2 layers."""
