@@ -1,4 +1,5 @@
-"""The non-matrix entry points of the train step (csrc/s2i_elementwise.hip): their argument lists, the gamma of each
+"""The non-matrix entry points of the train step (csrc/s2i_bn.hip, s2i_layout.hip, s2i_cvec.hip, s2i_losses.hip,
+s2i_optim.hip): their argument lists, the gamma of each
 family and the replay of one record against tests/elementwise_ref.py in fp64.  tests/test_step_elementwise_gpu.py documents
 the operands, the bound and the mutations and runs the replays over the train step; tests/test_eval_launches_gpu.py runs
 them over the eval-mode generator.  run() notes what it measured in the ledger of the suite that called it."""

@@ -1,6 +1,7 @@
 """Every non-matrix launch of the train step, at its production shape, against a plain fp64 reference.
 
-The BatchNorm, activation, layout, loss and optimiser kernels of csrc/s2i_elementwise.hip pick their variants from the
+The BatchNorm, activation, layout, loss and optimiser kernels of csrc/s2i_bn.hip, s2i_layout.hip, s2i_cvec.hip,
+s2i_losses.hip and s2i_optim.hip pick their variants from the
 launch's shape (finalize: small kernel up to 8 partial rows per group, else the shuffle or LDS reduction; bf16 forward:
 8- or 4-channel row kernel; backward apply: the walker with its rows per block; colreduce: the row chunks per group), so
 they are tested at the shapes the step really launches:
