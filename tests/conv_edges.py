@@ -1,0 +1,413 @@
+"""Hand-written convolution launches at the edges of the tile kernels: partly filled row tiles, column and K tails, short
+last K splits, pixel-chunk tails of the weight gradients, ragged image tiles of the bf16 kernels.
+
+The train step's census (tests/step_launches.json) holds production shapes only: batches of 24 / 48 (72 / 144 stacked)
+on power-of-two maps, where every GEMM is a whole number of row tiles and pixel chunks.  The records below use the
+census schema, so conv_replay.replay_conv / replay_wgrad run them unchanged, and carry extra keys the replay ignores:
+
+  why        one line on what the shape is for
+  reach      the plan features the record claims (REACH below); tests/test_conv_edges_cpu.py derives them from the
+             planners' host queries and asserts them, tests/test_conv_edges_gpu.py replays the record in fp64
+  tile_rows  the value of ops.TILE_ROWS the replay runs under (0 = the planner's choice)
+  tune       planner knobs (_lib.tuning) the replay runs under
+
+The constructors fill in the packed-weight shape, wR, ldw, w_offset and fast the way ops.ConvBnAct / ConvAct and
+ops._dgrad / _wgrad launch the layer."""
+from speech_to_image_translation_without_text_amd import ops
+
+KH = {"k1": 1, "k3s1": 3, "k4s2": 4, "up": 3}
+
+# the plan features a record may claim
+REACH = (
+    "rowtail-128",        # fp32 forward: 128 x 128 tiles, the last row tile partly filled
+    "rowtail-96",         # 96 x 128 tiles, the last row tile partly filled
+    "rowtail-128x64",     # 128 x 64 tiles (32 < N <= 64)
+    "rowtail-128x32",     # 128 x 32 tiles (N <= 32)
+    "single-partial-tile",  # one row tile per phase, partly filled
+    "coltail",            # N is no multiple of the tile width
+    "ktail",              # K = taps x channels is no multiple of the 32-deep chunk
+    "short-last-split",   # split-K whose last split has fewer chunks than the others
+    "rowtail-4phase",     # a partly filled row tile in each of the 4 phases of a transposed convolution
+    "groups-96",          # grouped BatchNorm statistics on groups of whole 96-row (not 128-row) tiles
+    "wg-pixtail-t0", "wg-pixtail-t1", "wg-pixtail-t3", "wg-pixtail-t4", "wg-pixtail-t5", "wg-pixtail-t8",
+    "wg-pixtail-t9",      # weight gradient: the pixel range ends on a short 32-pixel chunk, per tile shape of plan_wgrad
+    "wg-rows3-odd-batch",  # the row-segment kernel (3x3, W >= 32) at its smallest map with a batch that is no power of two
+    "b16-ragged-128",     # bf16 forward, 128-pixel kernel: the last tile holds fewer images than the others
+    "b16-ragged-256",     # the same on the 256-pixel kernel
+    "b16-persist-uneven",  # persistent 256-pixel kernel: the blocks walk different numbers of tiles
+    "b16-wg-stagetail",   # bf16 weight gradient: the pixel range ends on a short 64-pixel stage
+)
+
+
+def _r4(v):
+    return (v + 3) & ~3
+
+
+def _packed(layer, O, I):
+    return [16 if layer == "up" else KH[layer] ** 2, _r4(I), _r4(O)]
+
+
+def _dt(bf16):
+    return "bf16" if bf16 else "f32"
+
+
+def _extra(rec, why, reach, tile_rows, tune):
+    assert set(reach) <= set(REACH), reach
+    rec.update(why=why, reach=sorted(reach), tile_rows=tile_rows, tune=dict(tune or {}))
+    return rec
+
+
+def fwd(layer, B, H, Cx, N, why, reach, *, Cc=0, cls=0, stats=True, groups=1, bf16=False, tile_rows=0, tune=None):
+    """Forward of ops.ConvBnAct: x [B, H, H, Cx] (+ a broadcast vector of Cc channels, or cls leading weight rows folded
+    into the class-bias table) -> N channels."""
+    I = Cx + Cc + cls
+    packed = _packed(layer, N, I)
+    rec = dict(fn="conv_any" if bf16 else "conv_raw", kind=ops._KIND[layer], wmode=0, flip=0, x=[[B, H, H, Cx], _dt(bf16)],
+               w=dict(packed=packed, oihw=[N, I, KH[layer], KH[layer]], mode=ops.PACK_UPFOLD if layer == "up" else
+                      ops.PACK_PLAIN), N=N, out_dtype=_dt(bf16), stats=stats, groups=groups, w_offset=cls * packed[2],
+               cvec=Cc, cls_bias=bool(cls), bias=0, act=0, fast=bf16)
+    if not bf16:
+        rec.update(wR=packed[1], ldw=packed[2])
+    return _extra(rec, why, reach, tile_rows, tune)
+
+
+def dgrad(layer, B, H, Cx, O, why, reach, *, bf16=False, tile_rows=0, tune=None):
+    """Input gradient of a layer Cx -> O channels on an H x H input (ops._dgrad): dy [B, Ho, Ho, Op] -> [B, H, H, Cx]."""
+    kind, flip = ops._DGRAD[layer]
+    packed = _packed(layer, O, Cx)
+    Ho = {"k1": H, "k3s1": H, "k4s2": H // 2, "up": 2 * H}[layer]
+    rec = dict(fn="conv_any" if bf16 else "conv_raw", kind=kind, wmode=1, flip=flip, x=[[B, Ho, Ho, packed[2]], _dt(bf16)],
+               w=dict(packed=packed, oihw=[O, Cx, KH[layer], KH[layer]], mode=ops.PACK_UPFOLD if layer == "up" else
+                      ops.PACK_PLAIN), N=Cx, out_dtype=_dt(bf16), stats=False, groups=1, w_offset=0, cvec=0, cls_bias=False,
+               bias=0, act=0, fast=bf16)
+    if not bf16:
+        rec.update(wR=packed[1], ldw=packed[2])
+    return _extra(rec, why, reach, tile_rows, tune)
+
+
+def wgrad(layer, B, H, Cin, N, why, reach, *, Cc=0, a16=False, g16=False, accumulate=False, out=False, i_off=0, tune=None):
+    """Weight gradient of a layer Cin (+ Cc broadcast) -> N channels on an H x H input (ops._wgrad); the up layer gathers dy
+    by the k4s2 pattern against the layer input (swap, fold).  i_off > 0: the written slice of a wider tensor."""
+    k = KH[layer]
+    Ho = {"k1": H, "k3s1": H, "k4s2": H // 2, "up": 2 * H}[layer]
+    fn = "wgrad_any" if (a16 or g16) else "wgrad_raw"
+    if layer == "up":
+        rec = dict(fn=fn, kind=ops.CONV_K4S2, a=[[B, Ho, Ho, N], _dt(g16)], cvec=0, g=[[B, H, H, Cin], _dt(a16)],
+                   grad_shape=[N, Cin, 3, 3], swap=1, fold=1)
+    else:
+        rec = dict(fn=fn, kind=ops._KIND[layer], a=[[B, H, H, Cin], _dt(a16)], cvec=Cc, g=[[B, Ho, Ho, N], _dt(g16)],
+                   grad_shape=[N, Cin + Cc, k, k] if k > 1 else [N, Cin + Cc], swap=0, fold=0)
+    rec.update(out=bool(out or accumulate or i_off), accumulate=accumulate, i_off=i_off, I_total=i_off + Cin if i_off else 0)
+    return _extra(rec, why, reach, 0, tune)
+
+
+def _tiles(make, heights):
+    """One record per forced tile height (0 = the planner's choice)."""
+    return [make(tr) for tr in heights]
+
+
+def _table():
+    t = []
+    # ---- fp32 forward ------------------------------------------------------------------------------------------------
+    t += _tiles(lambda tr: fwd("k3s1", 5, 8, 64, 128, "M = 320: 96-row tiles end on 32 rows, 128-row tiles on 64; K split "
+                               "with a short last split", {0: ["short-last-split"], 96: ["rowtail-96", "short-last-split"],
+                                                           128: ["rowtail-128", "short-last-split"]}[tr], tile_rows=tr),
+                (0, 96, 128))
+    t += _tiles(lambda tr: fwd("k3s1", 11, 8, 64, 256, "M = 704: row tail under both heights, two column tiles",
+                               {0: ["short-last-split"], 96: ["rowtail-96", "short-last-split"],
+                                128: ["rowtail-128", "short-last-split"]}[tr], tile_rows=tr), (0, 96, 128))
+    t += _tiles(lambda tr: fwd("k3s1", 5, 8, 40, 136, "row tail, K = 360 (tail 8), N = 136 (tail 8); Cx % 32 != 0 takes the "
+                               "general gather", {0: ["rowtail-96", "coltail", "ktail"], 96: ["rowtail-96", "coltail", "ktail"],
+                                                  128: ["rowtail-128", "coltail", "ktail"]}[tr], tile_rows=tr), (0, 96, 128))
+    t += _tiles(lambda tr: fwd("k4s2", 7, 16, 64, 128, "M = 448: five 96-row or four 128-row tiles, 64 rows in the last",
+                               {0: [], 96: ["rowtail-96"], 128: ["rowtail-128"]}[tr], tile_rows=tr), (0, 96, 128))
+    t.append(fwd("k4s2", 3, 16, 64, 64, "128 x 64 tile, M = 192: the second row tile half filled, K split", ["rowtail-128x64"]))
+    t.append(fwd("k3s1", 5, 8, 32, 32, "128 x 32 tile, M = 320, unsplit: per-tile partial sums with a 64-row last tile",
+                 ["rowtail-128x32"]))
+    t.append(fwd("up", 5, 4, 64, 128, "transposed conv, M = 80: one partly filled tile in each of the 4 phases",
+                 ["rowtail-4phase", "single-partial-tile"]))
+    t.append(fwd("up", 3, 8, 64, 136, "transposed conv, M = 192, N = 136: column tail under phases", ["coltail"]))
+    t.append(fwd("up", 5, 8, 64, 128, "transposed conv, M = 320, 128-row tiles: a 64-row last tile in each phase",
+                 ["rowtail-4phase", "rowtail-128"], tile_rows=128))
+    t.append(fwd("up", 5, 8, 64, 128, "transposed conv, M = 320, 96-row tiles: a 32-row last tile in each phase",
+                 ["rowtail-4phase", "rowtail-96"], tile_rows=96))
+    t.append(fwd("k3s1", 1, 4, 512, 128, "one image, M = 16, broadcast vector of 32 channels; deep K split with a short last "
+                 "split", ["single-partial-tile", "short-last-split"], Cc=32))
+    t.append(fwd("k3s1", 5, 4, 128, 64, "M = 80 on the 128 x 64 tile, broadcast vector, K split",
+                 ["single-partial-tile", "rowtail-128x64"], Cc=32))
+    t.append(fwd("k1", 5, 1, 100, 2048, "the generator's fc at batch 5: M = 5, K = 228 (tail 4), broadcast vector of 128",
+                 ["single-partial-tile", "ktail"], Cc=128))
+    t.append(fwd("k4s2", 9, 16, 64, 128, "three stacked BatchNorm batches of 3 images: groups of 192 rows = 2 x 96, no "
+                 "multiple of 128", ["groups-96"], groups=3))
+    t.append(fwd("k4s2", 9, 16, 16, 128, "the same groups with K = 256, unsplit: per-tile partial sums, two 96-row tiles per "
+                 "group", ["groups-96"], groups=3))
+    t.append(fwd("k3s1", 5, 16, 32, 64, "class-bias table (32 folded weight rows), unsplit as ops launches it, 5 images on "
+                 "the 128 x 64 tile", [], cls=32))
+    t.append(fwd("k3s1", 7, 16, 32, 128, "class-bias table, unsplit, M = 1792 = 18 x 96 + 64: the border classes of the tail "
+                 "rows depend on their pixel position", ["rowtail-96"], cls=128, tile_rows=96))
+    t.append(fwd("k3s1", 5, 16, 32, 128, "class-bias table, unsplit, M = 1280 = 13 x 96 + 32", ["rowtail-96"], cls=128,
+                 tile_rows=96))
+    # ---- fp32 input gradient -----------------------------------------------------------------------------------------
+    t += _tiles(lambda tr: dgrad("k3s1", 5, 8, 128, 64, "flipped 3x3 input gradient, M = 320",
+                                 {0: ["short-last-split"], 96: ["rowtail-96", "short-last-split"],
+                                  128: ["rowtail-128", "short-last-split"]}[tr], tile_rows=tr), (0, 96, 128))
+    t += _tiles(lambda tr: dgrad("k3s1", 11, 8, 136, 40, "flipped 3x3 input gradient, M = 704, N = 136 (column tail), K = "
+                                 "360 (K tail)", {96: ["rowtail-96", "coltail", "ktail"],
+                                                  128: ["rowtail-128", "coltail", "ktail"]}[tr], tile_rows=tr), (96, 128))
+    t.append(dgrad("k4s2", 3, 16, 136, 64, "stride-2 input gradient = transposed conv on dy [3, 8, 8, 64]: M = 192 per "
+                   "phase, N = 136", ["coltail"]))
+    t.append(dgrad("k4s2", 5, 8, 128, 64, "stride-2 input gradient, M = 80 per phase", ["rowtail-4phase",
+                                                                                        "single-partial-tile"]))
+    t.append(dgrad("up", 5, 4, 64, 128, "up-block input gradient (stride-2 gather of dy on the folded weights), M = 80",
+                   ["single-partial-tile", "rowtail-128x64"]))
+    # ---- fp32 weight gradient ----------------------------------------------------------------------------------------
+    t.append(wgrad("k3s1", 5, 4, 160, 64, "M = 80: chunks of 32 + 32 + 16 pixels; 128 x 64 tile; K = 1440 (tail 32)",
+                   ["wg-pixtail-t1"]))
+    t.append(wgrad("k3s1", 3, 4, 40, 136, "M = 48, K = 360, N = 136: pixel, K and column tails together", ["wg-pixtail-t0"]))
+    for bm, f in ((128, "wg-pixtail-t0"), (256, "wg-pixtail-t8")):
+        t.append(wgrad("k4s2", 5, 8, 64, 128, "M = 80, K = 1024", [f], tune=dict(wgrad_bm=bm)))
+    for bm, f in ((128, "wg-pixtail-t0"), (256, "wg-pixtail-t8"), (512, "wg-pixtail-t9")):
+        t.append(wgrad("k3s1", 7, 4, 256, 512, "M = 112, K = 2304, N = 512", [f], tune=dict(wgrad_bm=bm)))
+    t.append(wgrad("k4s2", 1, 8, 4, 64, "the first discriminator conv's 64-row tile at one image, M = 16", ["wg-pixtail-t3"]))
+    t.append(wgrad("k3s1", 5, 8, 32, 64, "K = 288 on 96 x 64 tiles, M = 320", []))
+    t.append(wgrad("k3s1", 5, 4, 32, 64, "K = 288 on 96 x 64 tiles, M = 80", ["wg-pixtail-t4"]))
+    t.append(wgrad("k3s1", 5, 8, 32, 32, "K = 288 on 96 x 32 tiles, M = 320", []))
+    t.append(wgrad("k3s1", 3, 4, 32, 32, "K = 288 on 96 x 32 tiles, M = 48", ["wg-pixtail-t5"]))
+    t.append(wgrad("k1", 5, 1, 100, 2048, "the fc's weight gradient at batch 5: one chunk of 5 pixels, broadcast vector",
+                   ["wg-pixtail-t0"], Cc=128))
+    t.append(wgrad("k3s1", 3, 32, 32, 64, "row-segment kernel, W = 32, 3 images", ["wg-rows3-odd-batch"]))
+    t.append(wgrad("k3s1", 3, 32, 64, 128, "row-segment kernel, 64 -> 128 channels, W = 32, 3 images", ["wg-rows3-odd-batch"]))
+    t.append(wgrad("up", 5, 4, 64, 128, "up-block weight gradient (swap, 4x4 taps folded to 3x3), M = 80, K = 2048",
+                   ["wg-pixtail-t1"]))
+    t.append(wgrad("k3s1", 5, 4, 160, 64, "M = 80, accumulated into a prefilled gradient", ["wg-pixtail-t1"], accumulate=True))
+    t.append(wgrad("k3s1", 3, 4, 40, 136, "M = 48, written into input channels [32, 72) of a wider tensor",
+                   ["wg-pixtail-t0"], i_off=32))
+    t.append(wgrad("k4s2", 5, 8, 64, 128, "M = 80, 256 x 128 tile, accumulated into a slice", ["wg-pixtail-t8"],
+                   accumulate=True, i_off=8, tune=dict(wgrad_bm=256)))
+    # ---- bf16 --------------------------------------------------------------------------------------------------------
+    t.append(fwd("k3s1", 5, 4, 256, 512, "4x4 maps: a 128-pixel tile spans 8 images, the batch has 5", ["b16-ragged-128"],
+                 bf16=True))
+    t.append(fwd("k4s2", 9, 16, 64, 128, "8x8 outputs: 2 images per tile, 9 images", ["b16-ragged-128"], bf16=True))
+    t.append(fwd("up", 9, 4, 256, 256, "transposed conv on 4x4 maps: 8 images per tile, 9 images", ["b16-ragged-128"],
+                 bf16=True))
+    t.append(dgrad("k3s1", 5, 4, 256, 512, "input gradient on 4x4 maps, 5 of 8 images", ["b16-ragged-128"], bf16=True))
+    t.append(dgrad("k4s2", 9, 8, 128, 64, "stride-2 input gradient (transposed conv of dy on 4x4 maps), 9 images",
+                   ["b16-ragged-128"], bf16=True))
+    t.append(dgrad("up", 9, 4, 256, 256, "up-block input gradient: stride-2 gather of dy [9, 8, 8, 256]: 4x4 outputs, 8 images "
+                   "per tile", ["b16-ragged-128"], bf16=True))
+    v2 = dict(b16_v2=2, b16_persist=4)
+    t.append(fwd("k3s1", 5, 8, 96, 256, "256-pixel kernel on 8x8 maps: 4 images per tile, 5 images", ["b16-ragged-256"],
+                 bf16=True, tune=v2))
+    t.append(fwd("k4s2", 5, 32, 96, 256, "persistent 256-pixel kernel: 5 one-image tiles over 2 block slots",
+                 ["b16-persist-uneven"], bf16=True, tune=v2))
+    t.append(fwd("up", 5, 8, 192, 256, "256-pixel transposed conv on 8x8 maps: 4 images per tile, 5 images",
+                 ["b16-ragged-256"], bf16=True, tune=v2))
+    t.append(dgrad("k3s1", 5, 8, 256, 96, "256-pixel kernel, input gradient, 5 images on 8x8 maps", ["b16-ragged-256"],
+                   bf16=True, tune=v2))
+    for bm in (128, 256, 512):
+        t.append(wgrad("k3s1", 5, 4, 256, 256, "bf16 x bf16, M = 80: a 64-pixel stage and a 16-pixel one",
+                       ["b16-wg-stagetail"], a16=True, g16=True, tune=dict(wgrad16_bm=bm)))
+        t.append(wgrad("k3s1", 3, 4, 256, 256, "bf16 x bf16, M = 48: less than one stage", ["b16-wg-stagetail"], a16=True,
+                       g16=True, tune=dict(wgrad16_bm=bm)))
+    t.append(wgrad("k4s2", 5, 8, 64, 128, "bf16 x bf16 stride-2, M = 80, accumulated", ["b16-wg-stagetail"], a16=True,
+                   g16=True, accumulate=True))
+    t.append(wgrad("up", 5, 4, 64, 128, "bf16 x bf16 up-block (swap, fold), M = 80", ["b16-wg-stagetail"], a16=True, g16=True))
+    t.append(wgrad("k4s2", 5, 8, 4, 64, "the first discriminator conv in bf16 mode: fp32 NHWC4 image x bf16 gradient, M = 80",
+                   ["b16-wg-stagetail"], g16=True))
+    return t
+
+
+RECORDS = _table()
+
+
+def record_id(i, rec):
+    import launch_ref as R
+    op, layer = R.layer_op(rec)
+    shape = rec["x"][0] if "x" in rec else rec["a"][0]
+    n = rec["N"] if "N" in rec else rec["g"][0][3]
+    tag = "".join("-%s%d" % (k, v) for k, v in sorted(rec["tune"].items())) + ("-tr%d" % rec["tile_rows"] if rec["tile_rows"] else "")
+    return "%03d-%s-%s-%s-B%dH%dC%dN%d%s" % (i, "b16" if "bf16" in (rec.get("out_dtype"), rec.get("a", [0, 0])[1],
+                                                                     rec.get("g", [0, 0])[1]) else "f32", op, layer,
+                                             shape[0], shape[1], shape[3], n, tag)
+
+
+# ---- what a record's plan reaches, from the planners' host queries ---------------------------------------------------
+# The library loads and plans without a device.  What the queries cannot tell is restated from the planner and marked so.
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def _geom(kind, H, W):
+    return ops._geom(kind, H, W) if kind != ops.TCONV_K4S2 else (H, W)     # the planners count rows per phase
+
+
+def conv_desc(rec, **over):
+    """The descriptor ops.conv_raw / conv_any builds for this record (tile_rows reaches conv_raw only)."""
+    from speech_to_image_translation_without_text_amd import _lib
+    B, H, W, Cx = rec["x"][0]
+    raw = rec["fn"] == "conv_raw"
+    wR, ldw = (rec["wR"], rec["ldw"]) if raw else rec["w"]["packed"][1:]
+    f = dict(kind=rec["kind"], B=B, H=H, W=W, Cx=Cx, Cc=rec["cvec"], N=rec["N"], wmode=rec["wmode"], flip=rec["flip"], wR=wR,
+             ldw=ldw, act=rec["act"], stats=int(rec["stats"]), ldy=rec["N"], groups=rec["groups"], nosplit=int(rec["cls_bias"]),
+             kw=0, stride=0, pad=0, tile_rows=rec.get("tile_rows", 0) if raw else 0, in_act=0, in_groups=0)
+    f.update(over)
+    return _lib.ConvDesc(*[f[n] for n, _ in _lib.ConvDesc._fields_])
+
+
+def wgrad_desc(rec):
+    from speech_to_image_translation_without_text_amd import _lib
+    B, H, W, Ca = rec["a"][0]
+    N = rec["g"][0][3]
+    gs = rec["grad_shape"]
+    O, I, KH_, KW_ = gs if len(gs) == 4 else (gs[0], gs[1], 1, 1)
+    return _lib.WgradDesc(rec["kind"], B, H, W, Ca, rec["cvec"], N, N, rec["swap"], rec["fold"], O, I, KH_, KW_,
+                          int(rec["accumulate"]), rec["i_off"], rec["I_total"], 0, 0)
+
+
+def conv_plan(rec):
+    """dict(M, nphases, K, nchunks, splitk, cps, bm or None, BN, reach) of a conv_raw / conv_any record under its own
+    tile_rows and knobs."""
+    import ctypes
+    from speech_to_image_translation_without_text_amd import _lib
+    lib = _lib.load()
+    B, H, W, Cx = rec["x"][0]
+    kind, N = rec["kind"], rec["N"]
+    nph = 4 if kind == ops.TCONV_K4S2 else 1
+    Ho, Wo = _geom(kind, H, W)
+    M = B * Ho * Wo
+    K = ops._TAPS[kind] * (Cx + rec["cvec"])
+    reach = set()
+    with _lib.tuning(**rec.get("tune", {})):
+        if rec["fast"]:
+            return _bf16_plan(rec, lib, M, nph, Ho, Wo)
+        d = conv_desc(rec)
+        ws = lib.s2i_conv_workspace_bytes(ctypes.byref(d))
+        slab = M * nph * N * 4
+        assert ws % slab == 0, (ws, slab)                 # no thin-kernel table at these sizes
+        sk = max(ws // slab, 1)
+        # rows per tile: the statistics rows of an unsplit plan are gridM x nphases.  A forced height does not depend on the
+        # K split, so it is read from the unsplit twin of the descriptor; the planner's own choice does, so it is known only
+        # where the record itself is unsplit and has statistics.  N <= 64 has 128-row tiles only (plan_fwd: "96 x 128 only").
+        bm = None
+        if N <= 64:
+            bm = 128
+        elif rec.get("tile_rows", 0) or (sk == 1 and rec["stats"]):
+            parts = lib.s2i_conv_stat_parts(ctypes.byref(conv_desc(rec, stats=1, nosplit=1, act=0)))
+            assert parts > 0 and parts % nph == 0, parts
+            c128, c96 = _cdiv(M, 128), _cdiv(M, 96)
+            if c128 != c96:
+                bm = 128 if parts // nph == c128 else 96
+                assert parts // nph == _cdiv(M, bm), (parts, M)
+        if rec["stats"]:
+            assert lib.s2i_conv_stat_parts(ctypes.byref(d)) > 0, lib.s2i_last_error()
+    BN = 128 if N > 64 else (64 if N > 32 else 32)
+    nchunks = _cdiv(K, 32)
+    cps = _cdiv(nchunks, sk)
+    one_tile = M < (96 if N > 64 else 128)
+    tail = bm is not None and M % bm != 0 and not one_tile
+    if tail:
+        reach.add("rowtail-%d" % bm if N > 64 else "rowtail-128x%d" % BN)
+    if one_tile:
+        reach.add("single-partial-tile")
+        if N <= 64:
+            reach.add("rowtail-128x%d" % BN)
+    if nph == 4 and (tail or one_tile):
+        reach.add("rowtail-4phase")
+    if N % BN:
+        reach.add("coltail")
+    if K % 32:
+        reach.add("ktail")
+    if sk > 1 and nchunks % cps:
+        reach.add("short-last-split")
+    if rec["stats"] and rec["groups"] > 1 and (M // rec["groups"]) % 128 != 0 and (M // rec["groups"]) % 96 == 0:
+        reach.add("groups-96")
+    return dict(M=M, nphases=nph, K=K, nchunks=nchunks, splitk=sk, cps=cps, bm=bm, BN=BN, reach=reach)
+
+
+def _bf16_plan(rec, lib, M, nph, Ho, Wo):
+    import ctypes
+    B, N, kind = rec["x"][0][0], rec["N"], rec["kind"]
+    d = conv_desc(rec)
+    assert lib.s2i_conv_bf16_eligible(ctypes.byref(d)) == 1, lib.s2i_last_error()
+    ws = lib.s2i_conv_bf16_workspace_bytes(ctypes.byref(d))
+    sk = max(ws // (M * nph * N * 4), 1)
+    parts = lib.s2i_conv_bf16_stat_parts(ctypes.byref(conv_desc(rec, stats=1, nosplit=1)))
+    assert parts > 0 and parts % nph == 0, parts
+    grid_m = parts // nph
+    ck = lib.s2i_conv_bf16_weight_layout(ctypes.byref(d)) & 0xff
+    # pixels per tile: the tile is as wide as the map (up to 32), then rows, then images (plan_bf16); the tile count tells
+    # 128 from 256 pixels, and where both give the same count the channel chunk does (16 / 32 against 32 / 64)
+    cand = {}
+    for bm in (128, 256):
+        tw = min(Wo, 32)
+        th = min(bm // tw, Ho)
+        tb = bm // (tw * th)
+        if (Wo // tw) * (Ho // th) * _cdiv(B, tb) == grid_m:
+            cand[bm] = tb
+    assert cand, (grid_m, rec)
+    if len(cand) == 2:
+        big = ck == (64 if kind == ops.TCONV_K4S2 else 32) and kind != ops.CONV_K4S2
+        cand = {256: cand[256]} if big else {128: cand[128]}
+    (bm, tb), = cand.items()
+    reach = set()
+    if B % tb:
+        reach.add("b16-ragged-%d" % bm)
+    # restated from v2_grid_x: the persistent form is the stride-2 256-pixel kernel, unsplit, on b16_persist block slots
+    persist = rec.get("tune", {}).get("b16_persist", 1)
+    if bm == 256 and kind == ops.CONV_K4S2 and sk == 1 and persist > 1:
+        nblk = max(persist // _cdiv(N, 128), 1)
+        if grid_m > nblk and grid_m % nblk:
+            reach.add("b16-persist-uneven")
+    return dict(M=M, nphases=nph, splitk=sk, bm=bm, tb=tb, gridM=grid_m, reach=reach)
+
+
+def wgrad_plan(rec):
+    """dict(M, K, N, tile, rows3, splitk, reach).  The workspace query gives the split count; the tile shape is restated
+    from plan_wgrad: tiles 0 - 5 follow from K and N alone, 8 / 9 (fp32) and 6 / 7 (bf16) are forced through the knobs wgrad_bm /
+    wgrad16_bm where 256 divides K (and N), and the row-segment kernel takes 3x3 layers of 32 / 64 channels on maps at least 32 wide."""
+    import ctypes
+    from speech_to_image_translation_without_text_amd import _lib
+    lib = _lib.load()
+    d = wgrad_desc(rec)
+    a16, g16 = rec["a"][1] == "bf16", rec["g"][1] == "bf16"
+    B, H, W, Ca = rec["a"][0]
+    Ho, Wo = ops._geom(rec["kind"], H, W)
+    M, N = B * Ho * Wo, d.N
+    K = ops._TAPS[rec["kind"]] * (Ca + rec["cvec"])
+    tune = rec.get("tune", {})
+    with _lib.tuning(**tune):
+        ws = lib.s2i_wgrad_workspace_bytes_dt(ctypes.byref(d), int(a16), int(g16))
+        if not (a16 or g16):
+            assert ws == lib.s2i_wgrad_workspace_bytes(ctypes.byref(d))
+    assert ws > 0 and ws % (K * N * 4) == 0, (ws, K, N, lib.s2i_last_error())
+    sk = ws // (K * N * 4)
+    fp32 = not (a16 or g16)
+    tile = 0 if N > 64 else (1 if N > 32 else 2)
+    if K <= 64 and 32 < N <= 64:
+        tile = 3
+    if fp32 and K % 96 == 0 and N <= 64 and _cdiv(K, 128) * 128 * 5 > K * 6:
+        tile = 4 if N > 32 else 5
+    force = tune.get("wgrad_bm", 0)
+    if fp32 and tile == 0 and K % 256 == 0 and force in (256, 512):
+        tile = 9 if (force == 512 and N % 256 == 0) else 8
+    elif fp32 and tile == 0 and K % 256 == 0:
+        assert force == 128, "a weight gradient that may take the 256-row tiles needs wgrad_bm set: %r" % (rec,)
+    force16 = tune.get("wgrad16_bm", 0)
+    if a16 and g16 and tile == 0 and K % 256 == 0 and force16 in (256, 512):
+        tile = 7 if (force16 == 512 and N % 256 == 0) else 6
+    rows3 = (fp32 and rec["kind"] == ops.CONV_K3S1 and rec["cvec"] == 0 and Ca in (32, 64) and W >= 32 and N % 32 == 0
+             and N <= 128)
+    reach = set()
+    if a16 and g16 or (g16 and Ca == 4):
+        if M % 64:
+            reach.add("b16-wg-stagetail")
+    elif rows3:
+        if B & (B - 1):
+            reach.add("wg-rows3-odd-batch")
+    elif M % 32:
+        reach.add("wg-pixtail-t%d" % tile)
+    return dict(M=M, K=K, N=N, tile=tile, rows3=rows3, splitk=sk, reach=reach)
+
+
+def plan(rec):
+    return conv_plan(rec) if rec["fn"].startswith("conv") else wgrad_plan(rec)

@@ -136,7 +136,8 @@ def conv_ref(rec, op, layer, x, cvec, W, Op, table, bias, mutate=False):
 
 def replay_conv(rec, gen, dev, what, ledger, extra=None):
     """extra(ctx), if given, runs before the assertions with the operands, the output and the bound of this replay
-    (tests/test_eval_launches_gpu.py adds its power checks there) and returns a list of failure messages."""
+    (tests/test_eval_launches_gpu.py and tests/test_conv_edges_gpu.py add their power checks there) and returns a list of
+    failure messages."""
     from speech_to_image_translation_without_text_amd import ops
     op, layer = R.layer_op(rec)
     x = _operand(rec["x"], gen, dev)
@@ -198,7 +199,7 @@ def replay_conv(rec, gen, dev, what, ledger, extra=None):
     # power: one input channel's contribution removed
     _, mref = conv_ref(rec, op, layer, xd, d(cvec), W, Op, d(table), d(bias), mutate=True)
     sees_channel = LH.fails(out, R.act(mref, rec["act"]), absref, rnd, gamma)
-    stats_ok = True
+    stats_ok, stats = True, None
     if rec["stats"]:
         G = max(rec["groups"], 1)
         assert part is not None and nparts % G == 0, (what, nparts, G)
@@ -206,11 +207,12 @@ def replay_conv(rec, gen, dev, what, ledger, extra=None):
         sref = R.group_stats(pre, G)
         den = torch.stack((R.group_stats(absref, G)[0], 2 * (absref * pre.abs()).reshape(G, B // G, N, -1).sum((1, 3))))
         sratio, stats_ok = LH.compare(got, sref, den, 0.0, GAMMA_STATS)
+        stats = dict(got=got, den=den, groups=G)
         ledger.note("stats", sratio, what, GAMMA_STATS)
         print("%s: stats ratio %.3e (gamma %.3e)" % (what, sratio, GAMMA_STATS))
     more = [] if extra is None else extra(dict(rec=rec, op=op, layer=layer, x=xd, cvec=d(cvec), W=W, Op=Op, table=d(table),
                                                bias=d(bias), out=out, ref=ref, absref=absref, rnd=rnd, gamma=gamma,
-                                               ratio=ratio, cls=cls))
+                                               ratio=ratio, cls=cls, pre=pre, stats=stats))
     assert ok, "%s: element error %.3e x absref > gamma %.3e" % (what, ratio, gamma)
     assert stats_ok, "%s: BatchNorm partial sums off" % what
     assert not more, "%s: %s" % (what, "; ".join(more))

@@ -17,6 +17,9 @@ launch's shape, so they are tested here at the shapes the step really launches, 
     prefilled gradient (the written slice = prefill + gradient, every other element bit-identical) are checked too.
   * power: the same comparison must FAIL against a reference with one input channel's contribution removed (a dropped
     K chunk) and, for weight gradients, one image's contribution removed (a dropped pixel-range split).
+
+At these shapes every GEMM is a whole number of row tiles, pixel chunks and bf16 image tiles; partly filled tiles, tails
+and the ragged 23-image batch are tests/test_conv_edges_gpu.py's.
 """
 import os
 import sys
