@@ -345,6 +345,21 @@ int s2i_u8_to_image(const unsigned char* src, float* dst, int B, int H, int W, v
 int s2i_image_batch(const unsigned char* pool, long long pool_bytes, const long long* offsets, const int* sizes,
                     int npool, const int* plan, int n, int S, int L, const int* tab1, const int* tab2, float* out0,
                     float* out1, float* out2, void* stream);
+/* The snapshot grid of the training loop (StackGAN_v2/trainer.py:268-295: `vutils.save_image(img, path, normalize=True)`,
+   i.e. torchvision's make_grid(normalize=True) with its defaults followed by save_image's quantisation), composed on the
+   device.  src holds N three-channel fp32 images addressed by element strides (image, row, column, channel): an NCHW
+   batch and the generator's NHWC4 output alike; a fourth NHWC channel is never read.  dst is ONE uint8 HWC image of
+   ymaps (H + padding) + padding rows by xmaps (W + padding) + padding columns, xmaps = min(nrow, N), ymaps =
+   ceil(N / xmaps); image k has its top-left corner at row (k / xmaps)(H + padding) + padding, column
+   (k % xmaps)(W + padding) + padding; every other pixel, the cells of an incomplete last row included, is 0.
+   fp32, in this order, every operation rounded on its own (no fused multiply-add, IEEE division): lo / hi = minimum /
+   maximum over all N 3 H W values (one pair for the batch); d = max(hi - lo, 1e-5); v = (x - lo) / d; q = v * 255;
+   q = q + 0.5; clamp to [0, 255]; truncate.  A batch that holds a NaN or an infinity is outside the contract.
+   workspace: s2i_image_grid_workspace_bytes() bytes of the caller's (per-block minima and maxima: the reduction and the
+   composition are two launches on `stream` with no host round trip between them). */
+size_t s2i_image_grid_workspace_bytes(void);
+int s2i_image_grid_u8(const float* src, int N, int H, int W, long long stride_n, long long stride_y, long long stride_x,
+                      long long stride_c, int nrow, int padding, float* workspace, unsigned char* dst, void* stream);
 /* sum over the H*W rows of each image of the first C columns of a [B*HW][ld] tensor -> [B][C] */
 int s2i_spatial_sum(const float* src, int ld, int B, int HW, int C, float* dst, void* ws,
                     size_t ws_bytes, void* stream);

@@ -1,5 +1,5 @@
 // What two or more of the HBM-bound units share (internal; s2i_bn.hip, s2i_layout.hip, s2i_cvec.hip, s2i_losses.hip,
-// s2i_rnn.hip, s2i_optim.hip): the sigmoid forms, the 16-byte and scalar loads / stores of fp32 and bf16 tensors, the
+// s2i_rnn.hip, s2i_optim.hip, s2i_grid.hip): the sigmoid forms, the 16-byte and scalar loads / stores of fp32 and bf16 tensors, the
 // thread layout of the per-channel reductions, the grid of a grid-stride launch, the stream and dtype-check macros.  A
 // helper that one unit alone uses stays in that unit.  Kernels are never declared here: each __global__ kernel is defined
 // and instantiated in exactly one unit.

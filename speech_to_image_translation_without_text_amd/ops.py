@@ -1219,6 +1219,40 @@ def images_to_uint8_hwc(img_nhwc):
     return out
 
 
+def image_grid_uint8(images, nrow=8, padding=2, layout="nchw"):
+    """N three-channel images -> ONE (Hg, Wg, 3) uint8 device tensor: the picture the reference's
+    `vutils.save_image(images, path, nrow=8, padding=2, normalize=True)` writes (trainer.py:268-295), i.e. min-max
+    normalised over the whole batch, tiled `nrow` to a line with `padding` black pixels around every cell, quantised as
+    `mul(255).add(0.5).clamp(0, 255)` truncated (s2i_image_grid_u8; DESIGN.md section 8e).  layout "nchw": (N, 3, H, W);
+    "nhwc": (N, H, W, C >= 3), the generator's NHWC4 output, whose further channels are never read.  Any strides (a batch
+    slice, a channel slice) are taken as they are; a tensor that is not fp32 (bf16 activation mode) is converted first."""
+    lib = _lib_ready()
+    if layout not in ("nchw", "nhwc"):
+        raise ValueError("layout must be 'nchw' or 'nhwc'")
+    if images.dim() != 4 or images.shape[3 if layout == "nhwc" else 1] < 3:
+        raise ValueError("image_grid_uint8 takes a 4-d batch with at least three channels, got %s as %s"
+                         % (tuple(images.shape), layout))
+    if images.dtype != torch.float32:
+        images = images.float()
+    images = images.detach()
+    sn, s1, s2, s3 = images.stride()
+    if layout == "nhwc":
+        N, H, W = images.shape[:3]
+        sy, sx, sc = s1, s2, s3
+    else:
+        N, H, W = images.shape[0], images.shape[2], images.shape[3]
+        sc, sy, sx = s1, s2, s3
+    nrow, padding = int(nrow), int(padding)
+    xmaps = max(1, min(nrow, N))
+    ymaps = -(-N // xmaps) if N > 0 else 0
+    out = torch.empty((max(ymaps * (H + padding) + padding, 0), max(xmaps * (W + padding) + padding, 0), 3),
+                      dtype=torch.uint8, device=images.device)
+    ws = _ws.get(lib.s2i_image_grid_workspace_bytes(), images.device)
+    check(lib.s2i_image_grid_u8(ptr(images), N, H, W, sn, sy, sx, sc, nrow, padding, ptr(ws), ptr(out), stream()),
+          "s2i_image_grid_u8")
+    return out
+
+
 # ---- data edge -----------------------------------------------------------------------------------------------------
 def images_from_uint8_hwc(u8):
     """(B,H,W,3) uint8 RGB on the device -> (B,3,H,W) float in [-1,1]: the reference's per-sample

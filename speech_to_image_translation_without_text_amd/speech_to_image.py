@@ -8,6 +8,13 @@ utterance per sequence: cap_len = n_frames // 64, so a clip needs at least 64 fr
 last-stage image, written as `<out_dir>/<wav name>.png`.  G runs in .eval() mode as trainer.evaluate runs it; z and the
 conditioning-augmentation noise are drawn, in that order, from a CPU generator seeded with --seed, so a run is
 reproducible.  --cfg takes the training YAML (G's widths and branch count).
+
+    ... --interpolate 10 a.wav b.wav
+
+takes exactly two WAVs and writes the reference's interpolation strip (StackGAN_v2/interpolation.py:54-88): STEPS + 1
+embeddings on the line between the two utterances, row i = a * (i / STEPS) + b * (1 - i / STEPS) (so image 0 is b's and
+the last one a's), through G as one batch with ONE z and ONE eps shared by every row, as `<out_dir>/interp_<i>.png` and
+side by side, min-max normalised over the strip, as `<out_dir>/interp_grid.png` (ops.image_grid_uint8).
 """
 import argparse
 import os
@@ -56,6 +63,29 @@ def load_generator(path, device):
     return netG.to(device).eval()
 
 
+def interpolation_embeddings(emb_a, emb_b, steps):
+    """(steps + 1, D) rows emb_a * (i / steps) + emb_b * (1 - i / steps), the reference's order
+    (interpolation.py:69-71): row 0 is emb_b, the last row emb_a."""
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("interpolation needs at least one step, got %d" % steps)
+    a, b = emb_a.reshape(1, -1), emb_b.reshape(1, -1)
+    alpha = (torch.arange(steps + 1, dtype=a.dtype, device=a.device) / steps).reshape(-1, 1)
+    return a * alpha + b * (1 - alpha)
+
+
+@torch.no_grad()
+def interpolate(netG, emb_a, emb_b, steps, seed):
+    """G's last-stage NHWC4 images (steps + 1, H, W, 4) of interpolation_embeddings(emb_a, emb_b, steps), one batch, with
+    the single (z, eps) draw of `seed` repeated for every row (interpolation.py:74, 87: one noise for the strip)."""
+    emb = interpolation_embeddings(emb_a, emb_b, steps).contiguous()
+    dev = emb.device
+    z, eps = draw_noise(1, seed)
+    n = emb.shape[0]
+    fake_imgs, _, _ = netG(z.repeat(n, 1).to(dev), emb, eps.repeat(n, 1).to(dev), True)
+    return fake_imgs[-1]
+
+
 @torch.no_grad()
 def generate(netG, emb, seed):
     """uint8 (N, H, W, 3) images of the last stage of G for embeddings `emb` (N, 1024)."""
@@ -75,14 +105,32 @@ def main(argv=None):
     p.add_argument("--bidirectional", action="store_true", default=False)
     p.add_argument("--rnn_layers", type=int, default=1)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--interpolate", type=int, default=None, metavar="STEPS",
+                   help="two WAVs: write the STEPS + 1 images between them (interp_<i>.png, interp_grid.png)")
     args = p.parse_args(argv)
+    if args.interpolate is not None:
+        if len(args.wavs) != 2:
+            p.error("--interpolate takes exactly two WAV files, got %d" % len(args.wavs))
+        if args.interpolate < 1:
+            p.error("--interpolate needs STEPS >= 1")
     if args.cfg:
         cfg_from_file(args.cfg)
     dev = torch.device("cuda", torch.cuda.current_device())
     model = load_encoder(args.model, args.bidirectional, args.rnn_layers, dev)
     emb = embed(model, read_wavs(args.wavs))
-    images = generate(load_generator(args.netG, dev), emb, args.seed)
+    netG = load_generator(args.netG, dev)
     os.makedirs(args.out_dir, exist_ok=True)
+    if args.interpolate is not None:
+        imgs = interpolate(netG, emb[0], emb[1], args.interpolate, args.seed)
+        singles = ops.images_to_uint8_hwc(imgs).cpu().numpy()
+        strip = ops.image_grid_uint8(imgs, nrow=imgs.shape[0], padding=2, layout="nhwc").cpu().numpy()
+        outs = [(os.path.join(args.out_dir, "interp_%d.png" % i), img) for i, img in enumerate(singles)]
+        outs.append((os.path.join(args.out_dir, "interp_grid.png"), strip))
+        for out, img in outs:
+            Image.fromarray(img).save(out)
+            print(out)
+        return
+    images = generate(netG, emb, args.seed)
     for path, img in zip(args.wavs, images):
         out = os.path.join(args.out_dir, os.path.splitext(os.path.basename(path))[0] + ".png")
         Image.fromarray(img).save(out)

@@ -16,8 +16,10 @@ What is built differently (MI355X-first):
   * per-replica BatchNorm statistics and per-replica class-aware loss, as in the reference's DDP.
 The reference's quality metrics are opt-in (TRAIN.INCEPTION_WEIGHTS or enable_inception): the Inception-v3 pass over
 each step's fake and real 256 px images runs on the gfx950 kernels (inception.py) into device buffers, and every snapshot
-with >= 500 collected batches reports the Inception score, NLPP and FID (trainer.py:563-565, 603-629); the image dumps
-of the reference loop are not reproduced.
+with >= 500 collected batches reports the Inception score, NLPP and FID (trainer.py:563-565, 603-629).  Every snapshot
+also writes the reference's image grids (trainer.py:268-295, 589-601): Image/real_samples.png and
+Image/count_<count>_fake_samples<i>.png, from the EMA generator on a noise batch fixed for the run, composed on the device
+(ops.image_grid_uint8); TRAIN.VIS_COUNT = 0 turns them off.  The TensorBoard calls of the reference loop are not reproduced.
 """
 import json
 import os
@@ -339,6 +341,8 @@ class condGANTrainer(object):
         self._inception_rows = []
         if cfg.TRAIN.INCEPTION_WEIGHTS:
             self.enable_inception(cfg.TRAIN.INCEPTION_WEIGHTS)
+        # snapshot grids: z and the conditioning-augmentation noise of the whole run (drawn by train() / on first use)
+        self.fixed_noise = self.fixed_eps = None
 
     def _make_d_streams(self):
         """One stream per discriminator, all at the default priority.  (Round 2 gave the largest discriminator's stream the
@@ -881,11 +885,66 @@ class condGANTrainer(object):
             errD_total = errD_total + e
         return errD_total, errG_total, kl_loss
 
+    # -- snapshot image grids (trainer.py:268-295, 511-512, 589-601) ------------------------------------------------------
+    def draw_fixed_noise(self, device):
+        """fixed_noise (batch_size, Z_DIM) and fixed_eps (batch_size, EMBEDDING_DIM) of the snapshot grids, from a private
+        CPU generator seeded with torch.initial_seed(): neither the global CPU generator nor the device's is advanced, so
+        a seeded run draws the same training noise, and ends in the same weights, with the snapshots on or off.  (The
+        reference fixes z only, from the global generator, and lets CA_NET draw a fresh eps per snapshot.)"""
+        g = torch.Generator().manual_seed(torch.initial_seed())
+        self.fixed_noise = torch.randn(self.batch_size, cfg.GAN.Z_DIM, generator=g).to(device)
+        self.fixed_eps = torch.randn(self.batch_size, cfg.GAN.EMBEDDING_DIM, generator=g).to(device)
+
+    @torch.no_grad()
+    def snapshot_images(self, count, real_imgs, txt_embedding):
+        """The reference's snapshot pictures: G with the EMA weights, in training mode as the reference runs it (BatchNorm on
+        batch statistics), on fixed_noise[:B], the current batch's embeddings and fixed_eps[:B]; then one grid
+        (ops.image_grid_uint8, nrow 8, padding 2) of the first min(VIS_COUNT, B) real images of the last scale and one per
+        scale of the fake ones.  Returns the uint8 (Hg, Wg, 3) device grids, real grid first; rank 0 also writes them as
+        <image_dir>/real_samples.png (overwritten every time) and count_%09d_fake_samples%d.png.  Every rank runs the
+        forward pass.  Runs eagerly on the current stream, after the step's side streams have joined: train() calls it
+        outside the recorded step, so a plan or graph executor never holds it.
+        Deviations: the live weights come back afterwards (as in save()), and so do G's BatchNorm buffers (running_mean,
+        running_var, num_batches_tracked) -- the reference lets the snapshot forward move them; here a snapshot leaves
+        the training state untouched, so checkpoints do not depend on VIS_COUNT.  self.fake_imgs keeps the snapshot's
+        images (NHWC4) as in the reference, except under a captured step, whose self.fake_imgs are the recording's static
+        outputs and stay."""
+        netG = _unwrap(self.netG)
+        B = txt_embedding.shape[0]
+        if self.fixed_noise is None:
+            self.draw_fixed_noise(txt_embedding.device)
+        live = self.flatG.p.clone()
+        buffers = [(b, b.clone()) for b in netG.buffers()]
+        was_training = netG.training
+        load_params(self.netG, self.avg_param_G)
+        netG.train()
+        try:
+            fake_imgs, _, _ = netG(self.fixed_noise[:B], txt_embedding.detach(), self.fixed_eps[:B], True)
+        finally:
+            netG.train(was_training)
+            for b, kept in buffers:
+                b.copy_(kept)
+            self.flatG.p.copy_(live)
+            ops.refresh_packed(self.flatG.params)
+        if self._graph is None or self._graph.get('graphs') is None:
+            self.fake_imgs = fake_imgs
+        num = min(int(cfg.TRAIN.VIS_COUNT), B)
+        grids = [ops.image_grid_uint8(real_imgs[-1][:num], nrow=8, padding=2, layout="nchw")]
+        grids += [ops.image_grid_uint8(f[:num], nrow=8, padding=2, layout="nhwc") for f in fake_imgs]
+        rank0 = not self.distributed or torch.distributed.get_rank() == 0
+        if rank0 and getattr(self, 'image_dir', None):
+            from PIL import Image
+            names = ['real_samples.png'] + ['count_%09d_fake_samples%d.png' % (count, i) for i in range(len(fake_imgs))]
+            for name, grid in zip(names, grids):
+                Image.fromarray(grid.cpu().numpy()).save(os.path.join(self.image_dir, name))
+        return grids
+
     def train(self):
         start_count = self.build()
         dev = torch.device('cuda', self.gpus[0])
         nz = cfg.GAN.Z_DIM
         noise = torch.empty(self.batch_size, nz, device=dev)
+        self.draw_fixed_noise(dev)
         count = start_count
         start_epoch = start_count // max(self.num_batches, 1)
         errD_total = errG_total = kl_loss = None
@@ -901,6 +960,8 @@ class condGANTrainer(object):
                 count += 1
                 if count % cfg.TRAIN.SNAPSHOT_INTERVAL == 0:
                     self.save(count)
+                    if cfg.TRAIN.VIS_COUNT > 0:
+                        self.snapshot_images(count, real, emb)
                     self.score_inception(count)
             if errD_total is not None and self.gpus[0] == 0:
                 print('[%d/%d][%d] Loss_D: %.2f Loss_G: %.2f Loss_KL: %.2f Time: %.2fs'
@@ -912,7 +973,10 @@ class condGANTrainer(object):
         """The reference overwrites G's live weights with the EMA copy when it saves and never restores
         them (trainer.py:256, 590-601); the live weights are kept here.  With data-parallel ranks only
         rank 0 writes (the reference lets every rank write the same file names: a race on a shared filesystem); its
-        BatchNorm buffers are the ones kept, as DDP's broadcast_buffers would leave them."""
+        BatchNorm buffers are the ones kept, as DDP's broadcast_buffers would leave them.
+        A second deviation lives in snapshot_images: the reference's snapshot forward moves G's BatchNorm running
+        statistics (trainer.py:595-597), so its later checkpoints depend on how often it drew pictures; here the buffers
+        are restored after that forward and a checkpoint is the same with TRAIN.VIS_COUNT = 0 or not."""
         if self.distributed and torch.distributed.get_rank() != 0:
             return
         live = self.flatG.p.clone()
