@@ -593,9 +593,9 @@ int launch_thin(const s2i_conv_desc* d, const FwdPlan& pl, IgemmP p, void* ws, s
       hipLaunchKernelGGL(thin_out_kernel, dim3(blocks, 1, pl.nphases), dim3(256), 0, st, p, (const float*)table);
     } else {
       if (blocks > 4096) blocks = 4096;
+      // thin_kind admits 16 and 32 outputs only (64 ties with the matrix kernel, see there)
       if (d->N == 16) hipLaunchKernelGGL((thin_in_kernel<16>), dim3(blocks), dim3(256), 0, st, p, (const float*)table);
-      else if (d->N == 32) hipLaunchKernelGGL((thin_in_kernel<32>), dim3(blocks), dim3(256), 0, st, p, (const float*)table);
-      else hipLaunchKernelGGL((thin_in_kernel<64>), dim3(blocks), dim3(256), 0, st, p, (const float*)table);
+      else hipLaunchKernelGGL((thin_in_kernel<32>), dim3(blocks), dim3(256), 0, st, p, (const float*)table);
     }
     S2I_LAUNCH_CHECK("thin_conv");
     return 0;

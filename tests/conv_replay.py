@@ -219,7 +219,8 @@ def replay_conv(rec, gen, dev, what, ledger, extra=None):
     assert sees_channel, "%s: the bound cannot see one input channel's contribution" % what
 
 
-def replay_wgrad(rec, gen, dev, what, ledger):
+def replay_wgrad(rec, gen, dev, what, ledger, extra=None):
+    """extra(ctx), if given, runs before the assertions, as in replay_conv, and returns a list of failure messages."""
     from speech_to_image_translation_without_text_amd import ops
     op, layer = R.layer_op(rec)
     a = _operand(rec["a"], gen, dev)
@@ -286,7 +287,10 @@ def replay_wgrad(rec, gen, dev, what, ledger):
         untouched_ok = torch.equal(res[keep], prefill[keep])
     sees_channel = LH.fails(got, base + dw(channel=True), absref, rnd, gamma)
     sees_image = LH.fails(got, base + dw(image=True), absref, rnd, gamma)
+    more = [] if extra is None else extra(dict(rec=rec, layer=layer, a=ad, g=gd, kh=kh, got=got, base=base, ref=ref, absref=absref,
+                                               rnd=rnd, gamma=gamma, ratio=ratio, cls=cls))
     assert ok, "%s: element error %.3e x absref > gamma %.3e" % (what, ratio, gamma)
+    assert not more, "%s: %s" % (what, "; ".join(more))
     assert untouched_ok, "%s: elements outside input channels [%d, %d) changed" % (what, i_off, i_off + I)
     assert sees_channel, "%s: the bound cannot see one input channel's contribution" % what
     assert sees_image, "%s: the bound cannot see one image's contribution" % what
