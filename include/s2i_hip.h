@@ -429,6 +429,59 @@ int s2i_lstm_step(const float* xproj, int ldx, const float* whh_fwd, const float
 /* y[b][c] = mean over the T rows of x[b][t][c] (sent_emb = output.mean(-2), speech_encoder.py:93) */
 int s2i_time_mean(const float* x, int B, int T, int C, float* y, void* stream);
 
+/* ---- speech-encoder head, training (Audio_to_Image/train_audio_encoder.py:168-216, 308-361, jel.py:17-43) -------- */
+/*
+ * s2i_lstm_step that also stores what the backward needs.  Same recurrence, same `out` bit for bit.  In addition, for every
+ * valid (b, t, d): gates [B][T][D*4*Hd] (i, f, g, o AFTER their activations, in xproj's column layout), cst [B][T][D*Hd]
+ * (c_t, in out's layout) and hprev [D][B][T][Hd] (the h the step started from).  ldx = D*4*Hd and ldo = D*Hd (dense rows).
+ * The call with step = 0 also zeroes out and hprev at t >= lens[b], so neither needs clearing; gates and cst are not
+ * written there.  B <= 32, Hd % 8 == 0, Hd <= 512.
+ */
+int s2i_lstm_train_step(const float* xproj, int ldx, const float* whh_fwd, const float* whh_rev, const int* lens, int B, int T,
+                        int Hd, int D, int step, const float* h_in, float* h_out, float* c, float* out, int ldo,
+                        float* gates, float* cst, float* hprev, void* stream);
+/* s2i_lstm_cell with the same stores, one direction: xproj, out, gates (row stride ldx) and cst (row stride ldo) carry the
+ * direction's column offset, hprev is the direction's [B][T][Hd].  Any B and Hd. */
+int s2i_lstm_train_cell(const float* xproj, int ldx, const float* hproj, const int* lens, int B, int T, int Hd, int step,
+                        int reverse, float* h, float* c, float* out, int ldo, float* gates, float* cst, float* hprev,
+                        void* stream);
+/*
+ * One step of the LSTM's backward through time, every direction in one launch.  Called for step = max(lens)-1 .. 0, the
+ * first call with first = 1.  With dh = d_out[b][t] + d_sent[b] / T + dG_{step+1}[b] . W_hh (d_out [B][T][D*Hd] and d_sent
+ * [B][D*Hd] may each be null; d_sent is the gradient of the mean over all T steps) and dc = dc_rec + dh o (1 - tanh^2 c_t):
+ *   dG[b][t] = (dc g i(1-i), dc c_{prev} f(1-f), dc i (1-g^2), dh tanh(c_t) o(1-o)),   dc_rec = dc f
+ * dG [B][T][D*4*Hd] is written at every valid (b, t) and, by the first call, zeroed at t >= lens[b].  whht_* are the
+ * TRANSPOSED recurrent weights, [Hd][4*Hd] row-major.  dc [D][B][Hd] is scratch carried between the calls (initialised by
+ * the first).  A sequence with step >= lens[b] contributes nothing.  B <= 32, Hd % 8 == 0, Hd <= 512.
+ */
+int s2i_lstm_bwd_step(const float* d_out, const float* d_sent, const float* gates, const float* cst, const float* whht_fwd,
+                      const float* whht_rev, const int* lens, int B, int T, int Hd, int D, int step, int first, float* dc,
+                      float* dG, void* stream);
+/* The same step for one direction with the recurrent product done by the caller: dhrec [B][Hd] = dgt . W_hh of the
+ * previous call (ignored when first), dgt [B][4*Hd] receives this step's dG rows (zero for step >= lens[b]).  d_out, d_sent,
+ * cst (row stride ldo) and gates, dG (row stride ldg) carry the direction's column offset; dc [B][Hd].  Any B and Hd. */
+int s2i_lstm_bwd_cell(const float* d_out, const float* d_sent, int ldo, const float* gates, int ldg, const float* cst,
+                      const float* dhrec, const int* lens, int B, int T, int Hd, int step, int reverse, int first, float* dc,
+                      float* dG, float* dgt, void* stream);
+/* db [N] = the column sums of dG [M][N] (bias_ih and bias_hh gradients: both equal the sum of dG over every (b, t)) */
+int s2i_lstm_bias_grad(const float* dG, long long M, int N, float* db, void* stream);
+/*
+ * The encoder's loss and its gradient for the audio embedding; audio, image [B][C], label [B].
+ *   flags bit 0: joint-embedding loss, score = image . audio^T, score_abs[i][j] = score[i][j] - score[j][j],
+ *                (c_diff sum_{label_i != label_j} relu(score_abs + 1) + c_same sum_{label_i == label_j} relu(score_abs)) / B^2
+ *                and accu = 100 / B #{i: argmax_j score[i][j] == i} (lowest index wins a tie)
+ *         bit 1: mean |audio / |audio|_F - image / |image|_F| over B*C, times lambda_l1
+ *         bit 2: sum softmax(image / T) (log softmax(image / T) - log_softmax(audio)) / (B*C), times lambda_distill
+ * scal[5] = total, jel, l1, distill (unweighted parts), accu; grad [B][C] = d total / d audio.
+ */
+#define S2I_ENC_LOSS_JEL 1
+#define S2I_ENC_LOSS_L1 2
+#define S2I_ENC_LOSS_DISTILL 4
+size_t s2i_encoder_loss_workspace_bytes(int B);
+int s2i_encoder_loss(const float* audio, const float* image, const int* label, int B, int C, float c_diff, float c_same,
+                     int flags, float lambda_l1, float lambda_distill, float distill_T, void* ws, size_t ws_bytes,
+                     float* grad, float* scal, void* stream);
+
 /* ---- optimiser (trainer.py:236-252, 571-572) -------------------------------------------------- */
 /* torch.optim.Adam (no weight decay, no amsgrad) on a flat buffer, step = 1-based step count */
 int s2i_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,

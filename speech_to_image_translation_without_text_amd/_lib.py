@@ -20,6 +20,7 @@ DT_F32, DT_BF16 = 0, 1
 POOL_MAX3S2, POOL_AVG3S1, POOL_GLOBAL = 0, 1, 2
 POOL_THEN_LRN, LRN_THEN_POOL = 0, 1
 LOGMEL_BFT, LOGMEL_NHWC = 0, 1
+ENC_LOSS_JEL, ENC_LOSS_L1, ENC_LOSS_DISTILL = 1, 2, 4
 LOGMEL_TILE_FRAMES = 64
 ABI_VERSION = 4
 
@@ -135,6 +136,14 @@ _SIGNATURES = {
     "s2i_lstm_cell": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P]),
     "s2i_lstm_step": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P]),
     "s2i_time_mean": (c_int, [P, c_int, c_int, c_int, P, P]),
+    "s2i_lstm_train_step": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P]),
+    "s2i_lstm_train_cell": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, P]),
+    "s2i_lstm_bwd_step": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    "s2i_lstm_bwd_cell": (c_int, [P, P, c_int, P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P]),
+    "s2i_lstm_bias_grad": (c_int, [P, c_ll, c_int, P, P]),
+    "s2i_encoder_loss_workspace_bytes": (c_size_t, [c_int]),
+    "s2i_encoder_loss": (c_int, [P, P, P, c_int, c_int, c_float, c_float, c_int, c_float, c_float, c_float, P, c_size_t, P,
+                                 P, P]),
     "s2i_adam_step": (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_int, P, c_float, P]),
     "s2i_increment": (c_int, [P, P]),
     "s2i_ema_update": (c_int, [P, P, c_ll, c_float, P]),

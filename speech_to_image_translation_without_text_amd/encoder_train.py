@@ -1,0 +1,95 @@
+"""Fine-tuning the speech encoder's recurrent head on the MI355X kernels (the LSTM part of the reference's
+Audio_to_Image/train_audio_encoder.py:168-216, 308-361, 460-480).
+
+The conv stack of a CNNRNN runs frozen, exactly as inference runs it (eval-mode BatchNorm folded into the convolutions);
+its output [B, 1, L, 1024] is the seam.  Behind it, ops.lstm_sentence (LSTM forward that stores its gates, backward
+through time) and ops.encoder_loss (joint-embedding loss + L1 + distillation) give the gradients of `RNN.*`, which
+torch.optim.Adam (L2 weight decay, as the reference) and StepLR update: 6.3 M parameters, plumbing.  The model stays in
+.eval() mode throughout: CNNRNN.forward keeps refusing training mode, and with one LSTM layer nn.LSTM's dropout is a
+no-op, so train and eval agree.  The gradient for the conv stack's output is available from ops.lstm_sentence (x with
+requires_grad); nothing consumes it yet.
+"""
+import numpy as np
+import torch
+
+from . import _lib, ops, retrieval
+
+
+class HeadTrainer:
+    def __init__(self, model, lr=1e-3, weight_decay=1e-5, step_size=30, gamma=0.2, loss_diff=1, loss_same=1, jel=True,
+                 l1=False, lambda_l1=1, distill=False, distill_T=2, lambda_distill=1):
+        if model.rnn_layers != 1:
+            raise _lib.S2IError("HeadTrainer supports rnn_layers=1 (the reference's default)")
+        self.model = model.eval()
+        self.params = ops.lstm_params(model.RNN)
+        self.optimizer = torch.optim.Adam(model.RNN.parameters(), lr=lr, weight_decay=weight_decay)
+        self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=step_size, gamma=gamma)
+        self.loss_args = dict(loss_diff=loss_diff, loss_same=loss_same, jel=jel, l1=l1, lambda_l1=lambda_l1, distill=distill,
+                              distill_T=distill_T, lambda_distill=lambda_distill)
+
+    @property
+    def device(self):
+        return self.params[0].device
+
+    @torch.no_grad()
+    def features(self, mel_nhwc):
+        """The frozen conv stack on NHWC log-mel [B, 1, T, 40] (audio.log_mel(..., layout="nhwc")) -> [B, 1, T/64, 1024]."""
+        _lib.load()
+        _lib.require_device()
+        n_mels = self.model.Conv[1][0].kernel_size[0]
+        if mel_nhwc.dim() != 4 or mel_nhwc.shape[1] != 1 or mel_nhwc.shape[3] != n_mels:
+            raise _lib.S2IError("HeadTrainer.features: expected [B, 1, T, %d], got %s" % (n_mels, tuple(mel_nhwc.shape)))
+        return self.model._conv_features(mel_nhwc.contiguous())
+
+    @staticmethod
+    def _sorted(cap_lens, *tensors):
+        """Descending by length, as batch_process sorts a batch (sort_torch_data; ties keep their order)."""
+        lens = torch.as_tensor(cap_lens).cpu()
+        lens, order = torch.sort(lens, dim=0, descending=True, stable=True)
+        return lens.tolist(), [t.index_select(0, order.to(t.device)) for t in tensors]
+
+    def step_features(self, feat, cap_lens, image_feature, label):
+        """One optimiser step from conv features [B, 1, L, E]: what step() does behind features()."""
+        if self.model.training:
+            self.model.eval()
+        dev = self.device
+        lens, (feat, image_feature, label) = self._sorted(cap_lens, feat, image_feature.to(dev).float(), label.to(dev))
+        _, sent = ops.lstm_sentence(feat, lens, *self.params)
+        loss = ops.encoder_loss(sent, image_feature, label, **self.loss_args)
+        self.optimizer.zero_grad(set_to_none=True)
+        loss["loss"].backward()
+        self.optimizer.step()
+        return {k: v.detach() for k, v in loss.items()}
+
+    def step(self, mel_nhwc, cap_lens, image_feature, label):
+        """Sort by length, conv features, lstm_sentence, the loss, backward, Adam.  Returns the loss dict (device tensors:
+        loss, loss_jel, loss_l1, loss_distill, accu)."""
+        return self.step_features(self.features(mel_nhwc), cap_lens, image_feature, label)
+
+    def end_epoch(self):
+        self.scheduler.step()
+
+    @torch.no_grad()
+    def embed(self, mel_nhwc, cap_lens):
+        """Sentence embeddings [B, D*H] in the caller's order (the inference path)."""
+        lens, (x,) = self._sorted(cap_lens, mel_nhwc)
+        order = torch.sort(torch.as_tensor(cap_lens).cpu(), dim=0, descending=True, stable=True)[1].to(x.device)
+        sent = self.model.forward_nhwc(x, lens)[1]
+        out = torch.empty_like(sent)
+        out[order] = sent
+        return out
+
+    def evaluate(self, loader):
+        """(accuracy %, AP@50 %) of retrieval.eval_class over batches of (mel_nhwc, cap_lens, image_feature, label)."""
+        audio, image, labels = [], [], []
+        for mel, cap_lens, image_feature, label in loader:
+            audio.append(self.embed(mel.to(self.device), cap_lens).cpu().numpy())
+            image.append(torch.as_tensor(image_feature).float().cpu().numpy())
+            labels.append(torch.as_tensor(label).cpu().numpy())
+        return retrieval.eval_class(np.concatenate(audio), np.concatenate(image), np.concatenate(labels))
+
+    def save(self, path, epoch):
+        """The reference's checkpoint layout (Audio_to_Image/trainer.py save_checkpoint), read by
+        extract_audio_feature.load_encoder."""
+        state = {k: v.detach().cpu() for k, v in self.model.state_dict().items()}
+        torch.save({"meta": {"epoch": int(epoch)}, "state_dict": state}, path)

@@ -516,13 +516,17 @@ def conv_raw(kind, x, cvec, packed, N, *, wmode=0, flip=0, wR, ldw, bias=None, a
     return y, part, nparts
 
 
-def wgrad_raw(kind, a, cvec, g, grad_shape, *, swap=0, fold=0, out=None, accumulate=False, i_off=0, I_total=0, a_src=None):
+def wgrad_raw(kind, a, cvec, g, grad_shape, *, swap=0, fold=0, out=None, accumulate=False, i_off=0, I_total=0, a_src=None,
+              g_cols=None):
     """Weight gradient into an OIHW tensor of shape grad_shape.  a: gathered NHWC, g: plain NHWC.
-    With I_total > 0 only input channels [i_off, i_off + I) of a wider (O, I_total, KH, KW) tensor are written."""
+    With I_total > 0 only input channels [i_off, i_off + I) of a wider (O, I_total, KH, KW) tensor are written.
+    g_cols = (first, count) takes a column slice of g in place (row stride g.shape[-1]; first a multiple of 4)."""
     lib = _lib_ready()
     B, H, W, Ca = a.shape
     Cc = 0 if cvec is None else cvec.shape[1]
     N = g.shape[-1]
+    if g_cols is not None:
+        return _wgrad_cols(kind, a, g, grad_shape, g_cols)
     if len(grad_shape) == 2:
         O, I, KH, KW = grad_shape[0], grad_shape[1], 1, 1
     else:
@@ -559,6 +563,28 @@ def wgrad_raw(kind, a, cvec, g, grad_shape, *, swap=0, fold=0, out=None, accumul
     ws = _ws.get(wsb, a.device)
     check(lib.s2i_conv_wgrad(ctypes.byref(d), ptr(a), ptr(cvec), ptr(g), ptr(out), ptr(ws), ws.numel() * 4,
                              stream()), "s2i_conv_wgrad")
+    return out
+
+
+def _wgrad_cols(kind, a, g, grad_shape, g_cols):
+    """wgrad_raw on the columns [first, first + count) of g, read through the descriptor's row stride."""
+    lib = _lib_ready()
+    B, H, W, Ca = a.shape
+    first, N = g_cols
+    ldg = g.shape[-1]
+    if first % 4 or first < 0 or first + N > ldg or MATH_PLANES:
+        raise _lib.S2IError("wgrad: column slice (%d, %d) of %d columns (fp32 matrix mode only)" % (first, N, ldg))
+    O, I = grad_shape
+    d = WgradDesc(kind, B, H, W, Ca, 0, N, ldg, 0, 0, O, I, 1, 1, 0, 0, 0, 0, 0)
+    if EXEC_LOG is not None:
+        _log_exec("wgrad k%d a[%d,%d,%d,%d] g%d" % (kind, B, H, W, Ca, N), B * H * W, N, Ca, a.numel(), B * H * W * N, Ca * N)
+    out = torch.empty(grad_shape, dtype=torch.float32, device=a.device)
+    wsb = lib.s2i_wgrad_workspace_bytes(ctypes.byref(d))
+    if wsb == 0:
+        check(1, "s2i_wgrad_workspace_bytes")
+    ws = _ws.get(wsb, a.device)
+    check(lib.s2i_conv_wgrad(ctypes.byref(d), ptr(a), None, ptr(g) + 4 * first, ptr(out), ptr(ws), ws.numel() * 4, stream()),
+          "s2i_conv_wgrad")
     return out
 
 
@@ -1186,6 +1212,208 @@ class ToNCHW(torch.autograd.Function):
         dx = torch.empty((B, H, W, ctx.Cp), dtype=ctx.x_dtype, device=dout.device)
         check(lib.s2i_nchw_to_nhwc_dt(_dt(dx), ptr(dout), ptr(dx), B, C, H, W, ctx.Cp, stream()), "s2i_nchw_to_nhwc")
         return dx, None
+
+
+# ---- speech-encoder head: LSTM with backward through time, and the encoder loss ---------------------------------------
+# Tests set LSTM_SENTINEL to a float (NaN): every buffer the step kernels must fill completely, padded positions included
+# (out, sent, the previous-state copy, dG), is then allocated filled with it, so an element a kernel skipped shows.
+LSTM_SENTINEL = None
+# False sends every shape through the per-direction matrix-kernel + cell-kernel path (tests; the fused one-launch step
+# takes B <= 32, Hd % 8 == 0, Hd <= 512)
+LSTM_FUSED = True
+
+
+# A list here receives (h_n, c_n), each [D, B, Hd], of every LstmSentence forward: the final state is no output of the op
+# (the reference uses only `output`), but the packed-sequence rule "a finished sequence carries its state" shows nowhere else.
+LSTM_STATE_LOG = None
+
+
+def _new(shape, device, dtype=torch.float32):
+    if LSTM_SENTINEL is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    return torch.full(shape, LSTM_SENTINEL, dtype=dtype, device=device)
+
+
+def lstm_params(rnn):
+    """The parameters of a one-layer nn.LSTM in the order LstmSentence takes them."""
+    if rnn.num_layers != 1 or not rnn.batch_first or getattr(rnn, "proj_size", 0):
+        raise _lib.S2IError("lstm_sentence supports a one-layer batch_first nn.LSTM (the reference's default)")
+    sfx = ["", "_reverse"][:2 if rnn.bidirectional else 1]
+    return [getattr(rnn, n + "_l0" + s_) for s_ in sfx for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+
+
+class LstmSentence(torch.autograd.Function):
+    """(out [B, L, D*H], sent [B, D*H]) = packed-sequence LSTM over conv features x [B, 1, L, E] and its mean over all L
+    steps (Audio_to_Image/speech_encoder.py:84-93), differentiable in x and in every parameter.  params: weight_ih,
+    weight_hh, bias_ih, bias_hh of layer 0, then the same four of the reverse direction if bidirectional."""
+
+    @staticmethod
+    def forward(ctx, x, cap_lens, *params):
+        lib = _lib_ready()
+        if len(params) not in (4, 8):
+            raise _lib.S2IError("lstm_sentence: 4 parameters per direction, got %d" % len(params))
+        D = len(params) // 4
+        if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
+            raise _lib.S2IError("lstm_sentence: x must be fp32 NHWC [B, 1, L, E], got %s" % (tuple(x.shape),))
+        x = x.contiguous()
+        B, _, L, E = x.shape
+        Hd = params[1].shape[1]
+        if tuple(params[0].shape) != (4 * Hd, E) or Hd % 4 or E % 4:
+            raise _lib.S2IError("lstm_sentence: weight_ih %s does not fit E=%d, Hd=%d (both multiples of 4)"
+                                % (tuple(params[0].shape), E, Hd))
+        lens_host = [int(v) for v in (cap_lens.tolist() if torch.is_tensor(cap_lens) else cap_lens)]
+        if len(lens_host) != B or max(lens_host) > L or min(lens_host) < 1:
+            raise _lib.S2IError("lstm_sentence: cap_lens must hold B values in [1, %d]" % L)
+        dev = x.device
+        lens_dev = torch.tensor(lens_host, dtype=torch.int32, device=dev)
+        G4 = D * 4 * Hd
+        with torch.no_grad():
+            w_ih = pack_weight(torch.cat([params[4 * d] for d in range(D)], 0), PACK_PLAIN)          # [1][E][D*4H]
+            b = torch.cat([params[4 * d + 2] + params[4 * d + 3] for d in range(D)], 0).contiguous()
+            # [1][Hd][4*Hd]: the operand of the recurrent matrix product and, read as a matrix, W_hh transposed
+            w_hh = [pack_weight(params[4 * d + 1], PACK_PLAIN) for d in range(D)]
+            raw = [params[4 * d + 1].detach().contiguous() for d in range(D)]
+        xproj, _, _ = conv_raw(CONV_K1, x, None, w_ih, G4, wR=w_ih.shape[1], ldw=w_ih.shape[2], bias=b)  # [B, 1, L, D*4H]
+        out = _new((B, L, D * Hd), dev)
+        gates = torch.empty((B, L, G4), dtype=torch.float32, device=dev)
+        cst = torch.empty((B, L, D * Hd), dtype=torch.float32, device=dev)
+        hprev = _new((D, B, L, Hd), dev)
+        fused = LSTM_FUSED and B <= 32 and Hd % 8 == 0 and Hd <= 512
+        steps = max(lens_host)
+        if fused:
+            hbuf = torch.zeros((2, D, B, Hd), dtype=torch.float32, device=dev)
+            cs = torch.zeros((D, B, Hd), dtype=torch.float32, device=dev)
+            for step in range(steps):
+                check(lib.s2i_lstm_train_step(ptr(xproj), G4, ptr(raw[0]), ptr(raw[-1]), ptr(lens_dev), B, L, Hd, D, step,
+                                              ptr(hbuf[step & 1]), ptr(hbuf[(step + 1) & 1]), ptr(cs), ptr(out), D * Hd,
+                                              ptr(gates), ptr(cst), ptr(hprev), stream()), "s2i_lstm_train_step")
+            if LSTM_STATE_LOG is not None:
+                LSTM_STATE_LOG.append((hbuf[steps & 1].clone(), cs.clone()))
+        else:
+            hs_all = torch.zeros((D, B, 1, 1, Hd), dtype=torch.float32, device=dev)
+            cs_all = torch.zeros((D, B, Hd), dtype=torch.float32, device=dev)
+            for d in range(D):
+                hs, cs = hs_all[d], cs_all[d]
+                for step in range(steps):
+                    hproj, _, _ = conv_raw(CONV_K1, hs, None, w_hh[d], 4 * Hd, wR=w_hh[d].shape[1], ldw=w_hh[d].shape[2])
+                    check(lib.s2i_lstm_train_cell(ptr(xproj) + 4 * d * 4 * Hd, G4, ptr(hproj), ptr(lens_dev), B, L, Hd, step,
+                                                  d, ptr(hs), ptr(cs), ptr(out) + 4 * d * Hd, D * Hd,
+                                                  ptr(gates) + 4 * d * 4 * Hd, ptr(cst) + 4 * d * Hd, ptr(hprev[d]), stream()),
+                          "s2i_lstm_train_cell")
+            if LSTM_STATE_LOG is not None:
+                LSTM_STATE_LOG.append((hs_all.view(D, B, Hd).clone(), cs_all.clone()))
+        sent = _new((B, D * Hd), dev)
+        check(lib.s2i_time_mean(ptr(out), B, L, D * Hd, ptr(sent), stream()), "s2i_time_mean")
+        ctx.save_for_backward(x, gates, cst, hprev, lens_dev, w_ih, *w_hh)
+        ctx.dims = (B, L, E, Hd, D, steps, fused)
+        ctx.set_materialize_grads(False)
+        return out, sent
+
+    @staticmethod
+    def backward(ctx, d_out, d_sent):
+        lib = _lib_ready()
+        x, gates, cst, hprev, lens_dev, w_ih = ctx.saved_tensors[:6]
+        w_hh = ctx.saved_tensors[6:]
+        B, L, E, Hd, D, steps, fused = ctx.dims
+        dev = x.device
+        G4 = D * 4 * Hd
+        none = (None,) * (2 + 4 * D)
+        if d_out is None and d_sent is None:
+            return none
+        d_out = None if d_out is None else d_out.float().contiguous()
+        d_sent = None if d_sent is None else d_sent.float().contiguous()
+        dG = _new((B, L, G4), dev)
+        if fused:
+            dc = torch.empty((D, B, Hd), dtype=torch.float32, device=dev)
+            for step in range(steps - 1, -1, -1):
+                check(lib.s2i_lstm_bwd_step(ptr(d_out), ptr(d_sent), ptr(gates), ptr(cst), ptr(w_hh[0]), ptr(w_hh[-1]),
+                                            ptr(lens_dev), B, L, Hd, D, step, 1 if step == steps - 1 else 0, ptr(dc), ptr(dG),
+                                            stream()), "s2i_lstm_bwd_step")
+        else:
+            off = lambda t, n: None if t is None else ptr(t) + 4 * n
+            for d in range(D):
+                dc = torch.empty((B, Hd), dtype=torch.float32, device=dev)
+                dgt = torch.empty((B, 1, 1, 4 * Hd), dtype=torch.float32, device=dev)
+                dhrec = None
+                for step in range(steps - 1, -1, -1):
+                    check(lib.s2i_lstm_bwd_cell(off(d_out, d * Hd), off(d_sent, d * Hd), D * Hd, off(gates, d * 4 * Hd), G4,
+                                                off(cst, d * Hd), ptr(dhrec), ptr(lens_dev), B, L, Hd, step, d,
+                                                1 if step == steps - 1 else 0, ptr(dc), off(dG, d * 4 * Hd), ptr(dgt),
+                                                stream()), "s2i_lstm_bwd_cell")
+                    if step:    # dh_rec = dG_t . W_hh: the packed W_hh read untransposed
+                        dhrec, _, _ = conv_raw(CONV_K1, dgt, None, w_hh[d], Hd, wmode=1, wR=w_hh[d].shape[1],
+                                               ldw=w_hh[d].shape[2])
+        need = ctx.needs_input_grad
+        grads = [None] * (2 + 4 * D)
+        dG4 = dG.view(B, 1, L, G4)
+        if need[0]:     # the seam: the gradient for the conv stack's output
+            grads[0], _, _ = conv_raw(CONV_K1, dG4, None, w_ih, E, wmode=1, wR=w_ih.shape[1], ldw=w_ih.shape[2])
+        if any(need[2 + 4 * d] for d in range(D)):
+            dw_ih = wgrad_raw(CONV_K1, x, None, dG4, (G4, E))
+            for d in range(D):
+                if need[2 + 4 * d]:
+                    grads[2 + 4 * d] = dw_ih[d * 4 * Hd:(d + 1) * 4 * Hd]
+        for d in range(D):
+            if need[3 + 4 * d]:
+                grads[3 + 4 * d] = wgrad_raw(CONV_K1, hprev[d].view(B, 1, L, Hd), None, dG4, (4 * Hd, Hd),
+                                             g_cols=(d * 4 * Hd, 4 * Hd))
+        if any(need[4 + 4 * d] or need[5 + 4 * d] for d in range(D)):
+            db_all = torch.empty((G4,), dtype=torch.float32, device=dev)
+            check(lib.s2i_lstm_bias_grad(ptr(dG), B * L, G4, ptr(db_all), stream()), "s2i_lstm_bias_grad")
+            for d in range(D):
+                db = db_all[d * 4 * Hd:(d + 1) * 4 * Hd]
+                grads[4 + 4 * d] = db if need[4 + 4 * d] else None
+                grads[5 + 4 * d] = db.clone() if need[5 + 4 * d] else None   # db_hh = db_ih, its own tensor
+        return tuple(grads)
+
+
+def lstm_sentence(x, cap_lens, *params):
+    """LstmSentence on the parameters of a one-layer nn.LSTM (`lstm_params(rnn)`) or that module itself."""
+    if len(params) == 1 and isinstance(params[0], torch.nn.LSTM):
+        params = lstm_params(params[0])
+    return LstmSentence.apply(x, cap_lens, *params)
+
+
+class EncoderLoss(torch.autograd.Function):
+    """The five scalars of the reference's LossFunc (train_audio_encoder.py:308-361) as one device tensor
+    [total, jel, l1, distill, accu]; differentiable in `audio` through the total."""
+
+    @staticmethod
+    def forward(ctx, audio, image, label, c_diff, c_same, flags, lambda_l1, lambda_distill, distill_T):
+        lib = _lib_ready()
+        if audio.dim() != 2 or audio.shape != image.shape or label.shape[0] != audio.shape[0]:
+            raise _lib.S2IError("encoder_loss: audio %s, image %s, label %s" % (tuple(audio.shape), tuple(image.shape),
+                                                                                  tuple(label.shape)))
+        a = audio.detach().float().contiguous()
+        m = image.detach().float().contiguous()
+        lab = label.to(device=a.device, dtype=torch.int32).contiguous()
+        B, C = a.shape
+        grad = torch.empty_like(a)
+        scal = torch.empty((5,), dtype=torch.float32, device=a.device)
+        wsb = lib.s2i_encoder_loss_workspace_bytes(B)
+        ws = _ws.get(wsb, a.device)
+        check(lib.s2i_encoder_loss(ptr(a), ptr(m), ptr(lab), B, C, float(c_diff), float(c_same), int(flags), float(lambda_l1),
+                                   float(lambda_distill), float(distill_T), ptr(ws), ws.numel() * 4, ptr(grad), ptr(scal),
+                                   stream()), "s2i_encoder_loss")
+        ctx.save_for_backward(grad)
+        return scal
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g[0] if ctx.needs_input_grad[0] else None,) + (None,) * 8
+
+
+def encoder_loss(audio, image, label, loss_diff=1, loss_same=1, jel=True, l1=False, lambda_l1=1, distill=False, distill_T=2,
+                 lambda_distill=1):
+    """LossFunc(loss_diff, loss_same, jel, l1, lambda_l1, distill, distill_T, lambda_distill)(audio, image, label) of the
+    reference: {'loss', 'loss_jel', 'loss_l1', 'loss_distill', 'accu'}, all 0-d device tensors (nothing is copied to the
+    host); 'loss' carries the gradient for `audio`, the image side gets none."""
+    flags = (_lib.ENC_LOSS_JEL if jel else 0) | (_lib.ENC_LOSS_L1 if l1 else 0) | (_lib.ENC_LOSS_DISTILL if distill else 0)
+    scal = EncoderLoss.apply(audio, image, label, loss_diff, loss_same, flags, lambda_l1 if l1 else 0.0,
+                             lambda_distill if distill else 0.0, distill_T)
+    parts = scal.detach()
+    return {"loss": scal[0], "loss_jel": parts[1], "loss_l1": parts[2], "loss_distill": parts[3], "accu": parts[4]}
 
 
 # ---- optimiser -----------------------------------------------------------------------------------------------------------

@@ -12,7 +12,10 @@ reference, so seeded weights and checkpoints are interchangeable.  What runs is 
   * the LSTM's input projections for all steps and both directions are ONE GEMM; each recurrent step is a small
     GEMM + a fused gate kernel that applies the packed-sequence rule (per-sequence length, reverse direction
     starting at len-1, padded outputs zero) without packing anything.
-Training the encoder (JEL loss etc.) is out of scope: forward in training mode raises.
+forward / forward_nhwc / extract_feature* are inference only and raise in training mode.  What can be trained is the
+recurrent head: encoder_train.HeadTrainer runs the conv stack frozen (eval-mode BatchNorm, as above) and trains `RNN.*`
+through ops.lstm_sentence (backward through time) and ops.encoder_loss (JEL + L1 + distillation).  The conv stack's own
+backward and train-mode BatchNorm are not built; the gradient stops at the conv stack's output.
 """
 import torch
 import torch.nn as nn
@@ -145,9 +148,10 @@ class CNNRNN(nn.Module):
                                 % (self.Conv[1][0].kernel_size[0], tuple(x.shape)))
         return self._encode(x.contiguous(), cap_lens)
 
-    def _encode(self, h, cap_lens):
+    def _conv_features(self, h):
+        """The conv stack on NHWC log-mel [B, 1, T, 40] -> [B, 1, T/64, 1024]: the half of _encode in front of the LSTM,
+        which encoder_train.HeadTrainer runs frozen."""
         lib = _lib.load()
-        B = h.shape[0]
         prep = self._prepare()
         for layer in prep["layers"]:
             if layer[0] == "pool":
@@ -163,6 +167,13 @@ class CNNRNN(nn.Module):
                 _, packed, bias, n, geom = layer
                 h, _, _ = ops.conv_raw(CONV_1D, h, None, packed, n, wR=packed.shape[1], ldw=packed.shape[2], bias=bias,
                                        act=ACT_RELU, conv1d=geom)
+        return h
+
+    def _encode(self, h, cap_lens):
+        lib = _lib.load()
+        B = h.shape[0]
+        prep = self._prepare()
+        h = self._conv_features(h)
         Bh, _, L, E = h.shape                                           # [B, 1, T/64, 1024]
         lens_host = [int(v) for v in (cap_lens.tolist() if torch.is_tensor(cap_lens) else cap_lens)]
         if len(lens_host) != B or max(lens_host) > L or min(lens_host) < 1:
