@@ -37,7 +37,7 @@ extern "C" {
 
 #define S2I_CONV_1D      4  /* (1 x kw) conv along W with stride / padding from the descriptor: the temporal
                                convolutions of the speech encoder (Audio_to_Image/speech_encoder.py:26-37);
-                               forward only                                                      */
+                               forward only here: the gradients are s2i_conv1d_dgrad / s2i_conv1d_wgrad */
 
 /* activations */
 #define S2I_ACT_NONE     0
@@ -481,6 +481,56 @@ size_t s2i_encoder_loss_workspace_bytes(int B);
 int s2i_encoder_loss(const float* audio, const float* image, const int* label, int B, int C, float c_diff, float c_same,
                      int flags, float lambda_l1, float lambda_distill, float distill_T, void* ws, size_t ws_bytes,
                      float* grad, float* scal, void* stream);
+
+/* ---- speech-encoder conv stack, training (Audio_to_Image/speech_encoder.py:26-52 under autograd, as driven by
+ * train_audio_encoder.py:168-216).  fp32, single GPU, activations NHWC [B][1][W][C], W and Wo powers of two. ------------- */
+/*
+ * Input gradient of a (1 x kw) temporal convolution, Wo = (W + 2 pad - kw) / stride + 1:
+ *   dx[b][i][c] = sum_t sum_o dy[b][(i + pad - t) / stride][o] * w[o][c][t]   over the taps with (i + pad - t) % stride == 0
+ * dy [B][Wo][Cout], dx [B][W][Cin] (every element written); w_packed is the forward's P[t][wR][ldw] (S2I_PACK_PLAIN).
+ * stride 1 or 2, stride <= kw <= 31, 32 | Cout, 4 | Cin.  Implicit GEMM on v_mfma_f32_32x32x2_f32; with stride 2 each
+ * parity of i + pad is a launch phase with its own taps, so no structurally zero product is computed.
+ */
+int s2i_conv1d_dgrad(const float* dy, const float* w_packed, float* dx, int B, int W, int Cin, int Cout, int wR, int ldw,
+                     int kw, int stride, int pad, void* stream);
+/*
+ * Its weight gradient, written (not accumulated) in the parameter's OIHW (Cout, Cin, 1, kw) layout:
+ *   dw[o][c][0][t] = sum_{b, ox} dy[b][ox][o] * x[b][ox stride - pad + t][c]     (positions outside [0, W) contribute nothing)
+ * The B * Wo rows are split into slabs where the result has too few tiles to fill the chip, and never more than 512 rows
+ * per slab; a second launch adds the slabs in a fixed order (in double).  No atomics: bit-identical from run to run.
+ * The workspace holds the slabs; s2i_conv1d_wgrad_workspace_bytes returns 0 for a bad geometry.
+ */
+size_t s2i_conv1d_wgrad_workspace_bytes(int B, int W, int Cin, int Cout, int kw, int stride, int pad);
+int s2i_conv1d_wgrad(const float* x, const float* dy, float* dw_oihw, int B, int W, int Cin, int Cout, int kw, int stride,
+                     int pad, void* ws, size_t ws_bytes, void* stream);
+/* Train-mode BatchNorm + ReLU on the raw convolution output y [M][C] with the coefficient table of s2i_bn_finalize (one
+   group): out = max(scale * y + shift, 0). */
+int s2i_bn_relu_forward(const float* y, long long M, int C, const float* coef4, float* out, void* stream);
+/* Its backward in the reduce / finalize / apply scheme of s2i_bn_act_bwd_*: dz = dout where the stored forward output
+   `out` is > 0, else 0 (ReLU'(0) = 0).  Pass 1: part = [2][nparts][C] sums of dz and dz * xhat over nparts row chunks
+   (nparts <= M); s2i_bn_bwd_finalize turns them into dgamma, dbeta and red2; pass 2: dy = scale * (dz - mean_dz - xhat *
+   mean_dz_xhat). */
+int s2i_bn_relu_bwd_reduce(const float* y, const float* out, const float* dout, long long M, int C, const float* coef4,
+                           float* part, int nparts, void* stream);
+int s2i_bn_relu_bwd_apply(const float* y, const float* out, const float* dout, long long M, int C, const float* coef4,
+                          const float* red2, float* dy, void* stream);
+/* Backward of s2i_maxpool_w3s2 as a gather: dx[i] = sum of dy[j] over the (at most two) windows j that contain i and whose
+   maximum, recomputed from the stored pool input x, is at i; a tie goes to the lowest position, as torch's max_pool2d.
+   x, dx [B][H][W][C], dy [B][H][W/2][C]. */
+int s2i_maxpool_w3s2_backward(const float* x, const float* dy, int B, int H, int W, int C, float* dx, void* stream);
+/* The leading BatchNorm2d(1): one channel over all n = 4 q elements.  The per-channel kernels run on the [q][4] view
+   (s2i_colstats, s2i_bn_act_forward / _bwd_apply with C = 4, S2I_ACT_NONE); the two finalize calls fold the four columns
+   of the partial sums ([2][nparts][4]) into the one channel.  s2i_bn1_bwd_reduce writes the backward sums of dout and
+   dout * xhat in that layout (column 0; a block's terms are added in double: d weight is a sum over every input element).  s2i_bn1_finalize writes the C = 4 coefficient table
+   [mean x4 | invstd x4 | scale x4 | shift x4] and updates the running statistics as s2i_bn_finalize does (count = n);
+   s2i_bn1_bwd_finalize writes dgamma[0], dbeta[0] (assigned; either may be NULL) and red2 = [mean_dz x4 | mean_dz_xhat x4]. */
+int s2i_bn1_finalize(const float* part, int nparts, long long count, const float* gamma, const float* beta,
+                     float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps,
+                     float* coef4x4, void* stream);
+int s2i_bn1_bwd_reduce(const float* x, const float* dout, long long n, const float* coef4x4, float* part, int nparts,
+                       void* stream);
+int s2i_bn1_bwd_finalize(const float* part, int nparts, long long count, float* dgamma, float* dbeta, float* red2x4,
+                         void* stream);
 
 /* ---- optimiser (trainer.py:236-252, 571-572) -------------------------------------------------- */
 /* torch.optim.Adam (no weight decay, no amsgrad) on a flat buffer, step = 1-based step count */

@@ -144,6 +144,16 @@ _SIGNATURES = {
     "s2i_encoder_loss_workspace_bytes": (c_size_t, [c_int]),
     "s2i_encoder_loss": (c_int, [P, P, P, c_int, c_int, c_float, c_float, c_int, c_float, c_float, c_float, P, c_size_t, P,
                                  P, P]),
+    "s2i_conv1d_dgrad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "s2i_conv1d_wgrad_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "s2i_conv1d_wgrad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    "s2i_bn_relu_forward": (c_int, [P, c_ll, c_int, P, P, P]),
+    "s2i_bn_relu_bwd_reduce": (c_int, [P, P, P, c_ll, c_int, P, P, c_int, P]),
+    "s2i_bn_relu_bwd_apply": (c_int, [P, P, P, c_ll, c_int, P, P, P, P]),
+    "s2i_maxpool_w3s2_backward": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
+    "s2i_bn1_finalize": (c_int, [P, c_int, c_ll, P, P, P, P, P, c_float, c_float, P, P]),
+    "s2i_bn1_bwd_reduce": (c_int, [P, P, c_ll, P, P, c_int, P]),
+    "s2i_bn1_bwd_finalize": (c_int, [P, c_int, c_ll, P, P, P, P]),
     "s2i_adam_step": (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_int, P, c_float, P]),
     "s2i_increment": (c_int, [P, P]),
     "s2i_ema_update": (c_int, [P, P, c_ll, c_float, P]),

@@ -1,13 +1,18 @@
-"""Fine-tuning the speech encoder's recurrent head on the MI355X kernels (the LSTM part of the reference's
-Audio_to_Image/train_audio_encoder.py:168-216, 308-361, 460-480).
+"""Training the speech encoder on the MI355X kernels (the reference's Audio_to_Image/train_audio_encoder.py:168-216,
+308-361, 460-480): HeadTrainer fine-tunes the recurrent head with the conv stack frozen, EncoderTrainer trains all of it.
 
-The conv stack of a CNNRNN runs frozen, exactly as inference runs it (eval-mode BatchNorm folded into the convolutions);
-its output [B, 1, L, 1024] is the seam.  Behind it, ops.lstm_sentence (LSTM forward that stores its gates, backward
+HeadTrainer: the conv stack of a CNNRNN runs frozen, exactly as inference runs it (eval-mode BatchNorm folded into the
+convolutions); its output [B, 1, L, 1024] is the seam.  Behind it, ops.lstm_sentence (LSTM forward that stores its gates, backward
 through time) and ops.encoder_loss (joint-embedding loss + L1 + distillation) give the gradients of `RNN.*`, which
 torch.optim.Adam (L2 weight decay, as the reference) and StepLR update: 6.3 M parameters, plumbing.  The model stays in
 .eval() mode throughout: CNNRNN.forward keeps refusing training mode, and with one LSTM layer nn.LSTM's dropout is a
-no-op, so train and eval agree.  The gradient for the conv stack's output is available from ops.lstm_sentence (x with
-requires_grad); nothing consumes it yet.
+no-op, so train and eval agree.
+
+EncoderTrainer: the same step with ops.conv_stack_train in front (train-mode BatchNorm, temporal-conv and pool gradients),
+which consumes the gradient ops.lstm_sentence returns for the seam; Adam then updates Conv.* and RNN.*.  Train-mode
+BatchNorm is a property of this entry point: the module flag stays .eval() and CNNRNN.forward keeps refusing training
+mode.  Single GPU, fp32, one LSTM layer, frame counts that are powers of two; data-parallel training, bf16, more LSTM
+layers and dropout are not built.
 """
 import numpy as np
 import torch
@@ -93,3 +98,40 @@ class HeadTrainer:
         extract_audio_feature.load_encoder."""
         state = {k: v.detach().cpu() for k, v in self.model.state_dict().items()}
         torch.save({"meta": {"epoch": int(epoch)}, "state_dict": state}, path)
+
+
+class EncoderTrainer(HeadTrainer):
+    """HeadTrainer's interface, training every parameter: `features` is ops.conv_stack_train with gradients enabled, the
+    optimiser is the reference's Adam(model.parameters(), lr, weight_decay=1e-5) with StepLR.  embed / evaluate run the
+    inference path, which folds the running statistics training has produced."""
+
+    def __init__(self, model, lr=1e-3, weight_decay=1e-5, step_size=30, gamma=0.2, **loss_args):
+        super().__init__(model, lr=lr, weight_decay=weight_decay, step_size=step_size, gamma=gamma, **loss_args)
+        self.optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+        self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=step_size, gamma=gamma)
+
+    def _stale(self):
+        # the kernels update running_mean / running_var / num_batches_tracked through raw pointers, which leaves the
+        # version counters CNNRNN._prepare keys its folded weights by unchanged: drop the cache
+        self.model._prepared = None
+
+    def features(self, mel_nhwc):
+        """The conv stack in training mode on NHWC log-mel [B, 1, T, 40] -> [B, 1, T/64, 1024], with a graph behind it;
+        updates the running statistics."""
+        _lib.load()
+        _lib.require_device()
+        n_mels = self.model.Conv[1][0].kernel_size[0]
+        if mel_nhwc.dim() != 4 or mel_nhwc.shape[1] != 1 or mel_nhwc.shape[3] != n_mels:
+            raise _lib.S2IError("EncoderTrainer.features: expected [B, 1, T, %d], got %s" % (n_mels, tuple(mel_nhwc.shape)))
+        T = mel_nhwc.shape[2]
+        if T < 64 or T & (T - 1):
+            raise _lib.S2IError("EncoderTrainer.features: the frame count must be a power of two >= 64, got %d" % T)
+        self._stale()
+        with torch.enable_grad():
+            return ops.conv_stack_train(self.model.Conv, mel_nhwc.detach().float().contiguous())
+
+    def step_features(self, feat, cap_lens, image_feature, label):
+        try:
+            return super().step_features(feat, cap_lens, image_feature, label)
+        finally:
+            self._stale()

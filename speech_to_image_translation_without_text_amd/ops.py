@@ -11,6 +11,8 @@ Each Function stands in for a group of stock torch ops of the reference
   Glu2d, Reparam, KLLoss        CA_NET encode / reparametrize, KL_loss
   LogitHead, BCELoss, ClassAwareLoss   logits / uncond_logits + nn.BCELoss, class_aware_loss
   ToNHWC / ToNCHW               layout changes at the module boundary
+  LstmSentence, EncoderLoss     the speech encoder's LSTM head and loss (Audio_to_Image/train_audio_encoder.py)
+  TemporalConvBnRelu, InputBatchNorm, MaxPoolW3S2, conv_stack_train   its conv stack in training mode
 
 Activations between these ops are NHWC; parameters stay in the reference's OIHW layout and are
 re-packed to the kernels' layout when their version counter changes.  There is no CPU fallback.
@@ -1414,6 +1416,240 @@ def encoder_loss(audio, image, label, loss_diff=1, loss_same=1, jel=True, l1=Fal
                              lambda_distill if distill else 0.0, distill_T)
     parts = scal.detach()
     return {"loss": scal[0], "loss_jel": parts[1], "loss_l1": parts[2], "loss_distill": parts[3], "accu": parts[4]}
+
+
+# ---- speech-encoder conv stack under autograd: train-mode BatchNorm, temporal-conv gradients, pool backward ---------------
+# The reference trains all of CNNRNN (Audio_to_Image/train_audio_encoder.py:168-216); these operators are the conv stack of
+# speech_encoder.py:26-52 with a graph behind it.  fp32, one GPU, frame counts that are powers of two.  Tests set
+# CONV_STACK_SENTINEL to a float (NaN): every buffer a kernel must fill completely is then allocated filled with it.
+CONV_STACK_SENTINEL = None
+# A list here receives the stored forward tensors of every operator call, in call order: ("bn0", x, out), ("block", y raw,
+# out activated) and ("pool", x, out).  conv_stack_train clears it first, so it holds the last call: the ReLU decisions are
+# out > 0, the pool maxima follow from x.
+CONV_STACK_LOG = None
+
+
+def _cnew(shape, device):
+    if CONV_STACK_SENTINEL is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    return torch.full(shape, CONV_STACK_SENTINEL, dtype=torch.float32, device=device)
+
+
+def _nhwc1(x, what):
+    if x.dim() != 4 or x.shape[1] != 1 or x.dtype != torch.float32:
+        raise _lib.S2IError("%s: x must be fp32 NHWC [B, 1, W, C], got %s %s" % (what, tuple(x.shape), x.dtype))
+    return x.contiguous()
+
+
+class TemporalConvBnRelu(torch.autograd.Function):
+    """Conv2d(bias=False) + BatchNorm2d (training statistics) + ReLU of conv_layer_2d on NHWC [B, 1, W, Cin].  geom = (k,
+    stride, pad) of a (1 x k) temporal convolution, or None for the first (n_mels x 1) layer, a 1x1 conv over the mel axis.
+    Stored: x, the raw conv output and the activated output (the next layer's input)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, bn_buffers, geom):
+        lib = _lib_ready()
+        if MATH_PLANES:
+            raise _lib.S2IError("temporal_conv_bn_relu: native fp32 matrix mode only")
+        x = _nhwc1(x, "temporal_conv_bn_relu")
+        B, _, W, Cin = x.shape
+        Cout = weight.shape[0]
+        if geom is None:
+            if tuple(weight.shape[1:]) != (1, Cin, 1):
+                raise _lib.S2IError("temporal_conv_bn_relu: first-layer weight %s does not fit %d mel bands"
+                                    % (tuple(weight.shape), Cin))
+            packed = pack_weight(weight.detach().reshape(Cout, Cin), PACK_PLAIN)
+            y, part, nparts = conv_raw(CONV_K1, x, None, packed, Cout, wR=packed.shape[1], ldw=packed.shape[2], stats=True)
+        else:
+            k, st, pd = (int(v) for v in geom)
+            if tuple(weight.shape[1:]) != (Cin, 1, k):
+                raise _lib.S2IError("temporal_conv_bn_relu: weight %s does not fit Cin=%d, k=%d" % (tuple(weight.shape), Cin, k))
+            geom = (k, st, pd)
+            packed = pack_weight(weight, PACK_PLAIN)
+            y, part, nparts = conv_raw(_lib.CONV_1D, x, None, packed, Cout, wR=packed.shape[1], ldw=packed.shape[2],
+                                       stats=True, conv1d=geom)
+        M = y.numel() // Cout
+        coef = _cnew((1, 4, Cout), x.device)
+        rm, rv, nbt = bn_buffers
+        check(lib.s2i_bn_finalize(ptr(part), nparts, 1, Cout, M, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), ptr(nbt), BN_MOMENTUM,
+                                  BN_EPS, ptr(coef), stream()), "s2i_bn_finalize")
+        out = _cnew(tuple(y.shape), x.device)
+        check(lib.s2i_bn_relu_forward(ptr(y), M, Cout, ptr(coef), ptr(out), stream()), "s2i_bn_relu_forward")
+        if CONV_STACK_LOG is not None:
+            CONV_STACK_LOG.append(("block", y, out))
+        ctx.save_for_backward(x, packed, y, out, coef)
+        ctx.geom, ctx.wshape = geom, tuple(weight.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib_ready()
+        x, packed, y, out, coef = ctx.saved_tensors
+        geom = ctx.geom
+        B, _, W, Cin = x.shape
+        Cout = y.shape[-1]
+        M = y.numel() // Cout
+        dev = x.device
+        dout = dout.float().contiguous()
+        nparts = _num_parts(M)
+        part = _cnew((2, nparts, Cout), dev)
+        check(lib.s2i_bn_relu_bwd_reduce(ptr(y), ptr(out), ptr(dout), M, Cout, ptr(coef), ptr(part), nparts, stream()),
+              "s2i_bn_relu_bwd_reduce")
+        dgamma, dbeta, red2 = _cnew((Cout,), dev), _cnew((Cout,), dev), _cnew((2, Cout), dev)
+        check(lib.s2i_bn_bwd_finalize(ptr(part), nparts, 1, Cout, M, ptr(dgamma), ptr(dbeta), 0, ptr(red2), stream()),
+              "s2i_bn_bwd_finalize")
+        dy = _cnew(tuple(y.shape), dev)
+        check(lib.s2i_bn_relu_bwd_apply(ptr(y), ptr(out), ptr(dout), M, Cout, ptr(coef), ptr(red2), ptr(dy), stream()),
+              "s2i_bn_relu_bwd_apply")
+        need = ctx.needs_input_grad
+        dx = dw = None
+        if geom is None:
+            if need[0]:
+                dx, _, _ = conv_raw(CONV_K1, dy, None, packed, Cin, wmode=1, wR=packed.shape[1], ldw=packed.shape[2])
+            if need[1]:
+                dw = wgrad_raw(CONV_K1, x, None, dy, (Cout, Cin)).view(ctx.wshape)
+        else:
+            k, st, pd = geom
+            if need[0]:
+                dx = _cnew(tuple(x.shape), dev)
+                check(lib.s2i_conv1d_dgrad(ptr(dy), ptr(packed), ptr(dx), B, W, Cin, Cout, packed.shape[1], packed.shape[2], k,
+                                           st, pd, stream()), "s2i_conv1d_dgrad")
+            if need[1]:
+                dw = _cnew(ctx.wshape, dev)
+                wsb = lib.s2i_conv1d_wgrad_workspace_bytes(B, W, Cin, Cout, k, st, pd)
+                if wsb == 0:
+                    check(1, "s2i_conv1d_wgrad_workspace_bytes")
+                ws = _ws.get(wsb, dev)
+                check(lib.s2i_conv1d_wgrad(ptr(x), ptr(dy), ptr(dw), B, W, Cin, Cout, k, st, pd, ptr(ws), ws.numel() * 4,
+                                           stream()), "s2i_conv1d_wgrad")
+        return dx, dw, dgamma if need[2] else None, dbeta if need[3] else None, None, None
+
+
+def temporal_conv_bn_relu(x, weight, gamma, beta, bn_buffers, geom):
+    """x [B, 1, W, Cin] -> relu(batchnorm_train(conv(x))) [B, 1, Wo, Cout]; bn_buffers = (running_mean, running_var,
+    num_batches_tracked), updated as nn.BatchNorm2d in training mode does (momentum 0.1, unbiased variance)."""
+    return TemporalConvBnRelu.apply(x, weight, gamma, beta, tuple(bn_buffers), geom)
+
+
+class InputBatchNorm(torch.autograd.Function):
+    """The leading nn.BatchNorm2d(1) in training mode: ONE channel over all elements of x [B, 1, T, n_mels].  The
+    per-channel kernels run on the [n / 4][4] view of the tensor; s2i_bn1_finalize / s2i_bn1_bwd_finalize fold the four
+    columns into the channel."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, bn_buffers):
+        lib = _lib_ready()
+        x = _nhwc1(x, "input_batchnorm")
+        n = x.numel()
+        if n % 4 or gamma.numel() != 1 or beta.numel() != 1:
+            raise _lib.S2IError("input_batchnorm: one channel over a multiple of 4 elements (n=%d)" % n)
+        dev = x.device
+        R = n // 4
+        nparts = _num_parts(R)
+        part = _cnew((2, nparts, 4), dev)
+        check(lib.s2i_colstats(ptr(x), R, 4, 4, ptr(part), nparts, stream()), "s2i_colstats")
+        coef = _cnew((1, 4, 4), dev)
+        rm, rv, nbt = bn_buffers
+        check(lib.s2i_bn1_finalize(ptr(part), nparts, n, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), ptr(nbt), BN_MOMENTUM, BN_EPS,
+                                   ptr(coef), stream()), "s2i_bn1_finalize")
+        out = _cnew(tuple(x.shape), dev)
+        check(lib.s2i_bn_act_forward(ptr(x), R, 1, 4, ptr(coef), ACT_NONE, None, ptr(out), stream()), "s2i_bn_act_forward")
+        if CONV_STACK_LOG is not None:
+            CONV_STACK_LOG.append(("bn0", x, out))
+        ctx.save_for_backward(x, coef)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib_ready()
+        x, coef = ctx.saved_tensors
+        dev = x.device
+        n = x.numel()
+        R = n // 4
+        dout = dout.float().contiguous()
+        nparts = _num_parts(R)
+        part = _cnew((2, nparts, 4), dev)
+        check(lib.s2i_bn1_bwd_reduce(ptr(x), ptr(dout), n, ptr(coef), ptr(part), nparts, stream()), "s2i_bn1_bwd_reduce")
+        dgamma, dbeta, red2 = _cnew((1,), dev), _cnew((1,), dev), _cnew((2, 4), dev)
+        check(lib.s2i_bn1_bwd_finalize(ptr(part), nparts, n, ptr(dgamma), ptr(dbeta), ptr(red2), stream()),
+              "s2i_bn1_bwd_finalize")
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = _cnew(tuple(x.shape), dev)
+            check(lib.s2i_bn_act_bwd_apply(ptr(x), ptr(dout), 4, R, 1, 4, ptr(coef), ptr(red2), ACT_NONE, ptr(dx), stream()),
+                  "s2i_bn_act_bwd_apply")
+        return dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None, None
+
+
+def input_batchnorm(x, gamma, beta, bn_buffers):
+    return InputBatchNorm.apply(x, gamma, beta, tuple(bn_buffers))
+
+
+class MaxPoolW3S2(torch.autograd.Function):
+    """nn.MaxPool2d((1, 3), (1, 2), (0, 1)) on NHWC [B, H, W, C]; the backward recomputes each window's maximum from the
+    stored input (lowest position wins a tie, as torch)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib_ready()
+        if x.dim() != 4 or x.dtype != torch.float32:
+            raise _lib.S2IError("maxpool_w3s2: x must be fp32 NHWC, got %s" % (tuple(x.shape),))
+        x = x.contiguous()
+        B, H, W, C = x.shape
+        out = _cnew((B, H, W // 2, C), x.device)
+        check(lib.s2i_maxpool_w3s2(ptr(x), B, H, W, C, ptr(out), stream()), "s2i_maxpool_w3s2")
+        if CONV_STACK_LOG is not None:
+            CONV_STACK_LOG.append(("pool", x, out))
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib_ready()
+        (x,) = ctx.saved_tensors
+        B, H, W, C = x.shape
+        dout = dout.float().contiguous()
+        dx = _cnew(tuple(x.shape), x.device)
+        check(lib.s2i_maxpool_w3s2_backward(ptr(x), ptr(dout), B, H, W, C, ptr(dx), stream()), "s2i_maxpool_w3s2_backward")
+        return dx
+
+
+def maxpool_w3s2(x):
+    return MaxPoolW3S2.apply(x)
+
+
+def _bn_buffers(bn):
+    return bn.running_mean, bn.running_var, bn.num_batches_tracked
+
+
+def conv_stack_train(conv_sequential, mel_nhwc):
+    """CNNRNN.Conv (BatchNorm2d(1), conv_layer_2d blocks, MaxPool2d) in training mode on NHWC log-mel [B, 1, T, n_mels] ->
+    [B, 1, T / 64, 1024], differentiable in every Conv.* parameter; running statistics and num_batches_tracked are updated in
+    place through raw pointers (their torch version counters do not move)."""
+    if CONV_STACK_LOG is not None:
+        del CONV_STACK_LOG[:]
+    mods = list(conv_sequential)
+    if not isinstance(mods[0], torch.nn.BatchNorm2d) or mods[0].num_features != 1:
+        raise _lib.S2IError("conv_stack_train: expected CNNRNN.Conv (leading BatchNorm2d(1))")
+    h = input_batchnorm(mel_nhwc, mods[0].weight, mods[0].bias, _bn_buffers(mods[0]))
+    first = True
+    for m in mods[1:]:
+        if isinstance(m, torch.nn.MaxPool2d):
+            if (m.kernel_size, m.stride, m.padding) != ((1, 3), (1, 2), (0, 1)):
+                raise _lib.S2IError("conv_stack_train: unsupported pool %s" % (m,))
+            h = maxpool_w3s2(h)
+        elif isinstance(m, torch.nn.Sequential):
+            conv, bn = m[0], m[1]
+            if conv.bias is not None or bn.momentum != BN_MOMENTUM or bn.eps != BN_EPS:
+                raise _lib.S2IError("conv_stack_train: unsupported block %s" % (m,))
+            geom = None if first else (conv.kernel_size[1], conv.stride[1], conv.padding[1])
+            if not first and conv.kernel_size[0] != 1:
+                raise _lib.S2IError("conv_stack_train: temporal convolutions are (1 x k), got %s" % (conv.kernel_size,))
+            h = temporal_conv_bn_relu(h, conv.weight, bn.weight, bn.bias, _bn_buffers(bn), geom)
+            first = False
+        else:
+            raise _lib.S2IError("conv_stack_train: unsupported module %s" % (m,))
+    return h
 
 
 # ---- optimiser -----------------------------------------------------------------------------------------------------------

@@ -12,10 +12,11 @@ reference, so seeded weights and checkpoints are interchangeable.  What runs is 
   * the LSTM's input projections for all steps and both directions are ONE GEMM; each recurrent step is a small
     GEMM + a fused gate kernel that applies the packed-sequence rule (per-sequence length, reverse direction
     starting at len-1, padded outputs zero) without packing anything.
-forward / forward_nhwc / extract_feature* are inference only and raise in training mode.  What can be trained is the
-recurrent head: encoder_train.HeadTrainer runs the conv stack frozen (eval-mode BatchNorm, as above) and trains `RNN.*`
-through ops.lstm_sentence (backward through time) and ops.encoder_loss (JEL + L1 + distillation).  The conv stack's own
-backward and train-mode BatchNorm are not built; the gradient stops at the conv stack's output.
+forward / forward_nhwc / extract_feature* are inference only and raise in training mode.  Training has its own entry
+points (encoder_train): HeadTrainer runs the conv stack frozen (eval-mode BatchNorm, as above) and trains `RNN.*` through
+ops.lstm_sentence (backward through time) and ops.encoder_loss (JEL + L1 + distillation); EncoderTrainer also trains
+`Conv.*` through ops.conv_stack_train (train-mode BatchNorm, temporal-conv and pool gradients).  The inference path folds
+whatever running statistics training has left in the module.
 """
 import torch
 import torch.nn as nn

@@ -67,12 +67,15 @@ class SplitData:
             yield mel, (frames // MIN_FRAMES).tolist(), image, torch.tensor([c for _, _, c in drawn], dtype=torch.int64)
 
 
-def get_parser():
-    p = argparse.ArgumentParser(description="fine-tune the speech encoder's LSTM head (conv stack frozen); single GPU")
-    p.add_argument("--model", type=str, required=True, help="CNNRNN checkpoint to start from")
+def get_parser(description="fine-tune the speech encoder's LSTM head (conv stack frozen); single GPU", model_required=True,
+               output_dir="./output/Audio_to_Image/encoder_head", seed=None):
+    """The flags of this CLI; train_encoder builds its own from the same list (--model optional, a default seed)."""
+    p = argparse.ArgumentParser(description=description)
+    p.add_argument("--model", type=str, required=model_required, default="" if not model_required else None,
+                   help="CNNRNN checkpoint to start from")
     p.add_argument("--dataset", choices=["birds", "flowers"], default="birds")
     p.add_argument("--data_dir", type=str, default=None, help="directory with train.json / test.json (default ./data/<dataset>)")
-    p.add_argument("--output_dir", type=str, default="./output/Audio_to_Image/encoder_head")
+    p.add_argument("--output_dir", type=str, default=output_dir)
     p.add_argument("--epoch", type=int, default=100)
     p.add_argument("--batch_size", type=int, default=64)
     p.add_argument("--bidirectional", action="store_true", default=False)
@@ -88,23 +91,25 @@ def get_parser():
     p.add_argument("--lambda_l1", type=float, default=1.0)
     p.add_argument("--lambda_distill", type=float, default=1.0)
     p.add_argument("--distill_T", type=float, default=2.0)
-    p.add_argument("--seed", type=int, default=None, help="seed of `random` (utterance / view draws, batch order)")
+    p.add_argument("--seed", type=int, default=seed, help="seed of `random` (utterance / view draws, batch order)")
     return p
 
 
-def main(argv=None):
-    args = get_parser().parse_args(argv)
+def check_args(args):
     if args.batch_size < 1 or args.epoch < 1 or args.eval_every < 1:
         raise SystemExit("--batch_size, --epoch and --eval_every must be >= 1")
-    if args.seed is not None:
-        random.seed(args.seed)
+
+
+def trainer_kwargs(args):
+    return dict(lr=args.learning_rate, weight_decay=1e-5, step_size=args.lr_scheduler_step_size,
+                gamma=args.lr_scheduler_gamma, loss_diff=args.loss_diff, loss_same=args.loss_same, jel=args.jel_flag,
+                l1=args.l1_flag, lambda_l1=args.lambda_l1, distill=args.distill_flag, distill_T=args.distill_T,
+                lambda_distill=args.lambda_distill)
+
+
+def run(trainer, args, dev):
+    """The epoch loop, evaluation and checkpoints shared with train_encoder -> best test accuracy."""
     data_dir = args.data_dir or os.path.join(".", "data", args.dataset)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    model = load_encoder(args.model, args.bidirectional, 1, dev)
-    trainer = HeadTrainer(model, lr=args.learning_rate, weight_decay=1e-5, step_size=args.lr_scheduler_step_size,
-                          gamma=args.lr_scheduler_gamma, loss_diff=args.loss_diff, loss_same=args.loss_same,
-                          jel=args.jel_flag, l1=args.l1_flag, lambda_l1=args.lambda_l1, distill=args.distill_flag,
-                          distill_T=args.distill_T, lambda_distill=args.lambda_distill)
     train, test = SplitData(data_dir, "train", args.dataset), SplitData(data_dir, "test", args.dataset)
     os.makedirs(args.output_dir, exist_ok=True)
     best = -1.0
@@ -128,6 +133,16 @@ def main(argv=None):
                 shutil.copyfile(path, os.path.join(args.output_dir, "best.pth"))
             print(json.dumps({"epoch": epoch, "test_accu": accu, "test_ap50": ap50, "best_accu": best}))
     return best
+
+
+def main(argv=None):
+    args = get_parser().parse_args(argv)
+    check_args(args)
+    if args.seed is not None:
+        random.seed(args.seed)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    model = load_encoder(args.model, args.bidirectional, 1, dev)
+    return run(HeadTrainer(model, **trainer_kwargs(args)), args, dev)
 
 
 if __name__ == "__main__":
