@@ -662,6 +662,15 @@ int s2i_logmel_power(const float* x, const long long* offsets, const int* lens, 
    S2I_LOGMEL_NHWC layout */
 int s2i_logmel_finish(const float* melpow, const unsigned* maxbits, const int* lens, int B, int T, int layout,
                       float* out, void* stream);
+/* A batch out of kept log-mel rows: the padding / truncation to T of load_one_audio_file (utils.py:329-340) applied to
+   rows s2i_logmel_finish made earlier.  pool [rows][40] fp32 holds the kept rows of every utterance of a split back to
+   back; out is S2I_LOGMEL_NHWC [B][1][T][40].  out[b][0][t][:] = pool[row_offsets[b] + t][:] for t < frames[b] and 0.0f
+   (0 dB, the fill of s2i_logmel_finish) for frames[b] <= t < T; frames[b] is in [0, T] (values outside are clamped),
+   and a negative row offset (an utterance that is not stored) gives an all-fill utterance.  pool and out are 16-byte
+   aligned; the rows move as 16-byte pieces addressed in 64 bits, so a pool may hold more than 2^31 floats.  One
+   launch, no workspace. */
+int s2i_logmel_gather(const float* pool, const long long* row_offsets, const int* frames, int B, int T, float* out,
+                      void* stream);
 
 /* ---- streaming feature moments for the Frechet distance (StackGAN_v2/trainer.py:103-144) -----------------------------
  * compute_frethet_distance fits a Gaussian to each set of Inception pool3 rows with np.mean and np.cov.  Both follow

@@ -176,6 +176,7 @@ _SIGNATURES = {
     "s2i_signal_mean": (c_int, [P, P, P, c_int, P, P, P]),
     "s2i_logmel_power": (c_int, [P, P, P, c_int, P, P, P, P, P, c_int, c_int, P, P, P]),
     "s2i_logmel_finish": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
+    "s2i_logmel_gather": (c_int, [P, P, P, c_int, c_int, P, P]),
     "s2i_moments_accumulate": (c_int, [P, c_int, c_int, c_ll, P, P, P]),
 }
 

@@ -190,6 +190,31 @@ __global__ __launch_bounds__(256) void logmel_finish_kernel(const float* __restr
   out[idx] = v;
 }
 
+// A batch out of kept log-mel rows (speech_loader.py), standing for the padding and truncation to target_length of
+// load_one_audio_file (Audio_to_Image/utils.py:329-340) applied to rows computed earlier: one thread per 16-byte piece of `out`.  Utterance b owns the
+// T * 10 consecutive pieces [b * T * 10, +T * 10) of `out`; its first frames[b] * 10 of them are the consecutive pieces
+// of the pool from row off[b] on, the rest are the 0 dB fill of logmel_finish_kernel.  Lane i of a wave stores piece
+// base + i: 1 KiB per store instruction, and the loads are as contiguous inside an utterance.  Every address is a 64-bit
+// piece index: a pool may hold more than 2^31 floats.
+constexpr int ROW_PIECES = NMEL * 4 / 16;        // a 160-byte row is ten f32x4
+static_assert(ROW_PIECES * 16 == NMEL * 4, "a log-mel row must be whole 16-byte pieces");
+
+__global__ __launch_bounds__(256) void logmel_gather_kernel(const f32x4* __restrict__ pool,
+                                                            const long long* __restrict__ off,
+                                                            const int* __restrict__ frames, int T,
+                                                            f32x4* __restrict__ out, long long total) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const long long per = (long long)T * ROW_PIECES;
+  const long long b = idx / per;
+  const long long p = idx - b * per;
+  const long long o = off[b];
+  const long long kept = o >= 0 ? (long long)min(max(frames[b], 0), T) * ROW_PIECES : 0;   // unstored: all fill
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (p < kept) v = pool[o * ROW_PIECES + p];
+  out[idx] = v;
+}
+
 }  // namespace
 
 extern "C" size_t s2i_logmel_basis_elems(void) { return (size_t)NKG * 2 * NPT * 64 * 4; }
@@ -227,5 +252,18 @@ extern "C" int s2i_logmel_finish(const float* melpow, const unsigned* maxbits, c
   hipLaunchKernelGGL(logmel_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      melpow, maxbits, lens, T, layout, out, total);
   S2I_LAUNCH_CHECK("logmel_finish");
+  return 0;
+}
+
+extern "C" int s2i_logmel_gather(const float* pool, const long long* row_offsets, const int* frames, int B, int T,
+                                 float* out, void* stream) {
+  S2I_REQUIRE(pool && row_offsets && frames && out, "logmel_gather: null pointer");
+  S2I_REQUIRE(B >= 1 && T >= 1, "logmel_gather: bad shape (B %d, T %d)", B, T);
+  S2I_REQUIRE((((uintptr_t)pool | (uintptr_t)out) & 15) == 0, "logmel_gather: pool and out must be 16-byte aligned");
+  const long long total = (long long)B * T * ROW_PIECES;
+  S2I_REQUIRE((total + 255) / 256 <= 0x7fffffffLL, "logmel_gather: B %d x T %d is too large for one launch", B, T);
+  hipLaunchKernelGGL(logmel_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const f32x4*)pool, row_offsets, frames, T, (f32x4*)out, total);
+  S2I_LAUNCH_CHECK("logmel_gather");
   return 0;
 }

@@ -1753,3 +1753,38 @@ def image_batch(pool, offsets, sizes, plan, size, levels, tab1=None, tab2=None):
                               levels, ptr(tab1), ptr(tab2), ptr(o[0]), ptr(o[1]), ptr(o[2]), stream()),
           "s2i_image_batch")
     return outs
+
+
+# Tests set LOGMEL_GATHER_SENTINEL to a float (NaN): the output is then allocated filled with it, so a piece the kernel
+# skipped shows.
+LOGMEL_GATHER_SENTINEL = None
+
+
+def logmel_gather(pool, row_offsets, frames, T):
+    """A batch [B, 1, T, 40] out of kept log-mel rows (speech_loader.py) in one launch: utterance b is the `frames[b]`
+    rows of `pool` ([rows, 40] fp32) from row `row_offsets[b]` on, then the 0 dB fill to T -- what
+    `audio.log_mel(..., layout="nhwc", target_length=T)` gives for the utterances the rows were computed from, bit for
+    bit.  `row_offsets` int64 and `frames` int32 are device vectors of one length; 0 <= frames[b] <= T and the rows
+    they name lie inside the pool (the caller's business: they are device values).  No autograd."""
+    lib = _lib_ready()
+    T = int(T)
+    if pool.dtype != torch.float32 or pool.dim() != 2 or pool.shape[1] != 40 or not pool.is_contiguous():
+        raise ValueError("logmel_gather: pool must be a contiguous fp32 [rows, 40] tensor, got %s %s"
+                         % (pool.dtype, tuple(pool.shape)))
+    if (row_offsets.dtype != torch.int64 or frames.dtype != torch.int32 or row_offsets.dim() != 1
+            or frames.shape != row_offsets.shape or row_offsets.numel() < 1):
+        raise ValueError("logmel_gather: row_offsets (int64) and frames (int32) must be vectors of one length >= 1")
+    if not (pool.is_cuda and row_offsets.device == pool.device and frames.device == pool.device):
+        raise _lib.S2IError("logmel_gather runs on the MI355X kernel: pool, row_offsets and frames must share one "
+                            "device, got %s, %s, %s" % (pool.device, row_offsets.device, frames.device))
+    if T < 1:
+        raise ValueError("logmel_gather: T must be >= 1")
+    B = row_offsets.numel()
+    shape = (B, 1, T, 40)
+    if LOGMEL_GATHER_SENTINEL is None:
+        out = torch.empty(shape, dtype=torch.float32, device=pool.device)
+    else:
+        out = torch.full(shape, LOGMEL_GATHER_SENTINEL, dtype=torch.float32, device=pool.device)
+    check(lib.s2i_logmel_gather(ptr(pool.detach()), ptr(row_offsets.contiguous()), ptr(frames.contiguous()), B, T,
+                                ptr(out), stream()), "s2i_logmel_gather")
+    return out

@@ -9,13 +9,15 @@ Audio_to_Image/train_audio_encoder.py).  Single GPU.
 and a `class`.  Per item and epoch one random utterance with at least 64 frames and one random image view are drawn with
 `random`, as BirdDataset.__getitem__ does.  Every --eval_every epochs (and after the last) the test split is scored with
 retrieval.eval_class and `epoch_<n>.pth`, `latest.pth` and, on a new best test accuracy, `best.pth` are written in the
-reference's checkpoint layout, which extract_audio_feature --model reads.
+reference's checkpoint layout, which extract_audio_feature --model reads.  --resident reads every WAV once and keeps both
+splits' log-mel rows in device memory (speech_loader.ResidentSpeechSet): the same batches, one launch each.
 """
 import argparse
 import json
 import os
 import random
 import shutil
+import time
 
 import numpy as np
 import torch
@@ -92,6 +94,9 @@ def get_parser(description="fine-tune the speech encoder's LSTM head (conv stack
     p.add_argument("--lambda_distill", type=float, default=1.0)
     p.add_argument("--distill_T", type=float, default=2.0)
     p.add_argument("--seed", type=int, default=seed, help="seed of `random` (utterance / view draws, batch order)")
+    p.add_argument("--resident", action="store_true", default=False,
+                   help="keep both splits' log-mel rows in device memory (speech_loader.ResidentSpeechSet)")
+    p.add_argument("--resident_workers", type=int, default=16, help="threads that read the WAV files for --resident")
     return p
 
 
@@ -107,10 +112,23 @@ def trainer_kwargs(args):
                 lambda_distill=args.lambda_distill)
 
 
+def make_resident(split, name, dev, workers):
+    """`split` behind a speech_loader.ResidentSpeechSet, with one line about the pool."""
+    from .speech_loader import ResidentSpeechSet
+    t0 = time.perf_counter()
+    resident = ResidentSpeechSet(split, dev, workers=workers)
+    torch.cuda.synchronize(dev)
+    print("resident %s: %d utterances, %d rows, %d bytes, %.2f s" % (name, len(resident.row_offsets), resident.pool.shape[0],
+                                                                    resident.nbytes, time.perf_counter() - t0))
+    return resident
+
+
 def run(trainer, args, dev):
     """The epoch loop, evaluation and checkpoints shared with train_encoder -> best test accuracy."""
     data_dir = args.data_dir or os.path.join(".", "data", args.dataset)
     train, test = SplitData(data_dir, "train", args.dataset), SplitData(data_dir, "test", args.dataset)
+    if args.resident:
+        train, test = (make_resident(s, name, dev, args.resident_workers) for s, name in ((train, "train"), (test, "test")))
     os.makedirs(args.output_dir, exist_ok=True)
     best = -1.0
     for epoch in range(1, args.epoch + 1):
