@@ -536,6 +536,11 @@ int s2i_bn1_bwd_finalize(const float* part, int nparts, long long count, float* 
 /* torch.optim.Adam (no weight decay, no amsgrad) on a flat buffer, step = 1-based step count */
 int s2i_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
                   float beta2, float eps, int step, const int* step_dev, float gscale, void* stream);
+/* torch.optim.Adam(weight_decay = wd) on a flat buffer, the speech encoder's optimiser (train_audio_encoder.py:462):
+   the effective gradient is gscale * g + weight_decay * p (L2 decay, added before the moments), then the update of
+   s2i_adam_step.  With weight_decay = 0 the results are those of s2i_adam_step bit for bit. */
+int s2i_adam_l2_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+                     float eps, float weight_decay, int step, const int* step_dev, float gscale, void* stream);
 /* *counter += 1 on the stream (device-resident Adam step count, so a captured hipGraph of the
    train step replays with the right bias correction) */
 int s2i_increment(int* counter, void* stream);

@@ -155,6 +155,7 @@ _SIGNATURES = {
     "s2i_bn1_bwd_reduce": (c_int, [P, P, c_ll, P, P, c_int, P]),
     "s2i_bn1_bwd_finalize": (c_int, [P, c_int, c_ll, P, P, P, P]),
     "s2i_adam_step": (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_int, P, c_float, P]),
+    "s2i_adam_l2_step": (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_int, P, c_float, P]),
     "s2i_increment": (c_int, [P, P]),
     "s2i_ema_update": (c_int, [P, P, c_ll, c_float, P]),
     "s2i_scale_dev": (c_int, [P, P, c_ll, P, P]),

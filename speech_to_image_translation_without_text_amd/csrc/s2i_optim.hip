@@ -1,11 +1,22 @@
-// Optimiser passes over flat fp32 parameter buffers on gfx950: fused Adam (16 bytes per lane per buffer, device-side step
-// counter) and its counter increment, EMA of the generator weights, y = x * a[0] and y = a x + b y.  HBM-bound.
+// Optimiser passes over flat fp32 parameter buffers on gfx950: fused Adam, plain and with L2 weight decay (16 bytes per
+// lane per buffer, device-side step counter) and its counter increment, EMA of the generator weights, y = x * a[0] and
+// y = a x + b y.  HBM-bound.
 #include "s2i_elementwise.h"
 
 namespace {
+// one element's Adam update from its effective gradient gg; both kernels below end in it
+__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float gg, float b1, float b2, float eps,
+                                            float step_size, float bc2s) {
+  m = b1 * m + (1.f - b1) * gg;
+  v = b2 * v + (1.f - b2) * gg * gg;
+  p -= step_size * m / (sqrtf(v) / bc2s + eps);
+}
+
+// L2 = false: gg = gscale g (torch.optim.Adam).  L2 = true: gg = gscale g + wd p (torch.optim.Adam(weight_decay=wd)).
+template <bool L2>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, long long n4,
-                                                   long long n, float lr, float b1, float b2, float eps, int step,
+                                                   long long n, float lr, float b1, float b2, float eps, float wd, int step,
                                                    const int* __restrict__ step_dev, float gscale) {
   __shared__ float bc[2];
   if (threadIdx.x == 0) {
@@ -22,19 +33,20 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
       f32x4 pv = ld4(p + e * 4), gv = ld4(g + e * 4), mv = ld4(m + e * 4), vv = ld4(v + e * 4);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float gg = gv[j] * gscale;
-        mv[j] = b1 * mv[j] + (1.f - b1) * gg;
-        vv[j] = b2 * vv[j] + (1.f - b2) * gg * gg;
-        pv[j] -= step_size * mv[j] / (sqrtf(vv[j]) / bc2s + eps);
+        float pp = pv[j], mm = mv[j], v2 = vv[j];
+        float gg = gv[j] * gscale;
+        if (L2) gg += wd * pp;
+        adam_update(pp, mm, v2, gg, b1, b2, eps, step_size, bc2s);
+        pv[j] = pp; mv[j] = mm; vv[j] = v2;
       }
       st4(p + e * 4, pv); st4(m + e * 4, mv); st4(v + e * 4, vv);
     } else {
       for (long long k = e * 4; k < n; ++k) {
-        const float gg = g[k] * gscale;
-        const float mm = b1 * m[k] + (1.f - b1) * gg;
-        const float vv = b2 * v[k] + (1.f - b2) * gg * gg;
-        m[k] = mm; v[k] = vv;
-        p[k] -= step_size * mm / (sqrtf(vv) / bc2s + eps);
+        float pp = p[k], mm = m[k], vv = v[k];
+        float gg = g[k] * gscale;
+        if (L2) gg += wd * pp;
+        adam_update(pp, mm, vv, gg, b1, b2, eps, step_size, bc2s);
+        m[k] = mm; v[k] = vv; p[k] = pp;
       }
     }
   }
@@ -45,9 +57,20 @@ extern "C" int s2i_adam_step(float* p, const float* g, float* m, float* v, long 
   S2I_REQUIRE(p && g && m && v && n > 0, "adam_step: bad args");
   S2I_REQUIRE(step_dev || step >= 1, "adam_step: step must be >= 1");
   const long long n4 = (n + 3) / 4;
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n4)), dim3(256), 0, ST, p, g, m, v, n4, n, lr, beta1, beta2, eps,
-                     step, step_dev, gscale);
+  hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_for(n4)), dim3(256), 0, ST, p, g, m, v, n4, n, lr, beta1, beta2, eps,
+                     0.f, step, step_dev, gscale);
   S2I_LAUNCH_CHECK("adam_step");
+  return 0;
+}
+extern "C" int s2i_adam_l2_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, int step, const int* step_dev, float gscale,
+                                void* stream) {
+  S2I_REQUIRE(p && g && m && v && n > 0, "adam_l2_step: bad args");
+  S2I_REQUIRE(step_dev || step >= 1, "adam_l2_step: step must be >= 1");
+  const long long n4 = (n + 3) / 4;
+  hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n4)), dim3(256), 0, ST, p, g, m, v, n4, n, lr, beta1, beta2, eps,
+                     weight_decay, step, step_dev, gscale);
+  S2I_LAUNCH_CHECK("adam_l2_step");
   return 0;
 }
 

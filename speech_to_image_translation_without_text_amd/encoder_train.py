@@ -11,9 +11,19 @@ no-op, so train and eval agree.
 EncoderTrainer: the same step with ops.conv_stack_train in front (train-mode BatchNorm, temporal-conv and pool gradients),
 which consumes the gradient ops.lstm_sentence returns for the seam; Adam then updates Conv.* and RNN.*.  Train-mode
 BatchNorm is a property of this entry point: the module flag stays .eval() and CNNRNN.forward keeps refusing training
-mode.  Single GPU, fp32, one LSTM layer, frame counts that are powers of two; data-parallel training, bf16, more LSTM
-layers and dropout are not built.
+mode.  fp32, one LSTM layer, frame counts that are powers of two; bf16, more LSTM layers and dropout are not built.
+
+Both trainers take `fused_adam=True`: the trained parameters are re-homed into one flat fp32 buffer (trainer.FlatNet, as
+the GAN networks), their .grad views alias a second one, and the optimiser is s2i_increment + ONE s2i_adam_l2_step launch
+(torch.optim.Adam's L2 form, `gscale g + weight_decay p`) instead of torch.optim.Adam over 34 tensors (the head: 8); StepLR's rule is
+applied to the host-side learning rate in end_epoch.  `distributed=True` (implies fused_adam) is the data-parallel step of
+the reference's DistributedDataParallel run: the flat parameters and the BatchNorm buffers are broadcast from rank 0 at
+construction, every step sums the whole flat gradient buffer over the ranks in one torch.distributed.all_reduce between
+backward and the optimiser launch, and 1 / world_size is folded into that launch.  The loss and the train-mode BatchNorm
+statistics stay per rank, as under DDP; rank 0's running statistics are the ones a checkpoint keeps.
 """
+import warnings
+
 import numpy as np
 import torch
 
@@ -22,15 +32,41 @@ from . import _lib, ops, retrieval
 
 class HeadTrainer:
     def __init__(self, model, lr=1e-3, weight_decay=1e-5, step_size=30, gamma=0.2, loss_diff=1, loss_same=1, jel=True,
-                 l1=False, lambda_l1=1, distill=False, distill_T=2, lambda_distill=1):
+                 l1=False, lambda_l1=1, distill=False, distill_T=2, lambda_distill=1, fused_adam=False, distributed=False):
         if model.rnn_layers != 1:
             raise _lib.S2IError("HeadTrainer supports rnn_layers=1 (the reference's default)")
         self.model = model.eval()
-        self.params = ops.lstm_params(model.RNN)
-        self.optimizer = torch.optim.Adam(model.RNN.parameters(), lr=lr, weight_decay=weight_decay)
-        self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=step_size, gamma=gamma)
+        self.distributed = bool(distributed)
+        self.world = torch.distributed.get_world_size() if self.distributed else 1
+        self.step_size, self.gamma, self.epoch, self.steps = int(step_size), gamma, 0, 0
+        self.flat = self.optimizer = self.scheduler = None
+        if fused_adam or self.distributed:
+            from .trainer import FlatNet
+            self.flat = FlatNet(model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay,
+                                params=self._trained())
+            if self.distributed:        # identical start on every rank (DDP's initial broadcast)
+                torch.distributed.broadcast(self.flat.p, 0)
+                for buf in model.buffers():
+                    torch.distributed.broadcast(buf, 0)
+            self._stale()
+        else:
+            self.optimizer = torch.optim.Adam(self._trained(), lr=lr, weight_decay=weight_decay)
+            self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=step_size, gamma=gamma)
+        self.params = ops.lstm_params(model.RNN)       # after the re-homing: the flat buffer's views
         self.loss_args = dict(loss_diff=loss_diff, loss_same=loss_same, jel=jel, l1=l1, lambda_l1=lambda_l1, distill=distill,
                               distill_T=distill_T, lambda_distill=lambda_distill)
+
+    def _trained(self):
+        return list(self.model.RNN.parameters())
+
+    def _stale(self):
+        # the kernels write running_mean / running_var / num_batches_tracked and, with fused_adam, the parameters through
+        # raw pointers, which leaves the version counters CNNRNN._prepare keys its folded weights by unchanged: drop the cache
+        self.model._prepared = None
+
+    @property
+    def lr(self):
+        return self.flat.lr if self.flat is not None else self.optimizer.param_groups[0]["lr"]
 
     @property
     def device(self):
@@ -61,9 +97,18 @@ class HeadTrainer:
         lens, (feat, image_feature, label) = self._sorted(cap_lens, feat, image_feature.to(dev).float(), label.to(dev))
         _, sent = ops.lstm_sentence(feat, lens, *self.params)
         loss = ops.encoder_loss(sent, image_feature, label, **self.loss_args)
-        self.optimizer.zero_grad(set_to_none=True)
-        loss["loss"].backward()
-        self.optimizer.step()
+        if self.flat is None:
+            self.optimizer.zero_grad(set_to_none=True)
+            loss["loss"].backward()
+            self.optimizer.step()
+        else:
+            self.flat.zero_grad()           # one memset; never set_to_none, which would detach the views
+            loss["loss"].backward()
+            if self.distributed:            # on the current stream, behind the backward's launches
+                torch.distributed.all_reduce(self.flat.g, op=torch.distributed.ReduceOp.SUM)
+            self.flat.adam(1.0 / self.world)
+            self._stale()
+        self.steps += 1
         return {k: v.detach() for k, v in loss.items()}
 
     def step(self, mel_nhwc, cap_lens, image_feature, label):
@@ -72,7 +117,19 @@ class HeadTrainer:
         return self.step_features(self.features(mel_nhwc), cap_lens, image_feature, label)
 
     def end_epoch(self):
-        self.scheduler.step()
+        """StepLR: the learning rate is multiplied by gamma every step_size epochs."""
+        self.epoch += 1
+        if self.flat is None:
+            self.scheduler.step()
+        elif self.epoch % self.step_size == 0:
+            self.flat.lr *= self.gamma
+
+    def skip_epochs(self, n):
+        """Advance the schedule over n finished epochs (a resumed run; the Adam moments start afresh)."""
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)    # StepLR stepped before the first optimiser step
+            for _ in range(int(n)):
+                self.end_epoch()
 
     @torch.no_grad()
     def embed(self, mel_nhwc, cap_lens):
@@ -105,15 +162,8 @@ class EncoderTrainer(HeadTrainer):
     optimiser is the reference's Adam(model.parameters(), lr, weight_decay=1e-5) with StepLR.  embed / evaluate run the
     inference path, which folds the running statistics training has produced."""
 
-    def __init__(self, model, lr=1e-3, weight_decay=1e-5, step_size=30, gamma=0.2, **loss_args):
-        super().__init__(model, lr=lr, weight_decay=weight_decay, step_size=step_size, gamma=gamma, **loss_args)
-        self.optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
-        self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=step_size, gamma=gamma)
-
-    def _stale(self):
-        # the kernels update running_mean / running_var / num_batches_tracked through raw pointers, which leaves the
-        # version counters CNNRNN._prepare keys its folded weights by unchanged: drop the cache
-        self.model._prepared = None
+    def _trained(self):
+        return list(self.model.parameters())
 
     def features(self, mel_nhwc):
         """The conv stack in training mode on NHWC log-mel [B, 1, T, 40] -> [B, 1, T/64, 1024], with a graph behind it;

@@ -1659,6 +1659,13 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step=0, step_dev=None, gscale=1
                             ptr(step_dev), gscale, stream()), "s2i_adam_step")
 
 
+def adam_l2_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step=0, step_dev=None, gscale=1.0):
+    """torch.optim.Adam(weight_decay=...) on flat fp32 buffers: adam_step with gscale * g + weight_decay * p as the gradient."""
+    lib = _lib_ready()
+    check(lib.s2i_adam_l2_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, weight_decay, int(step),
+                               ptr(step_dev), gscale, stream()), "s2i_adam_l2_step")
+
+
 def ema_update(avg, p, decay):
     lib = _lib_ready()
     check(lib.s2i_ema_update(ptr(avg), ptr(p), p.numel(), decay, stream()), "s2i_ema_update")

@@ -167,16 +167,18 @@ class ResidentSpeechSet:
         frm_d = torch.from_numpy(frames.astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
         return ops.logmel_gather(self.pool, off_d, frm_d, self.T), frames
 
-    def batches(self, batch_size, device, shuffle):
+    def batches(self, batch_size, device, shuffle, order=None):
         """The batches of `SplitData.batches`: (mel_nhwc [B, 1, T, 40], cap_lens, image_feature [B, 1024], label [B]),
-        with its `random` calls in its order."""
+        with its `random` calls in its order.  `order`, where given, is the list of items to go through (a rank's share of
+        an epoch, train_encoder_head.shard_order; the pool itself is whole on every rank) and `shuffle` is not looked at."""
         from . import _lib
         if _resolve(device) != _resolve(self.device):
             raise _lib.S2IError("the log-mel pool is on %s, batches were asked for on %s: there is no CPU fallback and no "
                                 "copy between devices" % (self.device, device))
-        order = list(range(len(self)))
-        if shuffle:
-            random.shuffle(order)
+        if order is None:
+            order = list(range(len(self)))
+            if shuffle:
+                random.shuffle(order)
         for s in range(0, len(order), batch_size):
             items = order[s:s + batch_size]
             drawn = [self.draw(i) for i in items]

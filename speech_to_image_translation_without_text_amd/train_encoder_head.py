@@ -1,5 +1,5 @@
 """Fine-tune the LSTM head of a speech-encoder checkpoint on WAV recordings, conv stack frozen (the recurrent part of
-Audio_to_Image/train_audio_encoder.py).  Single GPU.
+Audio_to_Image/train_audio_encoder.py).
 
     python -m speech_to_image_translation_without_text_amd.train_encoder_head --model encoder.pt --dataset birds \\
         --data_dir data/birds --output_dir output/encoder_head --epoch 100 --batch_size 64 --bidirectional --jel_flag
@@ -11,6 +11,24 @@ and a `class`.  Per item and epoch one random utterance with at least 64 frames 
 retrieval.eval_class and `epoch_<n>.pth`, `latest.pth` and, on a new best test accuracy, `best.pth` are written in the
 reference's checkpoint layout, which extract_audio_feature --model reads.  --resident reads every WAV once and keeps both
 splits' log-mel rows in device memory (speech_loader.ResidentSpeechSet): the same batches, one launch each.
+
+--fused_adam keeps the trained parameters in one flat buffer and steps them with one fused Adam launch
+(encoder_train.py).  --resume PATH loads a checkpoint this CLI wrote and continues at its `meta.epoch` + 1 with the learning
+rate StepLR has reached by then; the Adam moments start afresh (the reference's checkpoints carry none either).  It stands
+in for --model, and `best.pth` becomes the best of the resumed run alone: a checkpoint does not record the accuracy it
+was saved at.
+--distributed trains data-parallel, one process per GPU, as the reference's run_audio_encoder.sh does under
+torch.distributed.launch:
+
+    python -m torch.distributed.run --nproc-per-node 8 -m speech_to_image_translation_without_text_amd.train_encoder_head \
+        --distributed --model encoder.pt ...
+
+RANK, WORLD_SIZE and LOCAL_RANK come from the launcher; --dist_backend (default nccl, i.e. RCCL) names the process group.
+Every rank loads the same model; an epoch's item order is drawn from random.Random(seed + epoch), alike on every rank, and
+rank r takes every world-th item of it from the r-th on (`shard_order`: DistributedSampler's padding and stride), so all
+ranks run ceil(N / world / batch_size) steps.  The global `random`, which draws views and utterances, is seeded seed + rank.
+Rank 0 alone prints, evaluates and writes checkpoints while the others wait at a barrier.  --resident keeps the WHOLE pool
+on every rank.
 """
 import argparse
 import json
@@ -57,11 +75,13 @@ class SplitData:
                 return image, wave, self.labels[index]
         raise ValueError("item %d: no utterance with at least %d frames in %d draws" % (index, MIN_FRAMES, MAX_DRAWS))
 
-    def batches(self, batch_size, device, shuffle):
-        """Batches of (mel_nhwc [B, 1, 2048, 40], cap_lens, image_feature [B, 1024], label [B])."""
-        order = list(range(len(self)))
-        if shuffle:
-            random.shuffle(order)
+    def batches(self, batch_size, device, shuffle, order=None):
+        """Batches of (mel_nhwc [B, 1, 2048, 40], cap_lens, image_feature [B, 1024], label [B]).  `order`, where given, is
+        the list of items to go through (a rank's share of an epoch, shard_order) and `shuffle` is not looked at."""
+        if order is None:
+            order = list(range(len(self)))
+            if shuffle:
+                random.shuffle(order)
         for s in range(0, len(order), batch_size):
             drawn = [self.draw(i) for i in order[s:s + batch_size]]
             mel, frames = audio.log_mel([w for _, w, _ in drawn], layout="nhwc", device=device)
@@ -69,12 +89,38 @@ class SplitData:
             yield mel, (frames // MIN_FRAMES).tolist(), image, torch.tensor([c for _, _, c in drawn], dtype=torch.int64)
 
 
-def get_parser(description="fine-tune the speech encoder's LSTM head (conv stack frozen); single GPU", model_required=True,
+def shard_order(order, rank, world):
+    """Rank `rank`'s share of an epoch's item order among `world` ranks, by torch's DistributedSampler rules: the order is
+    padded with its own head (repeated if need be) to a multiple of `world`, and the rank takes every world-th entry from
+    its own number on.  Every share has ceil(len(order) / world) entries."""
+    order = list(order)
+    if not 0 <= rank < world:
+        raise ValueError("shard_order: rank %d of %d" % (rank, world))
+    total = -(-len(order) // world) * world
+    padded = order
+    while order and len(padded) < total:
+        padded = padded + order[:total - len(padded)]
+    return padded[rank::world]
+
+
+class _Parser(argparse.ArgumentParser):
+    """--model is required (where the CLI requires it) unless --resume names the checkpoint to load."""
+    model_required = False
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if self.model_required and not ns.model and not ns.resume:
+            self.error("the following arguments are required: --model (or --resume)")
+        return ns
+
+
+def get_parser(description="fine-tune the speech encoder's LSTM head (conv stack frozen); single GPU, or one process per "
+               "GPU with --distributed", model_required=True,
                output_dir="./output/Audio_to_Image/encoder_head", seed=None):
     """The flags of this CLI; train_encoder builds its own from the same list (--model optional, a default seed)."""
-    p = argparse.ArgumentParser(description=description)
-    p.add_argument("--model", type=str, required=model_required, default="" if not model_required else None,
-                   help="CNNRNN checkpoint to start from")
+    p = _Parser(description=description)
+    p.model_required = model_required
+    p.add_argument("--model", type=str, default="", help="CNNRNN checkpoint to start from")
     p.add_argument("--dataset", choices=["birds", "flowers"], default="birds")
     p.add_argument("--data_dir", type=str, default=None, help="directory with train.json / test.json (default ./data/<dataset>)")
     p.add_argument("--output_dir", type=str, default=output_dir)
@@ -97,6 +143,14 @@ def get_parser(description="fine-tune the speech encoder's LSTM head (conv stack
     p.add_argument("--resident", action="store_true", default=False,
                    help="keep both splits' log-mel rows in device memory (speech_loader.ResidentSpeechSet)")
     p.add_argument("--resident_workers", type=int, default=16, help="threads that read the WAV files for --resident")
+    p.add_argument("--fused_adam", action="store_true", default=False,
+                   help="flat parameter storage and one fused Adam launch per step (encoder_train.py)")
+    p.add_argument("--distributed", action="store_true", default=False,
+                   help="data-parallel training, one process per GPU (start under torch.distributed.run); implies --fused_adam")
+    p.add_argument("--dist_backend", type=str, default="nccl", help="torch.distributed backend of --distributed")
+    p.add_argument("--resume", type=str, default="",
+                   help="checkpoint of this CLI to continue from, at its epoch + 1 (it stands in for --model; best.pth is "
+                        "the best of the resumed run alone)")
     return p
 
 
@@ -109,58 +163,124 @@ def trainer_kwargs(args):
     return dict(lr=args.learning_rate, weight_decay=1e-5, step_size=args.lr_scheduler_step_size,
                 gamma=args.lr_scheduler_gamma, loss_diff=args.loss_diff, loss_same=args.loss_same, jel=args.jel_flag,
                 l1=args.l1_flag, lambda_l1=args.lambda_l1, distill=args.distill_flag, distill_T=args.distill_T,
-                lambda_distill=args.lambda_distill)
+                lambda_distill=args.lambda_distill, fused_adam=args.fused_adam, distributed=args.distributed)
 
 
-def make_resident(split, name, dev, workers):
+def make_resident(split, name, dev, workers, say=print):
     """`split` behind a speech_loader.ResidentSpeechSet, with one line about the pool."""
     from .speech_loader import ResidentSpeechSet
     t0 = time.perf_counter()
     resident = ResidentSpeechSet(split, dev, workers=workers)
     torch.cuda.synchronize(dev)
-    print("resident %s: %d utterances, %d rows, %d bytes, %.2f s" % (name, len(resident.row_offsets), resident.pool.shape[0],
-                                                                    resident.nbytes, time.perf_counter() - t0))
+    say("resident %s: %d utterances, %d rows, %d bytes, %.2f s" % (name, len(resident.row_offsets), resident.pool.shape[0],
+                                                                  resident.nbytes, time.perf_counter() - t0))
     return resident
 
 
+def init_device(args):
+    """The device of this process.  Under --distributed: LOCAL_RANK's GPU and the process group (RANK and WORLD_SIZE from
+    the launcher's environment), set up before any other GPU work."""
+    if not args.distributed:
+        return torch.device("cuda", torch.cuda.current_device())
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local_rank)
+    dev = torch.device("cuda", local_rank)
+    if args.dist_backend == "nccl":
+        torch.distributed.init_process_group("nccl", device_id=dev)
+    else:
+        torch.distributed.init_process_group(args.dist_backend)
+    return dev
+
+
+def seed_draws(args):
+    """Seed the global `random` (views, utterances, and the batch order of a single-process run): --seed, plus the rank
+    under --distributed, so that the ranks draw independently."""
+    seed = args.seed
+    if args.distributed:
+        seed = (seed or 0) + torch.distributed.get_rank()
+    if seed is not None:
+        random.seed(seed)
+
+
+def resume_epoch(path):
+    """`meta.epoch` of a checkpoint written by `run`."""
+    ckpt = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(ckpt, dict) or "meta" not in ckpt or "epoch" not in ckpt["meta"]:
+        raise SystemExit("--resume %s: the checkpoint carries no meta.epoch" % path)
+    return int(ckpt["meta"]["epoch"])
+
+
+def train_and_close(make_trainer, args):
+    """main() of both CLIs behind the parser: device (and process group), model and trainer, `run`, and the process
+    group's end."""
+    dev = init_device(args)
+    try:
+        return run(make_trainer(dev), args, dev)
+    finally:
+        if args.distributed:
+            torch.distributed.destroy_process_group()
+
+
 def run(trainer, args, dev):
-    """The epoch loop, evaluation and checkpoints shared with train_encoder -> best test accuracy."""
+    """The epoch loop, evaluation and checkpoints shared with train_encoder -> best test accuracy.  The number of
+    optimiser steps taken is left in `trainer.steps` and, under --distributed, printed by every rank."""
+    rank, world = (torch.distributed.get_rank(), torch.distributed.get_world_size()) if args.distributed else (0, 1)
+    say = print if rank == 0 else (lambda *a, **k: None)
     data_dir = args.data_dir or os.path.join(".", "data", args.dataset)
-    train, test = SplitData(data_dir, "train", args.dataset), SplitData(data_dir, "test", args.dataset)
+    # the test split is rank 0's alone: the other ranks never evaluate, and with --resident would fill a pool they never read
+    names = ("train", "test") if rank == 0 else ("train",)
+    splits = [SplitData(data_dir, name, args.dataset) for name in names]
     if args.resident:
-        train, test = (make_resident(s, name, dev, args.resident_workers) for s, name in ((train, "train"), (test, "test")))
-    os.makedirs(args.output_dir, exist_ok=True)
-    best = -1.0
-    for epoch in range(1, args.epoch + 1):
+        splits = [make_resident(s, name, dev, args.resident_workers, say) for s, name in zip(splits, names)]
+    train, test = splits[0], (splits[1] if rank == 0 else None)
+    if rank == 0:
+        os.makedirs(args.output_dir, exist_ok=True)
+    first = 1
+    if args.resume:
+        first = resume_epoch(args.resume) + 1
+        trainer.skip_epochs(first - 1)
+    best = -1.0        # of THIS run: a resumed run does not know the accuracy behind an earlier best.pth and replaces it
+    for epoch in range(first, args.epoch + 1):
         total, seen = None, 0
-        for mel, cap_lens, image, label in train.batches(args.batch_size, dev, shuffle=True):
+        order = None
+        if args.distributed:
+            order = list(range(len(train)))
+            random.Random((args.seed or 0) + epoch).shuffle(order)       # alike on every rank
+            order = shard_order(order, rank, world)
+        for mel, cap_lens, image, label in train.batches(args.batch_size, dev, shuffle=True, order=order):
             loss = trainer.step(mel, cap_lens, image, label)
             part = torch.stack([loss["loss"], loss["accu"]]) * len(cap_lens)       # stays on the device until the epoch ends
             total = part if total is None else total + part
             seen += len(cap_lens)
         trainer.end_epoch()
         mean_loss, mean_accu = (total / seen).tolist()
-        print("epoch %d: loss %.4f, batch accu %.2f" % (epoch, mean_loss, mean_accu))
+        say("epoch %d: loss %.4f, batch accu %.2f" % (epoch, mean_loss, mean_accu))
         if epoch % args.eval_every == 0 or epoch == args.epoch:
-            accu, ap50 = trainer.evaluate(test.batches(args.batch_size, dev, shuffle=False))
-            path = os.path.join(args.output_dir, "epoch_%d.pth" % epoch)
-            trainer.save(path, epoch)
-            shutil.copyfile(path, os.path.join(args.output_dir, "latest.pth"))
-            if accu > best:
-                best = accu
-                shutil.copyfile(path, os.path.join(args.output_dir, "best.pth"))
-            print(json.dumps({"epoch": epoch, "test_accu": accu, "test_ap50": ap50, "best_accu": best}))
+            if rank == 0:
+                accu, ap50 = trainer.evaluate(test.batches(args.batch_size, dev, shuffle=False))
+                path = os.path.join(args.output_dir, "epoch_%d.pth" % epoch)
+                trainer.save(path, epoch)
+                shutil.copyfile(path, os.path.join(args.output_dir, "latest.pth"))
+                if accu > best:
+                    best = accu
+                    shutil.copyfile(path, os.path.join(args.output_dir, "best.pth"))
+                print(json.dumps({"epoch": epoch, "test_accu": accu, "test_ap50": ap50, "best_accu": best}))
+            if args.distributed:
+                torch.distributed.barrier()
+    if args.distributed:
+        print("rank %d of %d: %d steps" % (rank, world, trainer.steps), flush=True)
     return best
 
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
     check_args(args)
-    if args.seed is not None:
-        random.seed(args.seed)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    model = load_encoder(args.model, args.bidirectional, 1, dev)
-    return run(HeadTrainer(model, **trainer_kwargs(args)), args, dev)
+
+    def make_trainer(dev):
+        seed_draws(args)
+        model = load_encoder(args.resume or args.model, args.bidirectional, 1, dev)
+        return HeadTrainer(model, **trainer_kwargs(args))
+    return train_and_close(make_trainer, args)
 
 
 if __name__ == "__main__":

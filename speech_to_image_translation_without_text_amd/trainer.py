@@ -209,11 +209,14 @@ def load_network(gpus, distributed):
 # ---- flat parameter storage + fused optimiser -------------------------------------------------------------
 class FlatNet:
     """All parameters of one network re-homed into a flat buffer (views keep nn.Module semantics);
-    gradients accumulate into a second flat buffer; Adam moments in two more."""
+    gradients accumulate into a second flat buffer; Adam moments in two more.  `params` re-homes that subset of the
+    network's parameters instead of all of them; a `weight_decay` other than 0 makes the step torch.optim.Adam's L2 form
+    (ops.adam_l2_step: the speech encoder's optimiser, encoder_train.py)."""
 
-    def __init__(self, net, lr, betas=(0.5, 0.999), eps=1e-8, with_ema=False):
+    def __init__(self, net, lr, betas=(0.5, 0.999), eps=1e-8, with_ema=False, weight_decay=0.0, params=None):
         self.net = net
-        self.params = [p for p in net.parameters()]
+        self.params = [p for p in (net.parameters() if params is None else params)]
+        self.weight_decay = float(weight_decay)
         dev = self.params[0].device
         self.sizes = [p.numel() for p in self.params]
         self.offsets, off = [], 0
@@ -248,8 +251,12 @@ class FlatNet:
     def adam(self, gscale=1.0):
         ops.increment(self.step_dev)
         self.step_count += 1
-        ops.adam_step(self.p, self.g, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
-                      step_dev=self.step_dev, gscale=gscale)
+        if self.weight_decay:
+            ops.adam_l2_step(self.p, self.g, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
+                             self.weight_decay, step_dev=self.step_dev, gscale=gscale)
+        else:
+            ops.adam_step(self.p, self.g, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
+                          step_dev=self.step_dev, gscale=gscale)
         ops.refresh_packed(self.params)
 
     def ema(self, decay=0.999):

@@ -1,7 +1,9 @@
 """Times the speech encoder's full training step and the kernels it added, at the reference's shape (T = 2048 frames,
 bidirectional, 1024-d), with HIP events: median of --iters after --warmup.
 
-  * one EncoderTrainer.step at B = 64 and B = 32 (conv stack in training mode, LSTM head, loss, backward, Adam);
+  * one EncoderTrainer.step at B = 64 and B = 32 (conv stack in training mode, LSTM head, loss, backward, Adam), without and
+    with fused_adam, and the optimiser alone on that step's gradients: torch.optim.Adam.step over the separate tensors
+    against s2i_increment + one s2i_adam_l2_step launch over the flat buffer;
   * the conv stack alone, forward + backward, through ops.conv_stack_train and through the SAME nn.Sequential under stock
     PyTorch-ROCm autograd (.train(), NCHW, on the device): the only yardstick there is;
   * per production layer at B = 64: s2i_conv1d_dgrad and s2i_conv1d_wgrad in TFLOP/s next to torch's
@@ -9,7 +11,7 @@ bidirectional, 1024-d), with HIP events: median of --iters after --warmup.
 
 Prints one JSON line.  No thresholds: nobody has measured these numbers before.
 
-    python tools/encoder_train_bench.py [--iters 20] [--warmup 5] [--batches 64,32]
+    python tools/encoder_train_bench.py [--iters 20] [--warmup 5] [--batches 64,32] [--no_layers]
 """
 import argparse
 import copy
@@ -100,6 +102,7 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batches", type=str, default="64,32")
+    ap.add_argument("--no_layers", action="store_true", help="skip the per-layer rows")
     args = ap.parse_args(argv)
     lib = _lib.load()
     _lib.require_device()
@@ -116,6 +119,12 @@ def main(argv=None):
         model = copy.deepcopy(net).to(dev)
         trainer = EncoderTrainer(model, jel=True)
         r = {"step_ms": timed(lambda: trainer.step(mel, lens, image, label), args.iters, args.warmup)}
+        r["torch_adam_step_ms"] = timed(trainer.optimizer.step, args.iters, args.warmup)      # on the last step's gradients
+        fused = EncoderTrainer(copy.deepcopy(net).to(dev), jel=True, fused_adam=True)
+        r["fused_adam_step_ms"] = timed(lambda: fused.step(mel, lens, image, label), args.iters, args.warmup)
+        r["increment_adam_l2_ms"] = timed(fused.flat.adam, args.iters, args.warmup)
+        r["flat_parameters"] = fused.flat.total
+        del fused
         dfeat = torch.randn(B, 1, 32, 1024, generator=g).to(dev)
         params = list(model.Conv.parameters())
 
@@ -133,7 +142,8 @@ def main(argv=None):
         r["conv_stack_fwd_bwd_ms"] = timed(ours, args.iters, args.warmup)
         r["stock_autograd_conv_stack_fwd_bwd_ms"] = timed(theirs, args.iters, args.warmup)
         result["B%d" % B] = r
-    result["layers_B64"] = layer_rows(lib, dev, 64, args.iters, args.warmup)
+    if not args.no_layers:
+        result["layers_B64"] = layer_rows(lib, dev, 64, args.iters, args.warmup)
     print(json.dumps(result))
 
 
