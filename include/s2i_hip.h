@@ -518,12 +518,15 @@ int s2i_bn_relu_bwd_apply(const float* y, const float* out, const float* dout, l
    maximum, recomputed from the stored pool input x, is at i; a tie goes to the lowest position, as torch's max_pool2d.
    x, dx [B][H][W][C], dy [B][H][W/2][C]. */
 int s2i_maxpool_w3s2_backward(const float* x, const float* dy, int B, int H, int W, int C, float* dx, void* stream);
-/* The leading BatchNorm2d(1): one channel over all n = 4 q elements.  The per-channel kernels run on the [q][4] view
-   (s2i_colstats, s2i_bn_act_forward / _bwd_apply with C = 4, S2I_ACT_NONE); the two finalize calls fold the four columns
-   of the partial sums ([2][nparts][4]) into the one channel.  s2i_bn1_bwd_reduce writes the backward sums of dout and
+/* The leading BatchNorm2d(1): one channel over all n = 4 q elements.  The per-channel apply kernels run on the [q][4] view
+   (s2i_bn_act_forward / _bwd_apply with C = 4, S2I_ACT_NONE); the two finalize calls fold the four columns
+   of the partial sums ([2][nparts][4]) into the one channel.  s2i_bn1_stats writes the sums of x and of x * x in that
+   layout, formed in double and stored as (high, low) float pairs in columns 0 and 1: the input is un-normalised log-mel
+   (mean^2 several times the variance), which fp32 sums of fp32 squares do not tolerate.  s2i_bn1_bwd_reduce writes the backward sums of dout and
    dout * xhat in that layout (column 0; a block's terms are added in double: d weight is a sum over every input element).  s2i_bn1_finalize writes the C = 4 coefficient table
    [mean x4 | invstd x4 | scale x4 | shift x4] and updates the running statistics as s2i_bn_finalize does (count = n);
    s2i_bn1_bwd_finalize writes dgamma[0], dbeta[0] (assigned; either may be NULL) and red2 = [mean_dz x4 | mean_dz_xhat x4]. */
+int s2i_bn1_stats(const float* x, long long n, float* part, int nparts, void* stream);
 int s2i_bn1_finalize(const float* part, int nparts, long long count, const float* gamma, const float* beta,
                      float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps,
                      float* coef4x4, void* stream);

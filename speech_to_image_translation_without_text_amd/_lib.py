@@ -151,6 +151,7 @@ _SIGNATURES = {
     "s2i_bn_relu_bwd_reduce": (c_int, [P, P, P, c_ll, c_int, P, P, c_int, P]),
     "s2i_bn_relu_bwd_apply": (c_int, [P, P, P, c_ll, c_int, P, P, P, P]),
     "s2i_maxpool_w3s2_backward": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P]),
+    "s2i_bn1_stats": (c_int, [P, c_ll, P, c_int, P]),
     "s2i_bn1_finalize": (c_int, [P, c_int, c_ll, P, P, P, P, P, c_float, c_float, P, P]),
     "s2i_bn1_bwd_reduce": (c_int, [P, P, c_ll, P, P, c_int, P]),
     "s2i_bn1_bwd_finalize": (c_int, [P, c_int, c_ll, P, P, P, P]),

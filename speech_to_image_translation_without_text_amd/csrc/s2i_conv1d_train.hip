@@ -401,6 +401,38 @@ __global__ __launch_bounds__(256) void bn1_finalize_kernel(const float* __restri
   }
 }
 
+// Statistics of the one channel: part[0 | 1][block][0 .. 1] = the sum of x and of x * x over the block's quads, each held as
+// a (high, low) pair of floats (columns 2 .. 3 zero) that bn1_finalize_kernel, which adds all four columns in double, puts
+// together again.  Every term and every sum is double: the input is log-mel in dB (mean about -40, mean^2 / var 3 .. 5), so
+// var = E[x^2] - mean^2 magnifies the relative error of E[x^2] that many times, and fp32 squares in fp32 chains
+// (s2i_colstats on the [n / 4][4] view) left the running variance of an 80-element input 2.5e-7 off, outside its bound.
+__global__ __launch_bounds__(256) void bn1_stats_kernel(const float* __restrict__ x, long long Q, float* __restrict__ part,
+                                                        int nparts) {
+  __shared__ double sh[2][256];
+  const int tid = threadIdx.x;
+  const long long chunk = (Q + nparts - 1) / nparts;
+  const long long q0 = blockIdx.x * chunk;
+  const long long q1 = q0 + chunk < Q ? q0 + chunk : Q;
+  double a0 = 0.0, a1 = 0.0;
+  for (long long q = q0 + tid; q < q1; q += 256) {
+    const f32x4 xv = ld4(x + q * 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const double v = (double)xv[j];
+      a0 += v;
+      a1 += v * v;
+    }
+  }
+  sh[0][tid] = a0;
+  sh[1][tid] = a1;
+  __syncthreads();
+  if (tid != 0) return;
+  for (int k = 1; k < 256; ++k) { a0 += sh[0][k]; a1 += sh[1][k]; }
+  const float h0 = (float)a0, h1 = (float)a1;
+  st4(part + ((size_t)0 * nparts + blockIdx.x) * 4, f32x4{h0, (float)(a0 - (double)h0), 0.f, 0.f});
+  st4(part + ((size_t)1 * nparts + blockIdx.x) * 4, f32x4{h1, (float)(a1 - (double)h1), 0.f, 0.f});
+}
+
 // Backward sums of the one channel: part[0 | 1][block][0] = sum of dout and of dout * xhat over the block's quads (columns
 // 1 .. 3 zero, so bn1_finalize_kernel reads the layout of the C = 4 kernels).  A thread adds four products in fp32 and
 // carries its sum in double; the block's 256 sums are added in double, in thread order.  (The C = 4 walk of
@@ -533,6 +565,13 @@ extern "C" int s2i_maxpool_w3s2_backward(const float* x, const float* dy, int B,
   const long long total = (long long)B * H * W * C;
   hipLaunchKernelGGL(maxpool_w3s2_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, ST, x, dy, W, C, total, dx);
   S2I_LAUNCH_CHECK("maxpool_w3s2_backward");
+  return 0;
+}
+
+extern "C" int s2i_bn1_stats(const float* x, long long n, float* part, int nparts, void* stream) {
+  S2I_REQUIRE(x && part && n > 0 && n % 4 == 0 && nparts > 0, "bn1_stats: bad args");
+  hipLaunchKernelGGL(bn1_stats_kernel, dim3(nparts), dim3(256), 0, ST, x, n / 4, part, nparts);
+  S2I_LAUNCH_CHECK("bn1_stats");
   return 0;
 }
 

@@ -1533,8 +1533,8 @@ def temporal_conv_bn_relu(x, weight, gamma, beta, bn_buffers, geom):
 
 class InputBatchNorm(torch.autograd.Function):
     """The leading nn.BatchNorm2d(1) in training mode: ONE channel over all elements of x [B, 1, T, n_mels].  The
-    per-channel kernels run on the [n / 4][4] view of the tensor; s2i_bn1_finalize / s2i_bn1_bwd_finalize fold the four
-    columns into the channel."""
+    per-channel apply kernels run on the [n / 4][4] view of the tensor; s2i_bn1_finalize / s2i_bn1_bwd_finalize fold the
+    four columns into the channel.  The statistics are s2i_bn1_stats' (double sums: x is un-normalised log-mel)."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, bn_buffers):
@@ -1547,7 +1547,7 @@ class InputBatchNorm(torch.autograd.Function):
         R = n // 4
         nparts = _num_parts(R)
         part = _cnew((2, nparts, 4), dev)
-        check(lib.s2i_colstats(ptr(x), R, 4, 4, ptr(part), nparts, stream()), "s2i_colstats")
+        check(lib.s2i_bn1_stats(ptr(x), n, ptr(part), nparts, stream()), "s2i_bn1_stats")
         coef = _cnew((1, 4, 4), dev)
         rm, rv, nbt = bn_buffers
         check(lib.s2i_bn1_finalize(ptr(part), nparts, n, ptr(gamma), ptr(beta), ptr(rm), ptr(rv), ptr(nbt), BN_MOMENTUM, BN_EPS,

@@ -9,6 +9,11 @@ another run (`decisions`), and mutants can be made.  `mutant` names one delibera
   "pool_no_add" the pool backward assigns instead of adding where two windows meet
   "biased_var"  the running variance is updated with the biased batch variance
   "bn0_dropped" the leading BatchNorm2d(1) gets no gradients
+  "pad_even"    the input gradient gives every tap the rows of its parity as if pad were even ((i - t) % s == 0)
+  "even_k_drop" ... or loses the last tap of an even k
+  "col_tail_zero" the weight gradient leaves the columns c >= 64 * (Cin // 64) zero (a whole-tile-only column clip)
+The last three are inert at the seven layer geometries (every pad even, every k odd, every Cin a multiple of 64) and are
+what the edge cases below exist for.
 tests/test_encoder_conv_train_cpu.py pins the composition to torch autograd through the model's own nn.Sequential.
 """
 import torch
@@ -43,25 +48,28 @@ def conv_dgrad(dy, w, geom, W, mutant=None):
     B, _, Wo, O = dy.shape
     i = torch.arange(W, device=dy.device)
     dx = dy.new_zeros((B, W, w.shape[1]))
-    for t in range(k):
+    for t in range(k - 1 if (mutant == "even_k_drop" and k % 2 == 0) else k):
         num = i + pad - t
         j = torch.div(num, s, rounding_mode="floor")
         ok = (j >= 0) & (j < Wo)
         if mutant != "no_parity":
-            ok = ok & (num % s == 0)
+            ok = ok & ((i - t if mutant == "pad_even" else num) % s == 0)
         if bool(ok.any()):
             dx[:, ok] += dy[:, 0, j[ok]] @ w[:, :, t]
     return dx.unsqueeze(1)
 
 
-def conv_wgrad(x, dy, geom):
+def conv_wgrad(x, dy, geom, mutant=None):
     """dW[o, c, 0, t] = sum_{b, ox} dy[b, ox, o] x[b, ox s - pad + t, c] -> (O, C, 1, k)."""
     k, s, pad = geom
     B, _, Wo, O = dy.shape
     xp = F.pad(x[:, 0], (0, 0, pad, pad))
     g = dy[:, 0].reshape(B * Wo, O)
     dw = [g.t() @ xp[:, t:t + s * (Wo - 1) + 1:s].reshape(B * Wo, -1) for t in range(k)]
-    return torch.stack(dw, 2).unsqueeze(2)
+    dw = torch.stack(dw, 2).unsqueeze(2)
+    if mutant == "col_tail_zero":
+        dw[:, 64 * (x.shape[3] // 64):] = 0
+    return dw
 
 
 def bn_finalize(y, gamma, beta, running, mutant=None):
@@ -351,17 +359,17 @@ def bn_case(M, C, seed=0, m=BN_MARGIN):
     return y, gamma, beta, dout, running
 
 
-def pool_case(B, W, C, seed=0, ties=False):
-    """Pool input [B, 1, W, C] and a cotangent.  The values are a random permutation of an even grid over [-2, 2), so any two
-    differ by at least 4 / (B W C); with `ties` the input is post-ReLU (every negative value an exact zero: windows of
+def pool_case(B, W, C, seed=0, ties=False, H=1):
+    """Pool input [B, H, W, C] and a cotangent.  The values are a random permutation of an even grid over [-2, 2), so any two
+    differ by at least 4 / (B H W C); with `ties` the input is post-ReLU (every negative value an exact zero: windows of
     zeros tie) and one positive tie is constructed at positions 0 and 1 of (b, c) = (0, 0)."""
     g = torch.Generator().manual_seed(9800 + seed + 3 * W + C)
-    n = B * W * C
-    x = (torch.randperm(n, generator=g).double() * (4.0 / n) - 2.0).view(B, 1, W, C).float().double()
+    n = B * H * W * C
+    x = (torch.randperm(n, generator=g).double() * (4.0 / n) - 2.0).view(B, H, W, C).float().double()
     if ties:
         x = torch.relu(x)
         x[0, 0, 0, 0] = x[0, 0, 1, 0] = 2.5
-    dy = torch.randn(B, 1, W // 2, C, generator=g, dtype=torch.float32).double()
+    dy = torch.randn(B, H, W // 2, C, generator=g, dtype=torch.float32).double()
     return x, dy
 
 
@@ -397,6 +405,32 @@ BN_CASES = [(24, 64), (24, 1024), (6144, 64), (6144, 1024)]
 BN0_CASE = (3, 64)                    # B, T of the scalar input BatchNorm
 POOL_CASES = [(3, W, C, ties) for C in (64, 512) for W in (2, 16) for ties in (False, True)]
 STACK_CASE = (4, 128)
+
+# Off the layer shapes.  (cin, cout, (k, s, pad), B, Wo), W = Wo s:
+CONV_EDGE_CASES = [
+    (32, 32, (1, 1, 0), 3, 8),         # kw = 1; Cin < 64 in the 64-wide dgrad template; one K chunk
+    (4, 32, (2, 2, 0), 3, 8),          # kw == stride: one tap per phase; the smallest Cin
+    (36, 96, (4, 2, 1), 5, 8),         # even k, odd pad; 3 chunks per tap; wgrad 128 x 64 tile partial in both axes
+    (68, 32, (3, 2, 1), 3, 16),        # odd pad (r != ph); Cin = 68 in the 128-wide template; wgrad 64 x 64 + a 4-column tile
+    (192, 160, (31, 2, 15), 2, 4),     # kw = 31 with W < kw; partial second column tile; wgrad 128 x 128 partial in both axes
+    (64, 128, (30, 2, 14), 3, 4),      # wide even k
+    (64, 64, (3, 1, 1), 33, 16),       # M = 528: 17 chunks in 4 splits, the last chunk half full
+    (64, 64, (3, 1, 1), 5, 32),        # Mq = 160: partial second dgrad row tile, a batch boundary inside a tile
+    (64, 64, (3, 1, 1), 1, 1),         # B = Wo = 1
+]
+# s2i_conv1d_wgrad takes these, s2i_conv1d_dgrad refuses them (Cout % 32 != 0; stride 4): DESIGN.md 8b3
+WGRAD_ONLY_CASES = [(64, 36, (3, 1, 1), 3, 8), (8, 8, (4, 4, 0), 3, 8)]
+# (M, C): Q = 1; Q = 3 with idle lanes; Q = 513 (gy = 3, one live quad in the last block) and a chunk of 65 that does not
+# divide M; nparts = 1024 with trailing empty parts
+BN_EDGE_CASES = [(8, 4), (65, 12), (129, 2052), (65537, 4)]
+BN0_EDGE_CASES = [(1, 2), (7, 40)]    # R = 20 in one part; R = 2 800 in 43 parts of 66 with a ragged last one
+POOL_EDGE_CASES = [(B, H, W, C, ties) for B, H, W, C in ((3, 2, 4, 4), (1, 1, 2, 4), (2, 1, 64, 68)) for ties in (False, True)]
+# one block as ops.temporal_conv_bn_relu runs it: (cin, cout, geom or None for the first (n_mels x 1) layer, B, Wo)
+BLOCK_CASES = ([(40, 64, None, B, T) for B, T in ((3, 8), (33, 32))]
+               + [(cin, cout, geom, B, Wo) for cin, cout, geom in (LAYER_GEOMS[1], LAYER_GEOMS[6]) for B, Wo in ((3, 8), (33, 32))])
+# the edge case at which each of the edge mutants leaves its bound (tests/test_encoder_conv_train_cpu.py asserts it)
+MUTANT_KILLS = {"pad_even": (68, 32, (3, 2, 1), 3, 16), "even_k_drop": (36, 96, (4, 2, 1), 5, 8),
+                "col_tail_zero": (68, 32, (3, 2, 1), 3, 16)}
 TRAINER_STEPS = 5
 TRAINER_LOSS = dict(jel=True, l1=True)
 
@@ -406,6 +440,35 @@ def bn0_case(B, T, seed=0):
     r = lambda *shape: torch.randn(*shape, generator=g, dtype=torch.float32).double()
     x = mel_case(B, T, seed=seed + 5)
     return x, (1.0 + 0.1 * r(1)).float().double(), (0.2 * r(1)).float().double(), r(B, 1, T, 40), (0.2 * r(1), 0.5 + r(1).abs(), 3)
+
+
+def block_case(cin, cout, geom, B, Wo, seed=0):
+    """x [B, 1, W, cin], w (cout, cin, k), gamma, beta, a cotangent of the block's output and running statistics."""
+    x, w, dout = conv_case(cin, cout, geom or (1, 1, 0), B, Wo, seed=seed + 100)
+    g = torch.Generator().manual_seed(9600 + seed + cin + cout + Wo)
+    r = lambda *shape: torch.randn(*shape, generator=g, dtype=torch.float32).double()
+    gamma, beta = (1.0 + 0.1 * r(cout)).float().double(), (0.2 * r(cout)).float().double()
+    return x, w, gamma, beta, dout, (0.2 * r(cout), 0.5 + r(cout).abs(), 3)
+
+
+def block_all(x, w, gamma, beta, dout, running, geom, dtype, mask=None):
+    """Conv + train-mode BatchNorm + ReLU forward and backward in `dtype`; `mask` replaces the run's own out > 0."""
+    c = lambda t: t.to(dtype)
+    geom = geom or (1, 1, 0)
+    y = conv_fwd(c(x), c(w), geom)
+    coef, new = bn_finalize(y, c(gamma), c(beta), (c(running[0]), c(running[1]), running[2]))
+    z, out = bn_relu_forward(y, coef)
+    dy, dgamma, dbeta = bn_relu_backward(y, out > 0 if mask is None else mask, c(dout), coef)
+    return dict(z=z, out=out, mask=out > 0, dx=conv_dgrad(dy, c(w), geom, x.shape[2]), dw=conv_wgrad(c(x), dy, geom),
+                dgamma=dgamma, dbeta=dbeta, running_mean=new[0], running_var=new[1], nbt=new[2])
+
+
+def block_errs(got, ref, what=""):
+    """[(class, what, rel_err)] of one block's compared tensors."""
+    e = lambda k: rel_err(got[k].reshape(ref[k].shape), ref[k])
+    return [("block_out", what + " out", e("out")), ("block_dx", what + " dx", e("dx")), ("block_dw", what + " dW", e("dw")),
+            ("block_dparam", what + " dgamma", e("dgamma")), ("block_dparam", what + " dbeta", e("dbeta")),
+            ("block_running", what + " running_mean", e("running_mean")), ("block_running", what + " running_var", e("running_var"))]
 
 
 def bn_all(y, gamma, beta, dout, running, dtype, relu=True):
@@ -457,11 +520,14 @@ def measure_yardsticks(verbose=True):
         Y[cls] = max(Y.get(cls, 0.0), e)
 
     f = lambda t: t.float()
-    for cin, cout, geom, B, Wo in CONV_CASES:
+    for case in CONV_CASES + CONV_EDGE_CASES + WGRAD_ONLY_CASES:
+        cin, cout, geom, B, Wo = case
         x, w, dy = conv_case(cin, cout, geom, B, Wo)
-        put("dgrad", rel_err(conv_dgrad(f(dy), f(w), geom, x.shape[2]), conv_dgrad(dy, w, geom, x.shape[2])))
+        if case not in WGRAD_ONLY_CASES:
+            put("dgrad", rel_err(conv_dgrad(f(dy), f(w), geom, x.shape[2]), conv_dgrad(dy, w, geom, x.shape[2])))
         put("wgrad", rel_err(conv_wgrad(f(x), f(dy), geom), conv_wgrad(x, dy, geom)))
-    cases = [bn_case(M, C) + (True,) for M, C in BN_CASES] + [bn0_case(*BN0_CASE) + (False,)]
+    cases = ([bn_case(M, C) + (True,) for M, C in BN_CASES + BN_EDGE_CASES]
+             + [bn0_case(B, T) + (False,) for B, T in [BN0_CASE] + BN0_EDGE_CASES])
     for y, gamma, beta, dout, running, relu in cases:
         a, b = bn_all(y, gamma, beta, dout, running, torch.float32, relu), bn_all(y, gamma, beta, dout, running, torch.float64, relu)
         assert relu is False or torch.equal(a["out"] > 0, b["out"] > 0)
@@ -469,10 +535,19 @@ def measure_yardsticks(verbose=True):
         put("bn_dy", rel_err(a["dy"], b["dy"]))
         put("bn_dparam", max(rel_err(a["dgamma"], b["dgamma"]), rel_err(a["dbeta"], b["dbeta"])))
         put("running", max(rel_err(a["running_mean"], b["running_mean"]), rel_err(a["running_var"], b["running_var"])))
-    for B, W, C, ties in POOL_CASES:
-        x, dy = pool_case(B, W, C, ties=ties)
+    for B, H, W, C, ties in [(B, 1, W, C, ties) for B, W, C, ties in POOL_CASES] + POOL_EDGE_CASES:
+        x, dy = pool_case(B, W, C, ties=ties, H=H)
         idx = pool_argmax(x)
         put("pool_dx", rel_err(pool_backward(x.shape, idx, f(dy)), pool_backward(x.shape, idx, dy)))
+    # one block: the fp32 run's own ReLU decisions replayed into the fp64 backward
+    Y["_block_flips"] = []
+    for case in BLOCK_CASES:
+        inputs = block_case(*case)
+        a = block_all(*inputs, case[2], torch.float32)
+        b = block_all(*inputs, case[2], torch.float64, mask=a["mask"])
+        Y["_block_flips"].append((case, int((a["mask"] != b["mask"]).sum())))
+        for cls, _, e in block_errs(a, b):
+            put(cls, e)
     # whole stack: the fp32 run's own decisions replayed into the fp64 backward
     net = stack_net(bidirectional=True, nhidden=512)
     mel = mel_case(*STACK_CASE)

@@ -1,6 +1,7 @@
 """The hand-written restatement of the conv stack's training forward / backward (tests/encoder_conv_train_ref.py) pinned to
 torch autograd on the CPU, its mutants shown to be detectable at the GPU tests' inputs, the new entry points declared,
-exported and bound, and train_encoder's argument parsing.  No GPU."""
+exported and bound, and train_encoder's argument parsing; the edge cases off the layer shapes (autograd pins, the yardstick
+that must not rise, the mutants only they can see, the weight-gradient planner's sweep).  No GPU."""
 import os
 import re
 
@@ -14,7 +15,7 @@ import encoder_train_ref as TR
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NEW_SYMBOLS = ["s2i_conv1d_dgrad", "s2i_conv1d_wgrad_workspace_bytes", "s2i_conv1d_wgrad", "s2i_bn_relu_forward",
-               "s2i_bn_relu_bwd_reduce", "s2i_bn_relu_bwd_apply", "s2i_maxpool_w3s2_backward", "s2i_bn1_finalize",
+               "s2i_bn_relu_bwd_reduce", "s2i_bn_relu_bwd_apply", "s2i_maxpool_w3s2_backward", "s2i_bn1_stats", "s2i_bn1_finalize",
                "s2i_bn1_bwd_reduce", "s2i_bn1_bwd_finalize"]
 
 _CACHE = {}
@@ -182,6 +183,150 @@ def test_stack_mutants_differ():
     _, cache_b = R.stack_forward(layers, mel, "biased_var")
     a, b = R.running_state(layers, cache), R.running_state(layers, cache_b)
     assert max(R.rel_err(b[n], a[n]) for n in a if n.endswith("running_var")) > 10 * B["running"]
+
+
+# ---- off the layer shapes ---------------------------------------------------------------------------------------------------
+EDGE_GEOMS = R.CONV_EDGE_CASES + R.WGRAD_ONLY_CASES
+
+
+@pytest.mark.parametrize("case", EDGE_GEOMS, ids=lambda c: str(c).replace(" ", ""))
+def test_edge_restatements_equal_autograd(case):
+    cin, cout, geom, B, Wo = case
+    k, s, pad = geom
+    x, w, dy = R.conv_case(*case)
+    assert x.shape[2] == Wo * s and (x.shape[2] + 2 * pad - k) // s + 1 == Wo
+    xt = x.permute(0, 3, 1, 2).clone().requires_grad_(True)
+    wt = w.unsqueeze(2).clone().requires_grad_(True)
+    y = torch.nn.functional.conv2d(xt, wt, None, stride=(1, s), padding=(0, pad))
+    assert y.shape[3] == Wo
+    gx, gw = torch.autograd.grad(y, [xt, wt], dy.permute(0, 3, 1, 2))
+    assert R.rel_err(R.conv_dgrad(dy, w, geom, x.shape[2]), gx.permute(0, 2, 3, 1)) < 1e-12
+    assert R.rel_err(R.conv_wgrad(x, dy, geom), gw) < 1e-12
+
+
+def yardsticks():
+    if "yard" not in _CACHE:
+        _CACHE["yard"] = R.measure_yardsticks(verbose=False)
+    return _CACHE["yard"]
+
+
+def as_written(value, bound):
+    """`value` rounded to the number of significant digits `bound` is written with (BOUNDS holds two or three)."""
+    digits = next(d for d in range(1, 17) if float("%.*e" % (d - 1, bound)) == bound)
+    return float("%.*e" % (digits - 1, value))
+
+
+def test_no_yardstick_rises_above_half_its_bound():
+    """The bounds are twice the yardsticks, so over the old and the new cases no class may exceed BOUND / 2.  BOUNDS is
+    written to two or three digits, rounded to nearest (2 x 6.22e-7 is 1.24e-6), so the comparison is made at the bound's
+    own written precision; the block_* classes, new with the edge cases, are held to the exact statement."""
+    B = gpu_bounds()
+    Y = {k: v for k, v in yardsticks().items() if not k.startswith("_")}
+    for k, v in sorted(Y.items()):
+        print("%-18s %.3e" % (k, v))
+    assert set(B) <= set(Y)
+    bad = ["%s 2 x %.3e > %.3e" % (k, Y[k], B[k]) for k in B if not as_written(2 * Y[k], B[k]) <= B[k]]
+    assert not bad, "; ".join(bad)
+    for k in ("block_out", "block_running", "block_dx", "block_dw", "block_dparam"):
+        assert Y[k] <= B[k] / 2, k
+
+
+def test_fp32_block_restatement_flips_no_relu_decision():
+    flips = yardsticks()["_block_flips"]
+    assert [c for c, _ in flips] == R.BLOCK_CASES
+    assert all(n == 0 for _, n in flips), flips
+
+
+@pytest.mark.parametrize("mutant", sorted(R.MUTANT_KILLS))
+def test_edge_mutants_are_inert_on_the_layer_cases_and_rejected_on_the_edge_cases(mutant):
+    """The fp32 restatement stands in for the GPU: a kernel with this mistake would return bit-identical results at every
+    old case (the gap) and leaves BOUNDS at the edge cases (how the gap is closed)."""
+    B = gpu_bounds()
+    f = lambda t: t.float()
+    wgrad = mutant == "col_tail_zero"
+    cls = "wgrad" if wgrad else "dgrad"
+
+    def run(case, m, dtype=torch.float32):
+        x, w, dy = (t.to(dtype) for t in R.conv_case(*case))
+        return R.conv_wgrad(x, dy, case[2], m) if wgrad else R.conv_dgrad(dy, w, case[2], x.shape[2], m)
+
+    for case in R.CONV_CASES:
+        assert torch.equal(run(case, mutant), run(case, None)), case
+    killed = []
+    for case in R.CONV_EDGE_CASES + (R.WGRAD_ONLY_CASES if wgrad else []):
+        if R.rel_err(run(case, mutant), run(case, None, torch.float64)) > B[cls]:
+            killed.append(case)
+    print(mutant, "rejected at", killed)
+    assert R.MUTANT_KILLS[mutant] in killed
+    # and against the fp64 truth the mutant itself is far outside: what the GPU test asserts of the GPU's result
+    case = R.MUTANT_KILLS[mutant]
+    assert R.rel_err(run(case, None), run(case, mutant, torch.float64)) > 10 * B[cls]
+
+
+def wgrad_tiles(cin, cout, k):
+    """Blocks of one split under the documented tile choice: 128 x 128, 128 x 64 (Cin <= 64) or 64 x 64 (Cout <= 64)."""
+    bm, bn = (128, 128) if (cout > 64 and cin > 64) else ((128, 64) if cout > 64 else (64, 64))
+    return -(-cout // bm) * -(-cin // bn) * k
+
+
+def test_wgrad_planner_sweep():
+    from speech_to_image_translation_without_text_amd import _lib
+    lib = _lib.load()
+    geoms = sorted(set([g for g in R.LAYER_GEOMS] + [c[:3] for c in EDGE_GEOMS]))
+    widths = sorted(set(v for g in geoms for v in g[:2]))
+    combos = set(geoms) | set((ci, co, g[2]) for g in geoms for ci in widths for co in widths
+                              if (ci, co) in ((g[0], g[1]), (4, 1024), (1024, 4), (68, 36)))
+    n = 0
+    for cin, cout, (k, s, pad) in sorted(combos):
+        for B in (1, 3, 33, 64):
+            for Wo in (1, 8, 16, 32, 2048):
+                W = Wo * s
+                assert (W + 2 * pad - k) // s + 1 == Wo
+                nbytes = lib.s2i_conv1d_wgrad_workspace_bytes(B, W, cin, cout, k, s, pad)
+                slab = cout * k * cin * 4
+                what = (cin, cout, k, s, pad, B, Wo)
+                if max(B * Wo * cout, B * W * cin) * 4 >= 0x7ff00000:       # past the 2 GiB buffer-addressing window
+                    assert nbytes == 0, what
+                    continue
+                assert nbytes > 0 and nbytes % slab == 0, what
+                splits = nbytes // slab
+                nchunks = -(-B * Wo // 32)
+                lo = -(-nchunks // 16)
+                hi = max(1, lo, min(768 // wgrad_tiles(cin, cout, k), nchunks // 4))
+                assert lo <= splits <= hi, (what, splits, lo, hi)
+                n += 1
+    assert n >= 20 * len(geoms)
+    # every clause of the guard
+    ok = (3, 16, 64, 64, 3, 1, 1)
+    assert lib.s2i_conv1d_wgrad_workspace_bytes(*ok) == 64 * 3 * 64 * 4
+    refused = {"B = 0": (0, 16, 64, 64, 3, 1, 1), "W = 0": (3, 0, 64, 64, 3, 1, 1), "W = 48": (3, 48, 64, 64, 3, 1, 1),
+               "Cin = 0": (3, 16, 0, 64, 3, 1, 1), "Cin = 6": (3, 16, 6, 64, 3, 1, 1), "Cout = 0": (3, 16, 64, 0, 3, 1, 1),
+               "Cout = 34": (3, 16, 64, 34, 3, 1, 1), "kw = 0": (3, 16, 64, 64, 0, 1, 0), "kw = 32": (3, 16, 64, 64, 32, 1, 16),
+               "stride 0": (3, 16, 64, 64, 3, 0, 1), "pad -1": (3, 16, 64, 64, 3, 1, -1), "Wo = 14": (3, 16, 64, 64, 3, 1, 0),
+               "Wo = 0": (3, 2, 64, 64, 5, 1, 0), "dy over 2 GiB": (4096, 2048, 4, 64, 1, 1, 0),
+               "x over 2 GiB": (4096, 2048, 64, 4, 1, 1, 0)}
+    for why, args in refused.items():
+        assert lib.s2i_conv1d_wgrad_workspace_bytes(*args) == 0, why
+        assert b"conv1d wgrad" in lib.s2i_last_error(), why
+
+
+def test_dgrad_guard_is_narrower_than_wgrads():
+    """the two weight-gradient-only cases stay weight-gradient tests; the input gradient refuses them before
+    it touches a pointer (no device here: the pointers are never followed)."""
+    from speech_to_image_translation_without_text_amd import _lib
+    lib = _lib.load()
+    for cin, cout, (k, s, pad), B, Wo in R.WGRAD_ONLY_CASES:
+        assert lib.s2i_conv1d_wgrad_workspace_bytes(B, Wo * s, cin, cout, k, s, pad) > 0
+        assert lib.s2i_conv1d_dgrad(1, 1, 1, B, Wo * s, cin, cout, cin, cout, k, s, pad, None) != 0
+        assert b"conv1d dgrad" in lib.s2i_last_error()
+
+
+def test_bn1_stats_refuses_bad_arguments():
+    from speech_to_image_translation_without_text_amd import _lib
+    lib = _lib.load()
+    for args in ((None, 8, 1, 1), (1, 8, None, 1), (1, 0, 1, 1), (1, 6, 1, 1), (1, 8, 1, 0)):
+        assert lib.s2i_bn1_stats(*args, None) != 0, args
+        assert b"bn1_stats" in lib.s2i_last_error()
 
 
 # ---- the C surface and the CLI ---------------------------------------------------------------------------------------------
