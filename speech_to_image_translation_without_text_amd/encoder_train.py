@@ -21,7 +21,11 @@ the reference's DistributedDataParallel run: the flat parameters and the BatchNo
 construction, every step sums the whole flat gradient buffer over the ranks in one torch.distributed.all_reduce between
 backward and the optimiser launch, and 1 / world_size is folded into that launch.  The loss and the train-mode BatchNorm
 statistics stay per rank, as under DDP; rank 0's running statistics are the ones a checkpoint keeps.
+
+state_dict() / load_state_dict() carry the whole training state (weights, Adam moments and step counts in torch.optim.Adam's
+own state_dict form for either optimiser, the epoch and the learning rate): a fresh trainer that loads it continues bit for bit.
 """
+import copy
 import warnings
 
 import numpy as np
@@ -125,7 +129,8 @@ class HeadTrainer:
             self.flat.lr *= self.gamma
 
     def skip_epochs(self, n):
-        """Advance the schedule over n finished epochs (a resumed run; the Adam moments start afresh)."""
+        """Advance the schedule over n finished epochs (a resumed run; the Adam moments start afresh unless the checkpoint
+        carries them: load_state_dict)."""
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", UserWarning)    # StepLR stepped before the first optimiser step
             for _ in range(int(n)):
@@ -149,6 +154,50 @@ class HeadTrainer:
             image.append(torch.as_tensor(image_feature).float().cpu().numpy())
             labels.append(torch.as_tensor(label).cpu().numpy())
         return retrieval.eval_class(np.concatenate(audio), np.concatenate(image), np.concatenate(labels))
+
+    def state_dict(self):
+        """The whole training state on the CPU: the model's state_dict, `epoch` (finished epochs), `steps`, the current
+        `lr`, and `optimizer`, which is always a torch.optim.Adam.state_dict() over the trained parameters in _trained()
+        order -- torch's own, or with fused_adam the flat moments and step count in that form
+        (train_state.flat_to_adam_state) -- so a state written by either kind of trainer loads into the other, and into the
+        reference's resume_model."""
+        from . import train_state
+        if self.flat is None:
+            opt = train_state.to_cpu(self.optimizer.state_dict())
+        else:
+            f = self.flat
+            opt = train_state.flat_to_adam_state(f.m.cpu(), f.v.cpu(), f.step_count, [tuple(p.shape) for p in f.params],
+                                                 f.offsets, f.lr, f.betas, f.eps, f.weight_decay)
+        return {"state_dict": {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
+                "epoch": int(self.epoch), "steps": int(self.steps), "lr": float(self.lr), "optimizer": opt}
+
+    def load_state_dict(self, state):
+        """Inverse of state_dict(), in place: with fused_adam the parameters stay views of the flat buffer.  The learning
+        rate is the state's own, not StepLR's rule replayed."""
+        from . import train_state
+        self.model.load_state_dict(state["state_dict"])
+        self.epoch, self.steps = int(state["epoch"]), int(state["steps"])
+        lr = float(state["lr"])
+        if self.flat is None:
+            # a copy: torch keeps the `step` tensors it is handed and increments them in place
+            self.optimizer.load_state_dict(copy.deepcopy(state["optimizer"]))
+            for group, base in zip(self.optimizer.param_groups, self.scheduler.base_lrs):
+                group["lr"] = lr
+                group.setdefault("initial_lr", base)
+            sch = self.scheduler
+            sch.last_epoch, sch._step_count, sch._last_lr = self.epoch, self.epoch + 1, [lr] * len(self.optimizer.param_groups)
+        else:
+            f = self.flat
+            m, v, step = train_state.adam_state_to_flat(state["optimizer"], f.sizes, f.offsets, f.total)
+            with torch.no_grad():
+                f.m.copy_(m)
+                f.v.copy_(v)
+            f.step_count = step
+            f.step_dev.fill_(step)
+            f.lr = lr
+            ops.refresh_packed(f.params)
+            ops.invalidate_derived(f.params)
+        self._stale()
 
     def save(self, path, epoch):
         """The reference's checkpoint layout (Audio_to_Image/trainer.py save_checkpoint), read by

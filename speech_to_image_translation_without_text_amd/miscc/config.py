@@ -48,6 +48,8 @@ def _defaults():
             "COEFF": {"KL": 2.0, "CAL_LOSS": 0.0, "UNCOND_LOSS": 0.0, "COLOR_LOSS": 0.0},
             "LOG_INTERVAL": 10,
             "INCEPTION_WEIGHTS": "",   # local Inception-v3 state_dict file: '' = no IS / FID / NLPP during training
+            "STATE": "",               # Model/state.pt of an earlier run: continue it exactly (trainer.load_state)
+            "STATE_EVERY": 0,          # write Model/state.pt every this many epochs and after the last; 0 = never
         },
         "GAN": {"EMBEDDING_DIM": 128, "DF_DIM": 64, "GF_DIM": 64, "Z_DIM": 100,
                 "NETWORK_TYPE": "default", "R_NUM": 2, "B_CONDITION": True},

@@ -10,7 +10,7 @@ epoch), the per-epoch and evaluation lines and the checkpoints (`epoch_<n>.pth`,
 extract_audio_feature --model) are train_encoder_head's.  --model is optional: without it the encoder is
 CNNRNN(40, 1024, nhidden=1024, nsent=1024, bidirectional=...) built under torch.manual_seed(--seed), which is how the
 reference initialises it.  --seed (default 1234) also seeds `random` (utterance / view draws, batch order).
---fused_adam, --resume and --distributed are train_encoder_head's too (its docstring has the details): the reference's
+--fused_adam, --resume, --state_every and --distributed are train_encoder_head's too (its docstring has the details): the reference's
 own way to run this training, run_audio_encoder.sh, is data-parallel, and here that is
 
     python -m torch.distributed.run --nproc-per-node 8 -m speech_to_image_translation_without_text_amd.train_encoder \

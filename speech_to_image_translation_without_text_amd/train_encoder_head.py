@@ -14,9 +14,17 @@ splits' log-mel rows in device memory (speech_loader.ResidentSpeechSet): the sam
 
 --fused_adam keeps the trained parameters in one flat buffer and steps them with one fused Adam launch
 (encoder_train.py).  --resume PATH loads a checkpoint this CLI wrote and continues at its `meta.epoch` + 1 with the learning
-rate StepLR has reached by then; the Adam moments start afresh (the reference's checkpoints carry none either).  It stands
-in for --model, and `best.pth` becomes the best of the resumed run alone: a checkpoint does not record the accuracy it
-was saved at.
+rate StepLR has reached by then; the Adam moments start afresh unless the checkpoint carries them (the reference's layout
+has an `optimizer` field for them; `epoch_<n>.pth`, `latest.pth` and `best.pth` leave it out).  It stands in for --model, and
+`best.pth` becomes the best of the resumed run alone unless the checkpoint records the accuracy it was saved at.
+--state_every N writes the checkpoint that carries both: every N-th epoch and after the last, rank 0 atomically replaces
+`<output_dir>/state.pth` with `meta` {epoch, best_accu}, `state_dict`, `optimizer` (always a torch.optim.Adam.state_dict()
+over the trained parameters, also under --fused_adam) and `rng`, the state of every rank's `random` (train_state.py).
+--resume state.pth restores all of it -- moments, step counts, the learning rate, `best` and each rank's draws -- so the
+epochs that follow are, bit for bit, those of a run that was never stopped.  The state is taken behind an epoch's
+scheduled evaluation (--eval_every) and in front of the closing evaluation of a run's last epoch, which a longer run would
+not have made: neither that evaluation's draws nor its accuracy enter the state.  A state written by another number of
+ranks is refused.
 --distributed trains data-parallel, one process per GPU, as the reference's run_audio_encoder.sh does under
 torch.distributed.launch:
 
@@ -150,13 +158,19 @@ def get_parser(description="fine-tune the speech encoder's LSTM head (conv stack
     p.add_argument("--dist_backend", type=str, default="nccl", help="torch.distributed backend of --distributed")
     p.add_argument("--resume", type=str, default="",
                    help="checkpoint of this CLI to continue from, at its epoch + 1 (it stands in for --model; best.pth is "
-                        "the best of the resumed run alone)")
+                        "the best of the resumed run alone unless the file is a --state_every state.pth, which is "
+                        "continued exactly)")
+    p.add_argument("--state_every", type=int, default=0,
+                   help="every this many epochs and after the last, replace <output_dir>/state.pth with the full training "
+                        "state (weights, Adam moments, learning rate, best accuracy, every rank's `random`); 0 = never")
     return p
 
 
 def check_args(args):
     if args.batch_size < 1 or args.epoch < 1 or args.eval_every < 1:
         raise SystemExit("--batch_size, --epoch and --eval_every must be >= 1")
+    if args.state_every < 0:
+        raise SystemExit("--state_every must be >= 0")
 
 
 def trainer_kwargs(args):
@@ -210,6 +224,36 @@ def resume_epoch(path):
     return int(ckpt["meta"]["epoch"])
 
 
+def write_state(trainer, path, epoch, best, distributed):
+    """`path` replaced atomically by the full state behind `epoch` finished epochs (module docstring).  Every rank calls
+    it: the `random` states are gathered; rank 0 writes."""
+    from . import train_state
+    rng = train_state.gather(random.getstate(), distributed)
+    if distributed and torch.distributed.get_rank() != 0:
+        return
+    st = trainer.state_dict()
+    train_state.atomic_save({"format": train_state.FORMAT, "meta": {"epoch": int(epoch), "best_accu": float(best)},
+                             "state_dict": st["state_dict"], "optimizer": st["optimizer"], "rng": rng}, path)
+
+
+def resume_state(trainer, ckpt, path, rank, world):
+    """Continue from a checkpoint with an `optimizer` field -> (first epoch, best accuracy so far).  The learning rate is
+    the one the optimizer state records and the step count its parameters'; a file without `rng` or `best_accu` (the
+    reference's own save_checkpoint writes neither) keeps this run's seeding and starts `best` anew."""
+    from . import train_state
+    if "format" in ckpt:
+        train_state.check_format(ckpt, path)
+    rng = train_state.rank_entry(ckpt["rng"], rank, world, path) if "rng" in ckpt else None     # refused before any change
+    opt, meta = ckpt["optimizer"], ckpt.get("meta", {})
+    steps = max([int(e["step"]) for e in opt["state"].values()] or [0])
+    epoch = int(meta.get("epoch", 0))
+    trainer.load_state_dict({"state_dict": ckpt["state_dict"], "epoch": epoch, "steps": steps,
+                             "lr": opt["param_groups"][0]["lr"], "optimizer": opt})
+    if rng is not None:
+        random.setstate(train_state.as_tuple(rng))
+    return epoch + 1, float(meta.get("best_accu", -1.0))
+
+
 def train_and_close(make_trainer, args):
     """main() of both CLIs behind the parser: device (and process group), model and trainer, `run`, and the process
     group's end."""
@@ -236,10 +280,29 @@ def run(trainer, args, dev):
     if rank == 0:
         os.makedirs(args.output_dir, exist_ok=True)
     first = 1
-    if args.resume:
-        first = resume_epoch(args.resume) + 1
-        trainer.skip_epochs(first - 1)
     best = -1.0        # of THIS run: a resumed run does not know the accuracy behind an earlier best.pth and replaces it
+    if args.resume:
+        ckpt = torch.load(args.resume, map_location="cpu", weights_only=True)
+        if isinstance(ckpt, dict) and "optimizer" in ckpt:
+            first, best = resume_state(trainer, ckpt, args.resume, rank, world)     # ... unless the state records it
+        else:
+            first = resume_epoch(args.resume) + 1
+            trainer.skip_epochs(first - 1)
+        del ckpt
+
+    def evaluate(epoch, best):
+        if rank == 0:
+            accu, ap50 = trainer.evaluate(test.batches(args.batch_size, dev, shuffle=False))
+            path = os.path.join(args.output_dir, "epoch_%d.pth" % epoch)
+            trainer.save(path, epoch)
+            shutil.copyfile(path, os.path.join(args.output_dir, "latest.pth"))
+            if accu > best:
+                best = accu
+                shutil.copyfile(path, os.path.join(args.output_dir, "best.pth"))
+            print(json.dumps({"epoch": epoch, "test_accu": accu, "test_ap50": ap50, "best_accu": best}))
+        if args.distributed:
+            torch.distributed.barrier()
+        return best
     for epoch in range(first, args.epoch + 1):
         total, seen = None, 0
         order = None
@@ -255,18 +318,13 @@ def run(trainer, args, dev):
         trainer.end_epoch()
         mean_loss, mean_accu = (total / seen).tolist()
         say("epoch %d: loss %.4f, batch accu %.2f" % (epoch, mean_loss, mean_accu))
-        if epoch % args.eval_every == 0 or epoch == args.epoch:
-            if rank == 0:
-                accu, ap50 = trainer.evaluate(test.batches(args.batch_size, dev, shuffle=False))
-                path = os.path.join(args.output_dir, "epoch_%d.pth" % epoch)
-                trainer.save(path, epoch)
-                shutil.copyfile(path, os.path.join(args.output_dir, "latest.pth"))
-                if accu > best:
-                    best = accu
-                    shutil.copyfile(path, os.path.join(args.output_dir, "best.pth"))
-                print(json.dumps({"epoch": epoch, "test_accu": accu, "test_ap50": ap50, "best_accu": best}))
-            if args.distributed:
-                torch.distributed.barrier()
+        scheduled, last = epoch % args.eval_every == 0, epoch == args.epoch
+        if scheduled:
+            best = evaluate(epoch, best)
+        if args.state_every > 0 and (epoch % args.state_every == 0 or last):
+            write_state(trainer, os.path.join(args.output_dir, "state.pth"), epoch, best, args.distributed)
+        if last and not scheduled:
+            best = evaluate(epoch, best)        # the closing evaluation: behind the state, which a longer run continues
     if args.distributed:
         print("rank %d of %d: %d steps" % (rank, world, trainer.steps), flush=True)
     return best

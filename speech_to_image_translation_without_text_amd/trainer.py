@@ -20,6 +20,8 @@ with >= 500 collected batches reports the Inception score, NLPP and FID (trainer
 also writes the reference's image grids (trainer.py:268-295, 589-601): Image/real_samples.png and
 Image/count_<count>_fake_samples<i>.png, from the EMA generator on a noise batch fixed for the run, composed on the device
 (ops.image_grid_uint8); TRAIN.VIS_COUNT = 0 turns them off.  The TensorBoard calls of the reference loop are not reproduced.
+Beyond the reference: TRAIN.STATE_EVERY writes Model/state.pt, the full training state, at epoch boundaries, and TRAIN.STATE
+continues from one bit for bit (save_state / load_state, train_state.py); both are off by default.
 """
 import json
 import os
@@ -264,6 +266,48 @@ class FlatNet:
 
     def avg_params(self):
         return [self.avg[o:o + n].view_as(p) for p, o, n in zip(self.params, self.offsets, self.sizes)]
+
+    def state_dict(self):
+        """Clones of the parameters, both Adam moments and the EMA copy (if kept), the step count and learning rate, and
+        the layout (`sizes`, `offsets`) that load_state_dict checks.  The gradient buffer is not state: every update
+        zeroes it first."""
+        sd = {"p": self.p.detach().clone(), "m": self.m.clone(), "v": self.v.clone(), "step_count": int(self.step_count),
+              "lr": float(self.lr), "sizes": list(self.sizes), "offsets": list(self.offsets)}
+        if self.avg is not None:
+            sd["avg"] = self.avg.clone()
+        return sd
+
+    def load_state_dict(self, sd):
+        """Copy a state_dict() into the existing buffers in place: the flat buffers and every parameter view keep their
+        addresses, which a recorded plan or graph and avg_params() hold.  The device-side step counter follows, and every
+        packed, bf16 or split-plane copy of the old weights is re-derived."""
+        sizes = [int(n) for n in sd["sizes"]]
+        if sizes != self.sizes:
+            names = {id(p): n for n, p in self.net.named_parameters()} if self.net is not None else {}
+            for k in range(max(len(sizes), len(self.sizes))):
+                have = self.sizes[k] if k < len(self.sizes) else None
+                got = sizes[k] if k < len(sizes) else None
+                if have != got:
+                    name = names.get(id(self.params[k]), "") if k < len(self.params) else ""
+                    raise ValueError("FlatNet.load_state_dict: tensor %d%s has %s elements here and %s in the state "
+                                     "(%d tensors here, %d there)" % (k, " (%s)" % name if name else "", have, got,
+                                                                      len(self.sizes), len(sizes)))
+        if ("avg" in sd) != (self.avg is not None):
+            raise ValueError("FlatNet.load_state_dict: the state %s an EMA copy and this network %s"
+                             % (("has", "keeps none") if "avg" in sd else ("has no", "keeps one")))
+        pairs = [(self.p, sd["p"]), (self.m, sd["m"]), (self.v, sd["v"])] + ([(self.avg, sd["avg"])] if "avg" in sd else [])
+        for dst, src in pairs:
+            if src.shape != dst.shape or src.dtype != dst.dtype:
+                raise ValueError("FlatNet.load_state_dict: a buffer of %s %s for one of %s %s"
+                                 % (tuple(src.shape), src.dtype, tuple(dst.shape), dst.dtype))
+        with torch.no_grad():
+            for dst, src in pairs:
+                dst.copy_(src)
+        self.step_count = int(sd["step_count"])
+        self.step_dev.fill_(self.step_count)
+        self.lr = float(sd["lr"])
+        ops.refresh_packed(self.params)
+        ops.invalidate_derived(self.params)
 
 
 class _LegacyOptimizer:
@@ -951,9 +995,13 @@ class condGANTrainer(object):
         dev = torch.device('cuda', self.gpus[0])
         nz = cfg.GAN.Z_DIM
         noise = torch.empty(self.batch_size, nz, device=dev)
-        self.draw_fixed_noise(dev)
-        count = start_count
-        start_epoch = start_count // max(self.num_batches, 1)
+        if cfg.TRAIN.STATE:
+            start_epoch, count = self.load_state(cfg.TRAIN.STATE)    # before any recording of the step
+        else:
+            self.draw_fixed_noise(dev)
+            count = start_count
+            start_epoch = start_count // max(self.num_batches, 1)
+        state_every = int(cfg.TRAIN.STATE_EVERY)
         errD_total = errG_total = kl_loss = None
         for epoch in range(start_epoch, self.max_epoch):
             start_t = time.time()
@@ -974,6 +1022,8 @@ class condGANTrainer(object):
                 print('[%d/%d][%d] Loss_D: %.2f Loss_G: %.2f Loss_KL: %.2f Time: %.2fs'
                       % (epoch, self.max_epoch, self.num_batches, errD_total.item(), errG_total.item(),
                          kl_loss.item(), time.time() - start_t))
+            if state_every > 0 and ((epoch + 1) % state_every == 0 or epoch + 1 == self.max_epoch):
+                self.save_state(os.path.join(self.model_dir, 'state.pt'), epoch + 1, count)
         self.save(count)
 
     def save(self, count):
@@ -990,6 +1040,69 @@ class condGANTrainer(object):
         save_model(self.netG, self.avg_param_G, self.netsD, count, self.model_dir)
         self.flatG.p.copy_(live)
         ops.refresh_packed(self.flatG.params)
+
+    # -- full training state: an exact resume at an epoch boundary (train_state.py) ------------------
+    def save_state(self, path, epoch, count):
+        """Everything the next epoch depends on, in one file that rank 0 replaces atomically: the FlatNet state of G and of
+        every D (live weights, both Adam moments, G's EMA copy, step counts, learning rates), every BatchNorm buffer, the
+        snapshot grids' fixed_noise / fixed_eps, `epoch` (finished epochs) and `count`, every rank's generator states
+        (gathered: every rank must call this), and world size, batch size and math mode, which load_state checks.
+        Not saved: the Inception rows collected since the last metrics record (a resumed run's next record covers the
+        batches since the resume) and a recorded plan or graph (the resumed run records its own)."""
+        from . import train_state
+        dev = torch.device('cuda', self.gpus[0])
+        rng = train_state.gather(train_state.capture_rng(dev), self.distributed)
+        if self.distributed and torch.distributed.get_rank() != 0:
+            return
+        nets = [self.netG] + list(self.netsD)
+        state = {"format": train_state.FORMAT, "kind": "condGANTrainer", "epoch": int(epoch), "count": int(count),
+                 "world": int(self.world), "batch_size": int(self.batch_size), "act_bf16": bool(ops.ACT_BF16),
+                 "math_planes": int(ops.MATH_PLANES),
+                 "flats": [train_state.to_cpu(f.state_dict()) for f in [self.flatG] + self.flatsD],
+                 "buffers": [{k: b.detach().cpu() for k, b in _unwrap(n).named_buffers()} for n in nets],
+                 "fixed_noise": None if self.fixed_noise is None else self.fixed_noise.cpu(),
+                 "fixed_eps": None if self.fixed_eps is None else self.fixed_eps.cpu(), "rng": rng}
+        train_state.atomic_save(state, path)
+
+    def load_state(self, path):
+        """Inverse of save_state, into the networks build() made -> (epoch, count).  The flat buffers are written in place,
+        so it may follow build() at any time before the step is recorded; train() calls it there when TRAIN.STATE is set.
+        Refused: a state of another world size (the per-rank generator states do not map), batch size, math mode or
+        network layout.  With data parallelism every rank reads the file; rank r restores generator state r, and every
+        rank gets rank 0's BatchNorm buffers, as a checkpoint keeps them (the others' never reach an output)."""
+        from . import train_state
+        state = train_state.load(path)
+        if state.get("kind") != "condGANTrainer":
+            raise ValueError("%s is not a condGANTrainer state (kind %r)" % (path, state.get("kind")))
+        rank = torch.distributed.get_rank() if self.distributed else 0
+        rng = train_state.rank_entry(state["rng"], rank, self.world, path)
+        if int(state["world"]) != self.world:
+            raise ValueError("%s was written by %d rank(s) and cannot be resumed by %d" % (path, state["world"], self.world))
+        if int(state["batch_size"]) != self.batch_size:
+            raise ValueError("%s was written at batch size %d; this run has %d" % (path, state["batch_size"], self.batch_size))
+        mode, here = (bool(state["act_bf16"]), int(state["math_planes"])), (bool(ops.ACT_BF16), int(ops.MATH_PLANES))
+        if mode != here:
+            raise ValueError("%s was written with (ACT_BF16, MATH_PLANES) = %s; this run has %s" % (path, mode, here))
+        flats, nets = [self.flatG] + self.flatsD, [self.netG] + list(self.netsD)
+        if len(state["flats"]) != len(flats):
+            raise ValueError("%s holds %d networks; this run has %d" % (path, len(state["flats"]), len(flats)))
+        for k, (f, sd) in enumerate(zip(flats, state["flats"])):       # every layout first: nothing is half loaded
+            if [int(n) for n in sd["sizes"]] != f.sizes or ("avg" in sd) != (f.avg is not None):
+                raise ValueError("%s: network %d has another parameter layout than this run's" % (path, k))
+        for f, sd in zip(flats, state["flats"]):
+            f.load_state_dict(sd)
+        with torch.no_grad():
+            for n, saved in zip(nets, state["buffers"]):
+                mine = dict(_unwrap(n).named_buffers())
+                if set(mine) != set(saved):
+                    raise ValueError("%s: buffers %s do not match this network's" % (path, sorted(set(mine) ^ set(saved))))
+                for k, b in mine.items():
+                    b.copy_(saved[k])
+        dev = self.flatG.p.device
+        self.fixed_noise = None if state["fixed_noise"] is None else state["fixed_noise"].to(dev)
+        self.fixed_eps = None if state["fixed_eps"] is None else state["fixed_eps"].to(dev)
+        train_state.restore_rng(rng, dev)      # last: nothing above may draw after it
+        return int(state["epoch"]), int(state["count"])
 
     # -- evaluation (trainer.py:664-679, 681-825): the PNGs, and with TRAIN.INCEPTION_WEIGHTS set the IS / FID / NLPP that
     # the reference computes only after its early return (gan_metrics.GeneratorScorer)
