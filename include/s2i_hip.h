@@ -680,6 +680,39 @@ int s2i_logmel_finish(const float* melpow, const unsigned* maxbits, const int* l
 int s2i_logmel_gather(const float* pool, const long long* row_offsets, const int* frames, int B, int T, float* out,
                       void* stream);
 
+/* ---- any WAV -> 16 kHz mono fp32 (Audio_to_Image/utils.py:313, librosa.load(path, 16000)) ---------------------------
+ * Decode, mixdown and band-limited resampling (resampy's kaiser_best, which librosa.load of the reference's era calls) of
+ * one group of clips that share (rate, sample format, channel count), in one launch, in front of the log-mel entries.
+ * With g = gcd(16000, rate): L = 16000 / g, M = rate / g, scale = min(1, L / M), W = ceil(64 / scale), taps = 2 W + 2 and
+ *   table[p][j] = scale h(scale (W - j + p / L)),  h(t) = r sinc(r t) I0(beta sqrt(1 - (t / 64)^2)) / I0(beta) on |t| <= 64,
+ * r = 0.9475937167399596, beta = 14.769656459379492, built in float64 and rounded to fp32 once by the caller.  Output m of
+ * a clip of n frames: q = (m M) div L, p = (m M) mod L (64-bit), y[m] = sum_j x[q - W + j] table[p][j] with x = 0 outside
+ * [0, n); n_out = ceil(n L / M) outputs, those with m >= floor(n L / M) are 0.0f.  rate 16000 is L = M = 1, W = 0, table
+ * [1, 0].  Decode (little-endian, interleaved): u8 (v - 128) / 128; s16 / s24 / s32 float(v) 2^-(bits - 1); f32 as is; f64
+ * rounded to fp32.  Mono: channels added in channel order in fp32, then a correctly rounded division by float(channels).
+ * Decode, then mono, then resample. */
+#define S2I_PCM_U8   0
+#define S2I_PCM_S16  1
+#define S2I_PCM_S24  2
+#define S2I_PCM_S32  3
+#define S2I_PCM_F32  4
+#define S2I_PCM_F64  5
+#define S2I_RESAMPLE_TILE        1024   /* outputs per entry of the tile table                                        */
+#define S2I_RESAMPLE_MAX_WINDOW  13826  /* 12 * 1024 + 2 * 768 + 2 floats of LDS: a tile's input window at 192 kHz     */
+/* raw: the byte buffer (16-byte aligned); clip b's `data` bytes start at raw + byte_offsets[b], a multiple of 16, and
+   hold in_frames[b] frames of `channels` samples of `format`.  table is the device table in the layout
+   [L][tpad], tpad = taps rounded up to a multiple of 4, pad zero (each phase's row 16-byte aligned; the pad is not
+   read).  tiles [ntiles][2] holds (clip, first output index) for every 1024 outputs of every clip with out_lens > 0.
+   Clip b's out_lens[b] = ceil(in_frames[b] L / M) outputs go to out + out_offsets[b]; every one of them is written and
+   nothing else is.  Refused before any launch: null pointers, B < 1, an unknown format, channels outside [1, 8], L / M
+   that is not the reduced ratio of 16000 to a rate in [4000, 192000] (L in [1, 16000], L / 4 <= M <= 12 L, gcd 1), W
+   outside [0, 768] or a table over 2^24 floats, a tile window over S2I_RESAMPLE_MAX_WINDOW, raw, table or out off a
+   16-byte boundary.  W is otherwise the caller's (the section's value for a real rate; tests pass others with their own
+   tables).  One launch, dynamic LDS only; no atomics, no workspace, no synchronisation. */
+int s2i_pcm_resample(const void* raw, const long long* byte_offsets, const int* in_frames, int B, int format,
+                     int channels, int L, int M, int W, const float* table, const int* tiles, int ntiles, float* out,
+                     const long long* out_offsets, const int* out_lens, void* stream);
+
 /* ---- streaming feature moments for the Frechet distance (StackGAN_v2/trainer.py:103-144) -----------------------------
  * compute_frethet_distance fits a Gaussian to each set of Inception pool3 rows with np.mean and np.cov.  Both follow
  * from the row count, the column sums and the Gram matrix X^T X, which add up exactly across chunks of rows, so the

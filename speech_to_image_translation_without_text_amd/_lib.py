@@ -22,6 +22,9 @@ POOL_THEN_LRN, LRN_THEN_POOL = 0, 1
 LOGMEL_BFT, LOGMEL_NHWC = 0, 1
 ENC_LOSS_JEL, ENC_LOSS_L1, ENC_LOSS_DISTILL = 1, 2, 4
 LOGMEL_TILE_FRAMES = 64
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = 0, 1, 2, 3, 4, 5
+RESAMPLE_TILE = 1024
+RESAMPLE_MAX_WINDOW = 13826
 ABI_VERSION = 4
 
 c_int, c_float, c_void_p, c_size_t, c_ll = (ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
@@ -179,6 +182,7 @@ _SIGNATURES = {
     "s2i_logmel_power": (c_int, [P, P, P, c_int, P, P, P, P, P, c_int, c_int, P, P, P]),
     "s2i_logmel_finish": (c_int, [P, P, P, c_int, c_int, c_int, P, P]),
     "s2i_logmel_gather": (c_int, [P, P, P, c_int, c_int, P, P]),
+    "s2i_pcm_resample": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, P, P]),
     "s2i_moments_accumulate": (c_int, [P, c_int, c_int, c_ll, P, P, P]),
 }
 

@@ -7,7 +7,8 @@ datasets.py trains and evaluates on (Audio_to_Image/extract_audio_feature.py:25-
 For each split (train, test) it reads `<data_dir>/<split>.json`, takes `audio_base_path` + each item's `audio` (birds) or
 `wav` (flowers) list, and writes `<data_dir>/<split>/audio_features_<switch>.pickle` (N/10, 10, 1024) float32 and
 `audio_features_lens_<switch>.pickle` (N/10, 10) int64 (the n_frames of each file).  A relative `audio_base_path` is
-taken relative to the working directory, as the reference does.
+taken relative to the working directory, as the reference does.  The files are 16 kHz PCM16; --resample takes any rate
+from 4 to 192 kHz, PCM or float, 1 to 8 channels, as librosa.load(path, 16000) does for the reference (audio.to_16k).
 
 The reference processes files in chunks of 10, in file order: it sorts a chunk by n_frames (descending), replaces the
 shortest item's data and length by the second-shortest's when it has fewer than 64 frames, encodes with
@@ -67,8 +68,12 @@ def load_encoder(path, bidirectional=False, rnn_layers=1, device=None):
     return model.to(device) if device is not None else model
 
 
-def read_wavs(paths, workers=MAX_READERS):
+def read_wavs(paths, workers=MAX_READERS, resample=False):
+    """The files as 16 kHz mono float32 waveforms.  `resample` takes any rate and sample format `audio.read_audio`
+    accepts and converts on the current GPU (`audio.to_16k`: device tensors); without it, `audio.read_wav`'s arrays."""
     with ThreadPoolExecutor(max_workers=max(1, min(MAX_READERS, workers, len(paths)))) as pool:
+        if resample:
+            return audio.to_16k(list(pool.map(audio.read_audio, paths)))
         return list(pool.map(audio.read_wav, paths))
 
 
@@ -104,11 +109,11 @@ def split_files(data_dir, split, dataset):
     return [os.path.join(meta["audio_base_path"], name) for d in meta["data"] for name in d[key]]
 
 
-def extract_split(model, data_dir, split, dataset, audio_switch, batch_size=240):
+def extract_split(model, data_dir, split, dataset, audio_switch, batch_size=240, resample=False):
     files = split_files(data_dir, split, dataset)
     if not files or len(files) % CHUNK:
         raise ValueError("%s split has %d files: need a positive multiple of %d" % (split, len(files), CHUNK))
-    feats, frames = encode_waveforms(model, read_wavs(files), batch_size)
+    feats, frames = encode_waveforms(model, read_wavs(files, resample=resample), batch_size)
     out_dir = os.path.join(data_dir, split)
     datasets.save_embedding_pickle(feats.reshape(-1, CHUNK, feats.shape[1]),
                                    os.path.join(out_dir, "audio_features_%s.pickle" % audio_switch))
@@ -128,6 +133,9 @@ def get_parser():
     p.add_argument("--data_dir", type=str, default=None, help="directory with <split>.json (default ./data/<dataset>)")
     p.add_argument("--batch_size", type=int, default=240, help="utterances per GPU batch (any size)")
     p.add_argument("--splits", type=str, default="train,test")
+    p.add_argument("--resample", action="store_true", default=False,
+                   help="accept WAVs of any rate (4-192 kHz), PCM 8/16/24/32-bit or float 32/64-bit, 1-8 channels: "
+                        "decoded, mixed down and resampled to 16 kHz on the GPU (audio.to_16k)")
     return p
 
 
@@ -139,7 +147,7 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     model = load_encoder(args.model, args.bidirectional, args.rnn_layers, dev)
     for split in args.splits.split(","):
-        feats, _ = extract_split(model, data_dir, split, args.dataset, args.audio_switch, args.batch_size)
+        feats, _ = extract_split(model, data_dir, split, args.dataset, args.audio_switch, args.batch_size, args.resample)
         print("%s: %d utterances -> %s" % (split, len(feats), os.path.join(data_dir, split)))
 
 

@@ -66,11 +66,18 @@ def utterance_paths(split):
     return [[os.path.join(split.audio_base, n) for n in item[split.key]] for item in split.items]
 
 
-def scan_frames(split, workers=MAX_READ_THREADS, target_length=audio.TARGET_LENGTH):
-    """Per item an int64 array of `audio.n_frames` of each utterance, capped at `target_length`, from the WAV headers."""
+def _samples_16k(path):
+    """Samples the file has at 16 kHz, by the integer rule, from its header (any format `audio.probe_audio` accepts)"""
+    info = audio.probe_audio(path)
+    return audio.resampled_length(info.frames, info.rate)
+
+
+def scan_frames(split, workers=MAX_READ_THREADS, target_length=audio.TARGET_LENGTH, resample=False):
+    """Per item an int64 array of `audio.n_frames` of each utterance, capped at `target_length`, from the WAV headers;
+    with `resample`, of each utterance's length at 16 kHz."""
     paths = utterance_paths(split)
     with ThreadPoolExecutor(max_workers=_threads(workers)) as ex:
-        flat = list(ex.map(_samples, [p for item in paths for p in item]))
+        flat = list(ex.map(_samples_16k if resample else _samples, [p for item in paths for p in item]))
     out, k = [], 0
     for item in paths:
         out.append(np.array([audio.n_frames(n, target_length) for n in flat[k:k + len(item)]], dtype=np.int64))
@@ -99,9 +106,10 @@ class ResidentSpeechSet:
     The image features and labels stay on the host, as in SplitData.  `workers` (at most 16) threads read the files,
     `chunk` utterances at a time go through `audio.log_mel`, and only one chunk of waveforms is held on the host."""
 
-    def __init__(self, split, device, workers=16, chunk=256, target_length=audio.TARGET_LENGTH):
+    def __init__(self, split, device, workers=16, chunk=256, target_length=audio.TARGET_LENGTH, resample=False):
         from . import _lib
         self.split = split
+        self.resample = bool(resample)     # files of any accepted rate and format, through audio.to_16k
         self.device = torch.device(device)
         self.T = int(target_length)
         if self.T < MIN_FRAMES:
@@ -111,7 +119,7 @@ class ResidentSpeechSet:
         if self.device.type != "cuda":
             raise _lib.S2IError("the log-mel pool is made and read by the MI355X kernels: there is no CPU fallback (device %s)"
                                 % self.device)
-        self.frames = scan_frames(split, workers, self.T)
+        self.frames = scan_frames(split, workers, self.T, self.resample)
         self.row_offsets, rows = pool_layout(self.frames)
         counts = np.array([len(f) for f in self.frames], dtype=np.int64)
         self.first = np.cumsum(counts) - counts
@@ -127,7 +135,10 @@ class ResidentSpeechSet:
         steps = torch.arange(self.T, device=self.device)
         with ThreadPoolExecutor(max_workers=threads) as ex:
             for s in range(0, len(paths), chunk):
-                waves = list(ex.map(audio.read_wav, paths[s:s + chunk]))
+                if self.resample:
+                    waves = audio.to_16k(list(ex.map(audio.read_audio, paths[s:s + chunk])), self.device)
+                else:
+                    waves = list(ex.map(audio.read_wav, paths[s:s + chunk]))
                 for k, w in enumerate(waves, s):
                     if audio.n_frames(len(w), self.T) != flat[k]:
                         raise ValueError("%s holds %d samples, its header promised %d frames" % (paths[k], len(w), flat[k]))

@@ -7,7 +7,8 @@ Each 16 kHz PCM16 WAV becomes its log-mel (audio.log_mel), its 1024-d sentence e
 utterance per sequence: cap_len = n_frames // 64, so a clip needs at least 64 frames, about 0.65 s), and then G's
 last-stage image, written as `<out_dir>/<wav name>.png`.  G runs in .eval() mode as trainer.evaluate runs it; z and the
 conditioning-augmentation noise are drawn, in that order, from a CPU generator seeded with --seed, so a run is
-reproducible.  --cfg takes the training YAML (G's widths and branch count).
+reproducible.  --cfg takes the training YAML (G's widths and branch count).  --resample takes WAVs of any rate from 4 to
+192 kHz, PCM or float, 1 to 8 channels, and converts them to 16 kHz mono on the GPU first (audio.to_16k).
 
     ... --interpolate 10 a.wav b.wav
 
@@ -95,9 +96,9 @@ def generate(netG, emb, seed):
     return ops.images_to_uint8_hwc(fake_imgs[-1]).cpu().numpy()
 
 
-def main(argv=None):
+def get_parser():
     p = argparse.ArgumentParser(description="speech to image")
-    p.add_argument("wavs", nargs="+", help="16 kHz PCM16 WAV files")
+    p.add_argument("wavs", nargs="+", help="16 kHz PCM16 WAV files (any rate and PCM / float format with --resample)")
     p.add_argument("--model", required=True, help="CNNRNN checkpoint")
     p.add_argument("--netG", required=True, help="generator state_dict (netG_<N>.pth)")
     p.add_argument("--out_dir", required=True)
@@ -107,6 +108,14 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--interpolate", type=int, default=None, metavar="STEPS",
                    help="two WAVs: write the STEPS + 1 images between them (interp_<i>.png, interp_grid.png)")
+    p.add_argument("--resample", action="store_true", default=False,
+                   help="accept WAVs of any rate (4-192 kHz), PCM 8/16/24/32-bit or float 32/64-bit, 1-8 channels: "
+                        "decoded, mixed down and resampled to 16 kHz on the GPU (audio.to_16k)")
+    return p
+
+
+def main(argv=None):
+    p = get_parser()
     args = p.parse_args(argv)
     if args.interpolate is not None:
         if len(args.wavs) != 2:
@@ -117,7 +126,7 @@ def main(argv=None):
         cfg_from_file(args.cfg)
     dev = torch.device("cuda", torch.cuda.current_device())
     model = load_encoder(args.model, args.bidirectional, args.rnn_layers, dev)
-    emb = embed(model, read_wavs(args.wavs))
+    emb = embed(model, read_wavs(args.wavs, resample=args.resample))
     netG = load_generator(args.netG, dev)
     os.makedirs(args.out_dir, exist_ok=True)
     if args.interpolate is not None:

@@ -10,7 +10,9 @@ and a `class`.  Per item and epoch one random utterance with at least 64 frames 
 `random`, as BirdDataset.__getitem__ does.  Every --eval_every epochs (and after the last) the test split is scored with
 retrieval.eval_class and `epoch_<n>.pth`, `latest.pth` and, on a new best test accuracy, `best.pth` are written in the
 reference's checkpoint layout, which extract_audio_feature --model reads.  --resident reads every WAV once and keeps both
-splits' log-mel rows in device memory (speech_loader.ResidentSpeechSet): the same batches, one launch each.
+splits' log-mel rows in device memory (speech_loader.ResidentSpeechSet): the same batches, one launch each.  --resample
+takes WAVs of any rate from 4 to 192 kHz, PCM or float, 1 to 8 channels, converted to 16 kHz mono on the GPU per batch
+(audio.to_16k), also under --resident; without it the files are 16 kHz PCM16 as before.
 
 --fused_adam keeps the trained parameters in one flat buffer and steps them with one fused Adam launch
 (encoder_train.py).  --resume PATH loads a checkpoint this CLI wrote and continues at its `meta.epoch` + 1 with the learning
@@ -58,7 +60,8 @@ MAX_DRAWS = 64
 class SplitData:
     """One split: the JSON's items, the image-feature pickle and the class labels (0-based)."""
 
-    def __init__(self, data_dir, split, dataset):
+    def __init__(self, data_dir, split, dataset, resample=False):
+        self.resample = bool(resample)     # any WAV audio.read_audio accepts, converted by audio.to_16k per batch
         with open(os.path.join(data_dir, "%s.json" % split)) as f:
             meta = json.load(f)
         self.audio_base = meta["audio_base_path"]
@@ -73,11 +76,17 @@ class SplitData:
         return len(self.items)
 
     def draw(self, index):
-        """(image view (1024,), waveform, label): a random view and a random utterance of at least 64 frames."""
+        """(image view (1024,), waveform, label): a random view and a random utterance of at least 64 frames.  With
+        `resample` the waveform is the file's `audio.read_audio` pair, its 16 kHz length taken from the header."""
         views = self.image[index]
         image = views[random.randint(0, len(views) - 1)]
         names = self.items[index][self.key]
         for _ in range(MAX_DRAWS):
+            if self.resample:
+                clip = audio.read_audio(os.path.join(self.audio_base, names[random.randint(0, len(names) - 1)]))
+                if audio.n_frames(audio.resampled_length(clip[0].frames, clip[0].rate)) >= MIN_FRAMES:
+                    return image, clip, self.labels[index]
+                continue
             wave = audio.read_wav(os.path.join(self.audio_base, names[random.randint(0, len(names) - 1)]))
             if audio.n_frames(len(wave)) >= MIN_FRAMES:
                 return image, wave, self.labels[index]
@@ -92,7 +101,10 @@ class SplitData:
                 random.shuffle(order)
         for s in range(0, len(order), batch_size):
             drawn = [self.draw(i) for i in order[s:s + batch_size]]
-            mel, frames = audio.log_mel([w for _, w, _ in drawn], layout="nhwc", device=device)
+            waves = [w for _, w, _ in drawn]
+            if self.resample:
+                waves = audio.to_16k(waves, device)
+            mel, frames = audio.log_mel(waves, layout="nhwc", device=device)
             image = torch.from_numpy(np.stack([v for v, _, _ in drawn])).float()
             yield mel, (frames // MIN_FRAMES).tolist(), image, torch.tensor([c for _, _, c in drawn], dtype=torch.int64)
 
@@ -150,6 +162,9 @@ def get_parser(description="fine-tune the speech encoder's LSTM head (conv stack
     p.add_argument("--seed", type=int, default=seed, help="seed of `random` (utterance / view draws, batch order)")
     p.add_argument("--resident", action="store_true", default=False,
                    help="keep both splits' log-mel rows in device memory (speech_loader.ResidentSpeechSet)")
+    p.add_argument("--resample", action="store_true", default=False,
+                   help="accept WAVs of any rate (4-192 kHz), PCM 8/16/24/32-bit or float 32/64-bit, 1-8 channels: "
+                        "decoded, mixed down and resampled to 16 kHz on the GPU (audio.to_16k)")
     p.add_argument("--resident_workers", type=int, default=16, help="threads that read the WAV files for --resident")
     p.add_argument("--fused_adam", action="store_true", default=False,
                    help="flat parameter storage and one fused Adam launch per step (encoder_train.py)")
@@ -180,11 +195,11 @@ def trainer_kwargs(args):
                 lambda_distill=args.lambda_distill, fused_adam=args.fused_adam, distributed=args.distributed)
 
 
-def make_resident(split, name, dev, workers, say=print):
+def make_resident(split, name, dev, workers, say=print, resample=False):
     """`split` behind a speech_loader.ResidentSpeechSet, with one line about the pool."""
     from .speech_loader import ResidentSpeechSet
     t0 = time.perf_counter()
-    resident = ResidentSpeechSet(split, dev, workers=workers)
+    resident = ResidentSpeechSet(split, dev, workers=workers, resample=resample)
     torch.cuda.synchronize(dev)
     say("resident %s: %d utterances, %d rows, %d bytes, %.2f s" % (name, len(resident.row_offsets), resident.pool.shape[0],
                                                                   resident.nbytes, time.perf_counter() - t0))
@@ -273,9 +288,9 @@ def run(trainer, args, dev):
     data_dir = args.data_dir or os.path.join(".", "data", args.dataset)
     # the test split is rank 0's alone: the other ranks never evaluate, and with --resident would fill a pool they never read
     names = ("train", "test") if rank == 0 else ("train",)
-    splits = [SplitData(data_dir, name, args.dataset) for name in names]
+    splits = [SplitData(data_dir, name, args.dataset, resample=args.resample) for name in names]
     if args.resident:
-        splits = [make_resident(s, name, dev, args.resident_workers, say) for s, name in zip(splits, names)]
+        splits = [make_resident(s, name, dev, args.resident_workers, say, args.resample) for s, name in zip(splits, names)]
     train, test = splits[0], (splits[1] if rank == 0 else None)
     if rank == 0:
         os.makedirs(args.output_dir, exist_ok=True)
