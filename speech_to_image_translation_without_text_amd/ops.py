@@ -1236,6 +1236,16 @@ def _new(shape, device, dtype=torch.float32):
     return torch.full(shape, LSTM_SENTINEL, dtype=dtype, device=device)
 
 
+def _step_rows(t, B, L):
+    """[B, 1, L, C] or [B, L, C] as the 1x1 matrix kernels take it.  They tile spatial extents that are powers of two, and a
+    1x1 product sees nothing but rows, so any other L goes in as B * L images of one pixel: the same rows, the same plan
+    (it depends on the row count alone).  A power of two keeps its [B, 1, L, C] form."""
+    C = t.shape[-1]
+    if L & (L - 1):
+        return t.view(B * L, 1, 1, C)
+    return t.view(B, 1, L, C)
+
+
 def lstm_params(rnn):
     """The parameters of a one-layer nn.LSTM in the order LstmSentence takes them."""
     if rnn.num_layers != 1 or not rnn.batch_first or getattr(rnn, "proj_size", 0):
@@ -1275,7 +1285,8 @@ class LstmSentence(torch.autograd.Function):
             # [1][Hd][4*Hd]: the operand of the recurrent matrix product and, read as a matrix, W_hh transposed
             w_hh = [pack_weight(params[4 * d + 1], PACK_PLAIN) for d in range(D)]
             raw = [params[4 * d + 1].detach().contiguous() for d in range(D)]
-        xproj, _, _ = conv_raw(CONV_K1, x, None, w_ih, G4, wR=w_ih.shape[1], ldw=w_ih.shape[2], bias=b)  # [B, 1, L, D*4H]
+        xproj, _, _ = conv_raw(CONV_K1, _step_rows(x, B, L), None, w_ih, G4, wR=w_ih.shape[1], ldw=w_ih.shape[2],
+                               bias=b)                                  # [B, 1, L, D*4H]
         out = _new((B, L, D * Hd), dev)
         gates = torch.empty((B, L, G4), dtype=torch.float32, device=dev)
         cst = torch.empty((B, L, D * Hd), dtype=torch.float32, device=dev)
@@ -1347,17 +1358,18 @@ class LstmSentence(torch.autograd.Function):
                                                ldw=w_hh[d].shape[2])
         need = ctx.needs_input_grad
         grads = [None] * (2 + 4 * D)
-        dG4 = dG.view(B, 1, L, G4)
+        dG4 = _step_rows(dG, B, L)
         if need[0]:     # the seam: the gradient for the conv stack's output
-            grads[0], _, _ = conv_raw(CONV_K1, dG4, None, w_ih, E, wmode=1, wR=w_ih.shape[1], ldw=w_ih.shape[2])
+            dx, _, _ = conv_raw(CONV_K1, dG4, None, w_ih, E, wmode=1, wR=w_ih.shape[1], ldw=w_ih.shape[2])
+            grads[0] = dx.view(B, 1, L, E)
         if any(need[2 + 4 * d] for d in range(D)):
-            dw_ih = wgrad_raw(CONV_K1, x, None, dG4, (G4, E))
+            dw_ih = wgrad_raw(CONV_K1, _step_rows(x, B, L), None, dG4, (G4, E))
             for d in range(D):
                 if need[2 + 4 * d]:
                     grads[2 + 4 * d] = dw_ih[d * 4 * Hd:(d + 1) * 4 * Hd]
         for d in range(D):
             if need[3 + 4 * d]:
-                grads[3 + 4 * d] = wgrad_raw(CONV_K1, hprev[d].view(B, 1, L, Hd), None, dG4, (4 * Hd, Hd),
+                grads[3 + 4 * d] = wgrad_raw(CONV_K1, _step_rows(hprev[d], B, L), None, dG4, (4 * Hd, Hd),
                                              g_cols=(d * 4 * Hd, 4 * Hd))
         if any(need[4 + 4 * d] or need[5 + 4 * d] for d in range(D)):
             db_all = torch.empty((G4,), dtype=torch.float32, device=dev)

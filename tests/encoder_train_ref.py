@@ -213,3 +213,114 @@ def train_steps(params, batches, dtype, lr=1e-3, weight_decay=1e-5, **loss_args)
         opt.step()
         losses.append(res["loss"].detach())
     return torch.stack(losses), [p.detach() for p in params]
+
+
+# ---- edge cases of the fused step kernels, the two-kernel path and the loss (tests/test_encoder_head_edges_*.py) -----------------
+def fused_path(B, Hd):
+    """The rule ops.LstmSentence takes the one-launch step kernels by."""
+    return B <= 32 and Hd % 8 == 0 and Hd <= 512
+
+
+def edge_lens(pattern, B, L, seed=0):
+    """B lengths in [1, L]: "std" = case_lens (sorted descending, L twice); "full" = all L; "ones" = all 1; "unsorted" =
+    seeded draws with slot 0 set to 1 and the last slot set to L; "short" = seeded, unsorted, nothing above L - 2, the
+    longest not in slot 0."""
+    if pattern == "std":
+        return case_lens(B, L, seed)
+    if pattern == "full":
+        return [L] * B
+    if pattern == "ones":
+        return [1] * B
+    g = torch.Generator().manual_seed(90 + seed)
+    if pattern == "unsorted":
+        lens = torch.randint(1, L + 1, (B,), generator=g).tolist()
+        lens[0], lens[-1] = 1, L
+        return lens
+    if pattern == "short":
+        if L < 4 or B < 3:
+            raise ValueError("short lens need L >= 4 and B >= 3")
+        lens = torch.randint(1, L - 1, (B,), generator=g).tolist()
+        lens[0], lens[B // 2], lens[-1] = max(1, (L - 2) // 2), L - 2, 1
+        return lens
+    raise ValueError("unknown lens pattern %r" % (pattern,))
+
+
+# ((B, L, E, Hd, D), lens pattern, the path ops.LstmSentence takes at its defaults)
+EDGE_HEAD_CASES = [
+    ((32, 6, 32, 512, 2), "std", "fused"),          # production Hd, all 32 slots, both kernels above 64 KB of LDS
+    ((31, 6, 32, 512, 1), "unsorted", "fused"),     # one empty slot, one direction, the longest sequence last
+    ((32, 6, 32, 512, 2), "full", "fused"),         # no padded column anywhere
+    ((5, 6, 32, 408, 1), "std", "fused"),           # backward LDS 65 920 bytes: just over 64 KB
+    ((5, 6, 32, 400, 2), "std", "fused"),           # 64 640 bytes: just under
+    ((17, 5, 32, 256, 2), "unsorted", "fused"),     # forward LDS 66 560 bytes: just over, odd B
+    ((6, 8, 32, 64, 2), "short", "fused"),          # max(lens) < L
+    ((1, 4, 32, 8, 1), "full", "fused"),            # B = 1, one block per direction
+    ((32, 1, 32, 8, 2), "ones", "fused"),           # L = 1: the first backward launch is the only one
+    ((9, 7, 32, 8, 2), "ones", "fused"),            # one step, six padded columns per sequence
+    ((4, 6, 32, 12, 2), "std", "two-kernel"),       # Hd % 8 != 0; the bias gradient sees N = 96
+    ((3, 6, 32, 520, 1), "std", "two-kernel"),      # the first Hd the fused limit refuses
+    ((33, 8, 32, 16, 2), "short", "two-kernel"),    # B = 33 with max(lens) < L
+    ((33, 6, 32, 512, 2), "unsorted", "two-kernel"),  # production Hd through the other path
+]
+EDGE_MUTANT_CASES = [EDGE_HEAD_CASES[6], EDGE_HEAD_CASES[12]]
+
+
+def edge_case_id(entry):
+    return "B%d_L%d_E%d_H%d_D%d" % entry[0] + "_" + entry[1]
+
+
+def fwd_step_lds_bytes(Hd):
+    """Dynamic LDS of the fused forward step: h [32][Hd + 4] and the W_hh slice [32][Hd + 4], fp32."""
+    return 2 * 32 * (Hd + 4) * 4
+
+
+def bwd_step_lds_bytes(Hd):
+    """Dynamic LDS of the fused backward step: a dG chunk [32][Hd + 4] and the transposed W_hh slice [8][Hd + 4], fp32."""
+    return 40 * (Hd + 4) * 4
+
+
+EDGE_LOSS_SHAPES = [(257, 40), (300, 4), (37, 1000), (5, 63), (2, 8)]
+HOT_LOSS_FLAGS = {
+    "T2": dict(jel=False, distill=True, distill_T=2),
+    "T3": dict(jel=False, distill=True, distill_T=3, lambda_distill=0.4),
+}
+
+
+def label_case(kind):
+    """loss_case(12, 96) with its labels replaced: "one_class" = all zero (every pair is a same-class pair), "distinct" =
+    arange(12) (none is)."""
+    audio, image, _ = loss_case(12, 96)
+    label = torch.zeros(12, dtype=torch.long) if kind == "one_class" else torch.arange(12)
+    return audio, image, label
+
+
+def hinge_margin(audio, image, label):
+    """(smallest |hinge argument| off the diagonal, smallest gap between a score row's two largest entries)."""
+    _, _, score, score_abs, same = jel_loss(audio.double(), image.double(), label, 1, 1)
+    off = ~torch.eye(len(label), dtype=torch.bool)
+    hinge = torch.where(same, score_abs, score_abs + 1)
+    top2 = score.topk(2, dim=1)[0]
+    return float(hinge[off].abs().min()), float((top2[:, 0] - top2[:, 1]).min())
+
+
+def single_row_case(C=40, seed=0):
+    """B = 1: one embedding pair, one label."""
+    g = torch.Generator().manual_seed(7900 + seed)
+    audio = torch.randn(1, C, generator=g, dtype=torch.float64) * (1.5 / C ** 0.5)
+    image = torch.randn(1, C, generator=g, dtype=torch.float64) * (1.5 / C ** 0.5) + 0.5 * audio
+    return audio, image, torch.zeros(1, dtype=torch.long)
+
+
+def hot_loss_case(B=37, C=1000, seed=0):
+    """Logits near 100 (audio) and 200 (image): exp of either overflows fp32 unless the row maximum is subtracted first.
+    Both are rounded to fp32, so that the fp64 reference and an fp32 kernel start from the same numbers."""
+    g = torch.Generator().manual_seed(7950 + seed)
+    audio = (100 + 3 * torch.randn(B, C, generator=g, dtype=torch.float64)).float().double()
+    image = (200 + 6 * torch.randn(B, C, generator=g, dtype=torch.float64)).float().double()
+    label = torch.randint(0, B // 3, (B,), generator=g)
+    return audio, image, label
+
+
+def hits(accu, B):
+    """The hit count behind an accuracy in percent (100 * hits / B rounds differently in fp32 and fp64)."""
+    return int(round(float(accu) * B / 100))
