@@ -3,11 +3,24 @@
 // libs2i_hip_diag.so (`make diag`, -DS2I_DIAG): this code allocates, synchronises and copies, which the product
 // library (include/s2i_hip.h: "nothing here allocates, frees or synchronises") never does.
 // Knobs (s2i_set_tuning): b16_dbg = DBG value; the timeline of a DBG-32 launch is written to the path in $S2I_B16_TIMELINE.
+// This part is shared: s2i_bf16_conv_diag.inc and s2i_bf16_conv_v2_diag.inc hold the instantiations of their kernel.
 #include <stdlib.h>
 #include <vector>
 
-static int diag_timeline_dump(unsigned long long* dbuf, size_t nblk, hipStream_t st) {
-  const size_t bytes = nblk * 64 * sizeof(unsigned long long);
+// launches a DBG instantiation; timeline (DBG 32): its p.slab points at 64 stamps per block, which are then dumped
+template <class Kernel>
+static void diag_launch(Kernel kernel, int lds_max, int threads, size_t shb, ConvBP p, dim3 grid, hipStream_t st, bool timeline,
+                        int* rc) {
+  const size_t nblk = (size_t)grid.x * grid.y * grid.z, bytes = nblk * 64 * sizeof(unsigned long long);
+  unsigned long long* dbuf = nullptr;
+  if (timeline) {
+    if (hipMalloc((void**)&dbuf, bytes) != hipSuccess) { s2i_set_error("conv(bf16): timeline buffer"); *rc = 1; return; }
+    (void)hipMemsetAsync(dbuf, 0, bytes, st);
+    p.slab = reinterpret_cast<float*>(dbuf);
+  }
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), shb, st, p);
+  if (!timeline) return;
   (void)hipStreamSynchronize(st);
   const char* path = getenv("S2I_B16_TIMELINE");
   if (path) {
@@ -17,50 +30,4 @@ static int diag_timeline_dump(unsigned long long* dbuf, size_t nblk, hipStream_t
     if (f) { fwrite(h.data(), 1, bytes, f); fclose(f); }
   }
   (void)hipFree(dbuf);
-  return 0;
-}
-
-// returns true when it launched (or failed: *rc != 0), false to fall through to the production dispatch
-static bool diag_launch_conv_bf16(const BPlan& pl, const ConvBP& p, dim3 grid, hipStream_t st, int* rc) {
-  const int kb = pl.kb, bn = pl.BN, ck = pl.CK, tg = pl.TG;
-  *rc = 0;
-  if (!p.dbg) return false;
-  if (pl.v2 && p.dbg == 32 && kb == KB_K4S2 && p.splitk == 1) {
-    grid.x = v2_grid_x(pl);
-    const size_t nblk = (size_t)grid.x * grid.y * grid.z, bytes = nblk * 64 * sizeof(unsigned long long);
-    unsigned long long* dbuf = nullptr;
-    if (hipMalloc((void**)&dbuf, bytes) != hipSuccess) { s2i_set_error("conv(bf16): timeline buffer"); *rc = 1; return true; }
-    (void)hipMemsetAsync(dbuf, 0, bytes, st);
-    ConvBP q = p;
-    q.slab = reinterpret_cast<float*>(dbuf);
-    if (v2_padded(pl)) {
-      (void)hipFuncSetAttribute((const void*)conv_bf16_v2_kernel<KB_K4S2, 32, 4, false, 32, 66>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((conv_bf16_v2_kernel<KB_K4S2, 32, 4, false, 32, 66>), grid, dim3(512), bf16_smem_bytes(pl), st, q);
-    } else {
-      (void)hipFuncSetAttribute((const void*)conv_bf16_v2_kernel<KB_K4S2, 32, 4, false, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((conv_bf16_v2_kernel<KB_K4S2, 32, 4, false, 32>), grid, dim3(512), bf16_smem_bytes(pl), st, q);
-    }
-    diag_timeline_dump(dbuf, nblk, st);
-    return true;
-  }
-  if (pl.v2) return false;
-  if (kb == KB_K4S2 && bn == 128 && ck == 16 && tg == 8) {
-    const size_t shb = bf16_smem_bytes(pl);
-#define S2I_DBG(v) if (p.dbg == v) { (void)hipFuncSetAttribute((const void*)conv_bf16_kernel<KB_K4S2, 128, 16, 8, v>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); hipLaunchKernelGGL((conv_bf16_kernel<KB_K4S2, 128, 16, 8, v>), grid, dim3(256), shb, st, p); return true; }
-    S2I_DBG(1) S2I_DBG(2) S2I_DBG(4) S2I_DBG(7) S2I_DBG(8) S2I_DBG(15) S2I_DBG(16) S2I_DBG(31) S2I_DBG(24)
-#undef S2I_DBG
-  }
-  if (p.dbg == 32 && kb == KB_K4S2 && bn == 128 && ck == 32 && tg == 4 && p.splitk == 1) {
-    const size_t nblk = (size_t)grid.x * grid.y * grid.z, bytes = nblk * 64 * sizeof(unsigned long long);
-    unsigned long long* dbuf = nullptr;
-    if (hipMalloc((void**)&dbuf, bytes) != hipSuccess) { s2i_set_error("conv(bf16): timeline buffer"); *rc = 1; return true; }
-    (void)hipMemsetAsync(dbuf, 0, bytes, st);
-    ConvBP q = p;
-    q.slab = reinterpret_cast<float*>(dbuf);
-    (void)hipFuncSetAttribute((const void*)conv_bf16_kernel<KB_K4S2, 128, 32, 4, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    hipLaunchKernelGGL((conv_bf16_kernel<KB_K4S2, 128, 32, 4, 32>), grid, dim3(256), bf16_smem_bytes(pl), st, q);
-    diag_timeline_dump(dbuf, nblk, st);
-    return true;
-  }
-  return false;
 }

@@ -335,7 +335,7 @@ def _bf16_plan(rec, lib, M, nph, Ho, Wo):
     assert parts > 0 and parts % nph == 0, parts
     grid_m = parts // nph
     ck = lib.s2i_conv_bf16_weight_layout(ctypes.byref(d)) & 0xff
-    # pixels per tile: the tile is as wide as the map (up to 32), then rows, then images (plan_bf16); the tile count tells
+    # pixels per tile: the tile is as wide as the map (up to 32), then rows, then images (tile_geom of s2i_bf16_plan.hip); the tile count tells
     # 128 from 256 pixels, and where both give the same count the channel chunk does (16 / 32 against 32 / 64)
     cand = {}
     for bm in (128, 256):
@@ -352,7 +352,7 @@ def _bf16_plan(rec, lib, M, nph, Ho, Wo):
     reach = set()
     if B % tb:
         reach.add("b16-ragged-%d" % bm)
-    # restated from v2_grid_x: the persistent form is the stride-2 256-pixel kernel, unsplit, on b16_persist block slots
+    # restated from v2_grid_x (s2i_bf16_conv_v2.hip): the persistent form is the stride-2 256-pixel kernel, unsplit, on b16_persist block slots
     persist = rec.get("tune", {}).get("b16_persist", 1)
     if bm == 256 and kind == ops.CONV_K4S2 and sk == 1 and persist > 1:
         nblk = max(persist // _cdiv(N, 128), 1)

@@ -1,4 +1,4 @@
-// Ceiling probes for the matrix loops of s2i_igemm.h (mma_chunk) / s2i_bf16.hip (dev tool, GPU box):
+// Ceiling probes for the matrix loops of s2i_igemm.h (mma_chunk) / s2i_bf16_conv.hip (dev tool, GPU box):
 //   reg  : v_mfma with both operands in registers (no LDS, no memory): the instruction's own rate under this clock;
 //   lds  : the same MFMA stream with every fragment re-read from LDS (the access pattern of mma_chunk / conv_bf16_kernel,
 //          conflict-free), no global traffic and no barriers: the ceiling of an LDS-fed loop;
