@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define S2I_ABI_VERSION 4
+#define S2I_ABI_VERSION 5
 
 /* conv geometry kinds */
 #define S2I_CONV_K1      0  /* 1x1 / nn.Linear (model.py:179, 217)                              */
@@ -232,6 +232,13 @@ int s2i_conv_forward_dt(const s2i_conv_desc* d, const void* x, int x_dtype, cons
                         const float* bias, const float* cls_bias, void* y, int y_dtype, float* part, void* ws,
                         size_t ws_bytes, void* stream);
 size_t s2i_wgrad_workspace_bytes_dt(const s2i_wgrad_desc* d, int a_dtype, int g_dtype);
+/* What a weight gradient of this descriptor launches (host only; tools and the plan tests).  The operands are those of the
+   entry point that would run it: a_dtype / g_dtype as for s2i_conv_wgrad_dt, planes as for s2i_conv_wgrad_split (0 = none),
+   in_act != 0 for s2i_conv_wgrad_in.  out = { kernel id (WgKernel of csrc/s2i_igemm.h), K rows and N columns of the result per
+   block, threads per block, grid x / y / z, pixels per stage of the reduction loop, slabs the launch writes, slabs the workspace
+   holds (what the s2i_wgrad_workspace_bytes* queries size, never fewer), K, M }.  Non-zero, with out zeroed, where the plan
+   refuses the layer in this mode. */
+int s2i_wgrad_plan_query(const s2i_wgrad_desc* d, int a_dtype, int g_dtype, int planes, int in_act, int out[12]);
 int s2i_conv_wgrad_dt(const s2i_wgrad_desc* d, const void* a, int a_dtype, const float* cvec, const void* g,
                       int g_dtype, float* grad_oihw, void* ws, size_t ws_bytes, void* stream);
 /* `_dt` forms of the BatchNorm / activation / layout kernels below: every activation tensor of the call has `dtype`; they

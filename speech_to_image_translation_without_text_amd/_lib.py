@@ -25,7 +25,13 @@ LOGMEL_TILE_FRAMES = 64
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = 0, 1, 2, 3, 4, 5
 RESAMPLE_TILE = 1024
 RESAMPLE_MAX_WINDOW = 13826
-ABI_VERSION = 4
+ABI_VERSION = 5
+# s2i_wgrad_plan_query: the WgKernel values of csrc/s2i_igemm.h in order, and the twelve outputs
+WGRAD_KERNELS = ("f32-128x128", "f32-128x64", "f32-128x32", "f32-64x64", "f32-256x128", "f32-256x256", "f32-96x64", "f32-96x32",
+                 "f32in-128x128", "b16-128x128", "b16-128x64", "b16-128x32", "b16-64x64", "b16-256x128", "b16-256x256",
+                 "b16d1-64x64", "split-128x128", "split-128x64", "split-128x32", "split-64x64", "rows3-32x64", "rows3-32x32",
+                 "rows3-64x128", "rows3-64x64", "rows3-64x32", "smalln-16", "smalln-32", "smalln-64")
+WGRAD_PLAN_FIELDS = ("kernel", "bm", "bn", "threads", "gx", "gy", "gz", "stage", "slabs", "ws_slabs", "K", "M")
 
 c_int, c_float, c_void_p, c_size_t, c_ll = (ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
                                             ctypes.c_size_t, ctypes.c_longlong)
@@ -88,6 +94,7 @@ _SIGNATURES = {
     "s2i_conv_forward_dt": (c_int, [ctypes.POINTER(ConvDesc), P, c_int, P, P, P, P, P, c_int, P, P, c_size_t, P]),
     "s2i_wgrad_workspace_bytes_dt": (c_size_t, [ctypes.POINTER(WgradDesc), c_int, c_int]),
     "s2i_conv_wgrad_dt": (c_int, [ctypes.POINTER(WgradDesc), P, c_int, P, P, c_int, P, P, c_size_t, P]),
+    "s2i_wgrad_plan_query": (c_int, [ctypes.POINTER(WgradDesc), c_int, c_int, c_int, c_int, ctypes.POINTER(c_int * 12)]),
     "s2i_bn_act_forward_dt": (c_int, [c_int, P, c_ll, c_int, c_int, P, c_int, P, P, P]),
     "s2i_bn_act_bwd_reduce_dt": (c_int, [c_int, P, P, c_int, c_ll, c_int, c_int, P, c_int, P, c_int, P]),
     "s2i_bn_act_bwd_apply_dt": (c_int, [c_int, P, P, c_int, c_ll, c_int, c_int, P, P, c_int, P, P]),
@@ -245,6 +252,17 @@ class tuning:
         for k, v in self.old.items():
             check(lib.s2i_set_tuning(k.encode(), v), "s2i_set_tuning")
         return False
+
+
+def wgrad_plan(d, a_dtype=DT_F32, g_dtype=DT_F32, planes=0, in_act=0):
+    """What the weight gradient of WgradDesc d launches in this operand mode (s2i_wgrad_plan_query, host only): a dict of
+    WGRAD_PLAN_FIELDS with the kernel as its WGRAD_KERNELS name, or None where the plan refuses (s2i_last_error says why)."""
+    out = (c_int * 12)()
+    if load().s2i_wgrad_plan_query(ctypes.byref(d), a_dtype, g_dtype, planes, in_act, ctypes.byref(out)):
+        return None
+    plan = dict(zip(WGRAD_PLAN_FIELDS, out))
+    plan["kernel"] = WGRAD_KERNELS[plan["kernel"]]
+    return plan
 
 
 def require_device():

@@ -164,7 +164,6 @@ inline int bf16_raise_lds(const void* kernel, int bytes, bool* raised) {
 // s2i_bf16_plan.hip.  v2_padded: the 66-pixel-wide stride-2 patch takes the padded-row instantiation; bf16_patch_bytes: one
 // patch buffer in LDS; bf16_smem_bytes: the dynamic LDS of the planned kernel
 int plan_bf16(const s2i_conv_desc* d, BPlan* pl);
-int bf16_stat_parts(const BPlan& pl, int groups);
 bool v2_padded(const BPlan& pl);
 size_t bf16_patch_bytes(const BPlan& pl);
 size_t bf16_smem_bytes(const BPlan& pl);

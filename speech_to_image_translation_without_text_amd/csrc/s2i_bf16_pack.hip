@@ -218,7 +218,7 @@ int launch_splitk_reduce_bf16(const s2i_conv_desc* d, const BPlan& pl, unsigned 
   int cpb = 1;
   while (cpb < Q && cpb < 256) cpb <<= 1;
   const int groups = d->groups < 1 ? 1 : d->groups;
-  const int nparts = bf16_stat_parts(pl, groups);
+  const int nparts = stat_parts(pl, groups);
   hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3(nparts, (Q + cpb - 1) / cpb), dim3(256), 0, st, ws, pl.splitk, pl.Mrows,
                      d->N, y, d->ldy, d->stats ? part : nullptr, nparts, cpb, nparts / groups, pl.Mrows / groups);
   S2I_LAUNCH_CHECK("splitk_reduce_bf16");

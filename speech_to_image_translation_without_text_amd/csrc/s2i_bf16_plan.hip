@@ -130,17 +130,6 @@ int plan_bf16(const s2i_conv_desc* d, BPlan* pl) {
   return 0;
 }
 
-int bf16_stat_parts(const BPlan& pl, int groups) {
-  if (groups < 1) groups = 1;
-  if (pl.splitk > 1) {
-    int ppg = s2i_cdiv(pl.Mrows / groups, 8);
-    if (ppg > 512 / groups) ppg = 512 / groups;
-    if (ppg < 1) ppg = 1;
-    return ppg * groups;
-  }
-  return pl.gridM * pl.nphases;
-}
-
 // the 66-pixel-wide stride-2 patch (32-column tiles) takes the padded-row instantiation
 bool v2_padded(const BPlan& pl) { return pl.v2 && pl.kb == KB_K4S2 && pl.PW == 66 && pl.CK == 32; }
 
@@ -167,7 +156,7 @@ S2I_BF16_QUERY(int, s2i_conv_bf16_eligible, 0, (pl.v2 || bf16_has_kernel(pl.kb, 
 // layer at another batch size may be planned onto another kernel)
 S2I_BF16_QUERY(int, s2i_conv_bf16_weight_layout, -1, pl.CK | (pl.Npad << 8))
 S2I_BF16_QUERY(size_t, s2i_conv_bf16_workspace_bytes, 0, workspace_bytes(d, pl))
-S2I_BF16_QUERY(int, s2i_conv_bf16_stat_parts, -1, bf16_stat_parts(pl, d->groups))
+S2I_BF16_QUERY(int, s2i_conv_bf16_stat_parts, -1, stat_parts(pl, d->groups))
 S2I_BF16_QUERY(size_t, s2i_conv_bf16_weight_elems, 0, (size_t)pl.nphases * pl.T * pl.Npad * d->Cx)
 #undef S2I_BF16_QUERY
 

@@ -35,6 +35,18 @@ static inline int s2i_ilog2(int v) {
 static inline bool s2i_is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static inline int s2i_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// rows the BatchNorm statistics pass of a forward convolution plan writes (Plan: FwdPlan or BPlan): one per row tile, or,
+// where K is split, the rows of the reduce + stats pass (split-K layers have few output rows: keep that pass wide)
+template <class Plan>
+static inline int stat_parts(const Plan& pl, int groups) {
+  if (groups < 1) groups = 1;
+  if (pl.splitk <= 1) return pl.gridM * pl.nphases;
+  int ppg = s2i_cdiv(pl.Mrows / groups, 8);
+  if (ppg > 512 / groups) ppg = 512 / groups;
+  if (ppg < 1) ppg = 1;
+  return ppg * groups;
+}
+
 // ---- tuning knobs (s2i_set_tuning / S2I_TUNE, parsed once at load; s2i_runtime.hip) ----
 enum {
   S2I_TUNE_FWD_BM = 0,      // fwd_bm: force the tile height of the fp32 matrix kernel (0 = planner)

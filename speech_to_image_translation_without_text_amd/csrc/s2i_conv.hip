@@ -102,35 +102,28 @@ int plan_fwd(const s2i_conv_desc* d, FwdPlan* pl) {
   const int splitk = best_split;
   pl->cps = s2i_cdiv(pl->nchunks, splitk);
   pl->splitk = s2i_cdiv(pl->nchunks, pl->cps);
+  pl->small_n = d->N <= 4 && d->Cc == 0 && !d->stats && (d->kind == S2I_CONV_K3S1 || d->kind == S2I_TCONV_K4S2) &&
+                (pl->Ca == 16 || pl->Ca == 32 || pl->Ca == 64) && pl->M >= 4096;
   return 0;
 }
+
+// bytes of the split-K slabs (0 when K is not split)
+size_t slab_bytes(const FwdPlan& pl, int N) { return pl.splitk > 1 ? (size_t)pl.splitk * pl.Mrows * N * sizeof(float) : 0; }
 
 }  // namespace
 
 extern "C" size_t s2i_conv_workspace_bytes(const s2i_conv_desc* d) {
   FwdPlan pl;
   if (plan_fwd(d, &pl)) return 0;
-  const size_t slab = pl.splitk > 1 ? (size_t)pl.splitk * pl.Mrows * d->N * sizeof(float) : 0;
+  const size_t slab = slab_bytes(pl, d->N);
   const size_t thin = thin_workspace_bytes(d, pl);
   return thin > slab ? thin : slab;
-}
-
-// number of rows the stats pass writes; split-K layers take the column-stats kernel instead
-int stat_parts_for(const FwdPlan& pl, int groups) {
-  if (groups < 1) groups = 1;
-  if (pl.splitk > 1) {
-    int ppg = s2i_cdiv(pl.Mrows / groups, 8);  // split-K layers have few rows: keep the reduce+stats pass wide
-    if (ppg > 512 / groups) ppg = 512 / groups;
-    if (ppg < 1) ppg = 1;
-    return ppg * groups;
-  }
-  return pl.gridM * pl.nphases;
 }
 
 extern "C" int s2i_conv_stat_parts(const s2i_conv_desc* d) {
   FwdPlan pl;
   if (plan_fwd(d, &pl)) return -1;
-  return stat_parts_for(pl, d->groups);
+  return stat_parts(pl, d->groups);
 }
 
 static int conv_forward_impl(const s2i_conv_desc* d, const float* x, const float* cvec, const float* w,
@@ -144,7 +137,7 @@ static int conv_forward_impl(const s2i_conv_desc* d, const float* x, const float
   S2I_REQUIRE(d->Cc == 0 || cvec != nullptr, "conv: cvec is null but Cc > 0");
   S2I_REQUIRE((w || wsp) && y, "conv: null weight/output");
   S2I_REQUIRE(!d->stats || part, "conv: stats requested without a partial buffer");
-  const size_t need = pl.splitk > 1 ? (size_t)pl.splitk * pl.Mrows * d->N * sizeof(float) : 0;
+  const size_t need = slab_bytes(pl, d->N);
   S2I_REQUIRE(ws_bytes >= need && (need == 0 || ws), "conv: workspace too small (%zu < %zu)", ws_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   IgemmP p;
@@ -176,10 +169,7 @@ static int conv_forward_impl(const s2i_conv_desc* d, const float* x, const float
     const int r = launch_thin(d, pl, p, ws, ws_bytes, st);
     if (r >= 0) return r;
   }
-  if (!wsp && d->N <= 4 && d->Cc == 0 && !d->stats && !cls_bias && (d->kind == S2I_CONV_K3S1 || d->kind == S2I_TCONV_K4S2) &&
-      (pl.Ca == 16 || pl.Ca == 32 || pl.Ca == 64) && pl.M >= 4096) {
-    return launch_small_n_conv(d, pl, p, st);
-  }
+  if (pl.small_n && !wsp && !cls_bias) return launch_small_n_conv(d, pl, p, st);
   dim3 grid(pl.gridM, pl.gridN, pl.nphases * pl.splitk);
   const bool wt = d->wmode != 0;
   const int wtaps = d->kind == S2I_TCONV_K4S2 ? 16 : pl.T;
@@ -226,9 +216,7 @@ extern "C" int s2i_conv_forward_in(const s2i_conv_desc* d, const float* x_raw, c
 extern "C" int s2i_conv_split_eligible(const s2i_conv_desc* d) {
   FwdPlan pl;
   if (plan_fwd(d, &pl)) return 0;
-  const bool small_n = d->N <= 4 && d->Cc == 0 && !d->stats && (d->kind == S2I_CONV_K3S1 || d->kind == S2I_TCONV_K4S2) &&
-                       (pl.Ca == 16 || pl.Ca == 32 || pl.Ca == 64) && pl.M >= 4096;
-  return (pl.Ca % 32) == 0 && (d->Cc % 32) == 0 && !small_n;
+  return (pl.Ca % 32) == 0 && (d->Cc % 32) == 0 && !pl.small_n;
 }
 
 extern "C" int s2i_conv_forward_split(const s2i_conv_desc* d, const float* x, const float* cvec,

@@ -739,7 +739,7 @@ int launch_splitk_reduce(const s2i_conv_desc* d, const FwdPlan& pl, const float*
     int cpb = 1;
     while (cpb < Q && cpb < 256) cpb <<= 1;
     const int groups = d->groups < 1 ? 1 : d->groups;
-    const int nparts = stat_parts_for(pl, groups);
+    const int nparts = stat_parts(pl, groups);
     hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3(nparts, (Q + cpb - 1) / cpb), dim3(256), 0, st,
                        (const float*)ws, pl.splitk, pl.Mrows, d->N, y, d->ldy, part, nparts, cpb, nparts / groups,
                        pl.Mrows / groups, y16);
@@ -753,7 +753,7 @@ int launch_splitk_reduce(const s2i_conv_desc* d, const FwdPlan& pl, const float*
                      pl.Mrows, d->N, bias, d->act, y, d->ldy, y16);
   S2I_LAUNCH_CHECK("splitk_reduce");
   S2I_REQUIRE(!(d->stats && y16), "conv: bf16 output with statistics needs N %% 4 == 0 on a split-K layer");
-  if (d->stats) return s2i_colstats(y, pl.Mrows, d->N, d->ldy, part, stat_parts_for(pl, 1), stream);
+  if (d->stats) return s2i_colstats(y, pl.Mrows, d->N, d->ldy, part, stat_parts(pl, 1), stream);
   return 0;
 }
 

@@ -196,17 +196,51 @@ __device__ __forceinline__ void split4(const f32x4 v, u32x2 (&out)[NP]) {
 // ---- host side ---------------------------------------------------------------------------------
 struct FwdPlan {
   int T, K, Ca, Ho, Wo, M, nphases, tile, bm, gridM, gridN, nchunks, splitk, cps;
+  int small_n;   // <= 4 output channels of a 3x3 / transposed layer: small_n_conv_kernel where no thin kernel takes the layer
   long long Mrows;
 };
 
-struct WgPlan {
-  int T, K, Cin, Ho, Wo, M, tile, gridK, gridN, nchunks, splitk, cps, small_n, rows3, bn3;
+// What the operands of a weight gradient are (derived once from the entry point's dtypes, planes and coefficient table)
+enum WgMode {
+  WG_MODE_F32,      // fp32 a and g
+  WG_MODE_F32_IN,   // fp32, a is the producer's raw output activated while it is staged (s2i_conv_wgrad_in)
+  WG_MODE_A16,      // a stored as bf16, g fp32
+  WG_MODE_G16,      // g stored as bf16, a fp32
+  WG_MODE_B16,      // both stored as bf16
+  WG_MODE_SPLIT1, WG_MODE_SPLIT2, WG_MODE_SPLIT3   // fp32 operands split into 1 - 3 bf16 planes while they are staged
 };
+
+// The kernel a planned weight gradient launches: family and K x N tile.  The matrix families list their tile shapes in one
+// order (F32 all eight, B16 the first six, SPLIT the first four), so a family's first value + the shape's index is the kernel.
+// wg_kernels[] (s2i_wgrad_plan.hip) holds each one's tile and block size; s2i_wgrad_plan_query reports these values.
+enum WgKernel {
+  WG_F32_128x128, WG_F32_128x64, WG_F32_128x32, WG_F32_64x64, WG_F32_256x128, WG_F32_256x256, WG_F32_96x64, WG_F32_96x32,
+  WG_F32IN_128x128,                                                       // igemm_wgrad_kernel<..., INACT>
+  WG_B16_128x128, WG_B16_128x64, WG_B16_128x32, WG_B16_64x64, WG_B16_256x128, WG_B16_256x256,   // igemm_wgrad_b16_kernel
+  WG_B16D1_64x64,                                                         // ... with the fp32 NHWC4 image of the first D conv
+  WG_SPLIT_128x128, WG_SPLIT_128x64, WG_SPLIT_128x32, WG_SPLIT_64x64,     // igemm_wgrad_split_kernel<..., planes>
+  WG_ROWS3_32x64, WG_ROWS3_32x32, WG_ROWS3_64x128, WG_ROWS3_64x64, WG_ROWS3_64x32,   // wgrad_k3_rows_kernel<Ca, BN>
+  WG_SMALLN_16, WG_SMALLN_32, WG_SMALLN_64,                               // small_n_wgrad_kernel<Ca / 4>
+  WG_KERNEL_COUNT
+};
+struct WgKernelInfo { int bm, bn, threads; };   // K rows and N columns of the result per block, block size
+
+// Everything a weight-gradient launch needs, decided by plan_wgrad; the launcher takes it as const
+struct WgPlan {
+  int T, K, Cin, Ho, Wo, M;
+  WgKernel kernel;
+  int planes;           // bf16 planes of the SPLIT family (else 0)
+  int threads, gx, gy, gz;
+  int stage;            // pixels per stage of the kernel's reduction loop: 32, or 64 in the B16 families
+  int nchunks, cps;     // stages in the pixel range and stages per split (WgradP::nchunks / cps)
+  int slabs;            // K x N fp32 slabs the launch writes and the finish sums
+  int ws_slabs;         // slabs the workspace holds: the split of the 32-pixel plan, >= slabs
+};
+// bytes of the workspace every s2i_wgrad_workspace_bytes* query reports and the launcher asks for
+static inline size_t wg_workspace_bytes(const WgPlan& pl, int N) { return (size_t)pl.ws_slabs * pl.K * N * sizeof(float); }
 
 // Unit interfaces.  A launch_* function returns 0 after a launch, 1 with the error text set.  None of them is exported.
 #pragma GCC visibility push(hidden)
-// s2i_conv.hip
-int stat_parts_for(const FwdPlan& pl, int groups);
 // s2i_conv_fwd.hip: grid and the byte windows of p come from the dispatcher (conv_forward_impl)
 int launch_igemm_fwd(const FwdPlan& pl, const IgemmP& p, dim3 grid, bool wt, bool ca32, hipStream_t st);
 int launch_igemm_fwd_split(const FwdPlan& pl, const IgemmP& p, dim3 grid, int planes, hipStream_t st);
@@ -217,7 +251,8 @@ int launch_splitk_reduce(const s2i_conv_desc* d, const FwdPlan& pl, const float*
 // takes the layer; thin_workspace_bytes is the largest table / fragment buffer any of them could ask for (0: none applies)
 int launch_thin(const s2i_conv_desc* d, const FwdPlan& pl, IgemmP p, void* ws, size_t ws_bytes, hipStream_t st);
 size_t thin_workspace_bytes(const s2i_conv_desc* d, const FwdPlan& pl);
-// s2i_wgrad_plan.hip: 0, or 1 with the error text set; wgrad_in_ok: the planned layer can take the apply-on-load kernel
-int plan_wgrad(const s2i_wgrad_desc* d, WgPlan* pl, int planes = 0);
-bool wgrad_in_ok(const s2i_wgrad_desc* d, const WgPlan& pl);
+// s2i_wgrad_plan.hip: both return 0, or 1 with the error text set.  wg_mode names the operands of an entry point's
+// arguments; plan_wgrad decides the launch, or refuses a layer that no kernel takes in this mode.
+int wg_mode(int a16, int g16, int planes, bool a_coef, WgMode* mode);
+int plan_wgrad(const s2i_wgrad_desc* d, WgMode mode, WgPlan* pl);
 #pragma GCC visibility pop

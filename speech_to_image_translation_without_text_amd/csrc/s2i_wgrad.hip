@@ -734,16 +734,12 @@ static void launch_wgrad_split(const WgradP& p, dim3 grid, int planes, hipStream
   else hipLaunchKernelGGL((igemm_wgrad_split_kernel<BM, BN, WM, WN, 3>), grid, dim3(256), 0, st, p);
 }
 
-static int conv_wgrad_impl(const s2i_wgrad_desc* d, int planes, const float* a, const float* cvec, const float* g,
-                           float* grad_oihw, void* ws, size_t ws_bytes, void* stream, int a16 = 0, int g16 = 0, const float* a_coef = nullptr) {
-  WgPlan pl;
-  // bf16 operands: the plan of the split modes (no row-segment / 96-row tiles, which stage fp32 rows)
-  if (plan_wgrad(d, &pl, (a16 && g16) ? 16 : ((planes || a16 || g16) ? 1 : 0))) return 1;
-  S2I_REQUIRE(!(planes && (a16 || g16)), "wgrad(split): bf16 tensors go through s2i_conv_wgrad_dt");
-  S2I_REQUIRE(!(pl.small_n && g16), "wgrad: the <= 4 channel gradient stream expects an fp32 output gradient");
+// launches what plan_wgrad decided, then the finish: slab sum and the transpose into OIHW
+static int launch_wgrad(const s2i_wgrad_desc* d, const WgPlan& pl, const float* a, const float* cvec, const float* g,
+                        float* grad_oihw, void* ws, size_t ws_bytes, void* stream, int a16, int g16, const float* a_coef) {
   S2I_REQUIRE((a || d->Ca == 0) && g && grad_oihw, "wgrad: null operand");
   S2I_REQUIRE(d->Cc == 0 || cvec != nullptr, "wgrad: cvec is null but Cc > 0");
-  const size_t need = (size_t)pl.splitk * pl.K * d->N * sizeof(float);
+  const size_t need = wg_workspace_bytes(pl, d->N);
   S2I_REQUIRE(ws && ws_bytes >= need, "wgrad: workspace too small (%zu < %zu)", ws_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   WgradP p;
@@ -754,11 +750,6 @@ static int conv_wgrad_impl(const s2i_wgrad_desc* d, int planes, const float* a, 
   p.cps = pl.cps; p.nchunks = pl.nchunks;
   p.a16 = a16; p.g16 = g16;
   p.a_coef = a_coef; p.a_groups = d->a_groups < 1 ? 1 : d->a_groups; p.a_ipg = d->B / p.a_groups;
-  if (a_coef) {
-    S2I_REQUIRE(!planes && !a16 && !g16 && wgrad_in_ok(d, pl),
-                "wgrad(apply-on-load): fp32 operands, LeakyReLU producer, no broadcast vector, 128 x 128 tile plan (check "
-                "s2i_conv_wgrad_in_eligible)");
-  }
   {
     const unsigned long long ab = (unsigned long long)d->B * d->H * d->W * d->Ca * (a16 ? 2ull : 4ull);
     const unsigned long long gb = (unsigned long long)pl.M * d->ldg * (g16 ? 2ull : 4ull);
@@ -766,57 +757,42 @@ static int conv_wgrad_impl(const s2i_wgrad_desc* d, int planes, const float* a, 
     p.a_bytes = (unsigned)ab; p.g_bytes = (unsigned)gb;
     p.c_bytes = (unsigned)((unsigned long long)d->B * d->Cc * 4ull);
   }
-  dim3 grid(pl.gridK, pl.gridN, pl.splitk);
-  if (!a16 && g16 && d->kind == S2I_CONV_K4S2 && d->Ca == 4 && d->Cc == 0 && pl.K == 64 && d->N <= 64 && (d->N % 8) == 0 &&
-      (d->ldg % 8) == 0) {
-    // first discriminator conv: fp32 NHWC4 image x bf16 output gradient on the bf16 matrix cores
-    WgradP q = p;
-    q.nchunks = s2i_cdiv(pl.M, 64);
-    q.cps = s2i_cdiv(q.nchunks, pl.splitk);
-    dim3 g32(1, 1, s2i_cdiv(q.nchunks, q.cps));
-    pl.splitk = (int)g32.z;
-    pl.gridK = 1; pl.gridN = 1;
-    hipLaunchKernelGGL((igemm_wgrad_b16_kernel<64, 64, 2, 2, true>), g32, dim3(256), 0, st, q);
-  } else if (a16 && g16 && !pl.small_n && d->Cc == 0 && (pl.Cin % 8) == 0 && (d->N % 8) == 0 && (d->ldg % 8) == 0) {
-    // both operands bf16: 64-pixel stages on the bf16 matrix cores
-    WgradP q = p;
-    q.nchunks = s2i_cdiv(pl.M, 64);
-    q.cps = s2i_cdiv(q.nchunks, pl.splitk);
-    dim3 g16grid(pl.gridK, pl.gridN, s2i_cdiv(q.nchunks, q.cps));
-    S2I_REQUIRE((int)g16grid.z <= pl.splitk, "wgrad(bf16): split plan mismatch");
-    // slabs of splits that this plan does not launch must not be summed: shrink the slab count instead
-    pl.splitk = (int)g16grid.z;
-    if (pl.tile == 7) hipLaunchKernelGGL((igemm_wgrad_b16_kernel<256, 256, 4, 4>), g16grid, dim3(1024), 0, st, q);
-    else if (pl.tile == 6) hipLaunchKernelGGL((igemm_wgrad_b16_kernel<256, 128, 4, 2>), g16grid, dim3(512), 0, st, q);
-    else if (pl.tile == 0) hipLaunchKernelGGL((igemm_wgrad_b16_kernel<128, 128, 2, 2>), g16grid, dim3(256), 0, st, q);
-    else if (pl.tile == 1) hipLaunchKernelGGL((igemm_wgrad_b16_kernel<128, 64, 2, 2>), g16grid, dim3(256), 0, st, q);
-    else if (pl.tile == 2) hipLaunchKernelGGL((igemm_wgrad_b16_kernel<128, 32, 4, 1>), g16grid, dim3(256), 0, st, q);
-    else hipLaunchKernelGGL((igemm_wgrad_b16_kernel<64, 64, 2, 2>), g16grid, dim3(256), 0, st, q);
-  } else if (pl.rows3) {
-    dim3 g3(d->Ca == 32 ? 1 : 3, pl.gridN, pl.splitk);
-    if (d->Ca == 32 && pl.bn3 == 64) hipLaunchKernelGGL((wgrad_k3_rows_kernel<32, 64, 3, 1, 3>), g3, dim3(192), 0, st, p);
-    else if (d->Ca == 32) hipLaunchKernelGGL((wgrad_k3_rows_kernel<32, 32, 3, 1, 3>), g3, dim3(192), 0, st, p);
-    else if (pl.bn3 == 128) hipLaunchKernelGGL((wgrad_k3_rows_kernel<64, 128, 2, 2, 1>), g3, dim3(256), 0, st, p);
-    else if (pl.bn3 == 64) hipLaunchKernelGGL((wgrad_k3_rows_kernel<64, 64, 2, 2, 1>), g3, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((wgrad_k3_rows_kernel<64, 32, 2, 1, 1>), g3, dim3(128), 0, st, p);
-  } else if (planes && !pl.small_n) {
-    if (pl.tile == 0) launch_wgrad_split<128, 128, 2, 2>(p, grid, planes, st);
-    else if (pl.tile == 1) launch_wgrad_split<128, 64, 2, 2>(p, grid, planes, st);
-    else if (pl.tile == 2) launch_wgrad_split<128, 32, 4, 1>(p, grid, planes, st);
-    else launch_wgrad_split<64, 64, 2, 2>(p, grid, planes, st);
-  } else if (pl.small_n) {
-    if (d->Ca == 16) hipLaunchKernelGGL(small_n_wgrad_kernel<4>, dim3(pl.splitk), dim3(256), 0, st, p);
-    else if (d->Ca == 32) hipLaunchKernelGGL(small_n_wgrad_kernel<8>, dim3(pl.splitk), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(small_n_wgrad_kernel<16>, dim3(pl.splitk), dim3(256), 0, st, p);
-  } else if (pl.tile == 9) hipLaunchKernelGGL((igemm_wgrad_kernel<256, 256, 4, 4>), grid, dim3(1024), 0, st, p);
-  else if (pl.tile == 8) hipLaunchKernelGGL((igemm_wgrad_kernel<256, 128, 4, 2>), grid, dim3(512), 0, st, p);
-  else if (pl.tile == 0 && a_coef) hipLaunchKernelGGL((igemm_wgrad_kernel<128, 128, 2, 2, true>), grid, dim3(256), 0, st, p);
-  else if (pl.tile == 0) hipLaunchKernelGGL((igemm_wgrad_kernel<128, 128, 2, 2>), grid, dim3(256), 0, st, p);
-  else if (pl.tile == 1) hipLaunchKernelGGL((igemm_wgrad_kernel<128, 64, 2, 2>), grid, dim3(256), 0, st, p);
-  else if (pl.tile == 2) hipLaunchKernelGGL((igemm_wgrad_kernel<128, 32, 4, 1>), grid, dim3(256), 0, st, p);
-  else if (pl.tile == 3) hipLaunchKernelGGL((igemm_wgrad_kernel<64, 64, 2, 2>), grid, dim3(256), 0, st, p);
-  else if (pl.tile == 4) hipLaunchKernelGGL((igemm_wgrad_kernel<96, 64, 3, 1>), grid, dim3(192), 0, st, p);
-  else hipLaunchKernelGGL((igemm_wgrad_kernel<96, 32, 3, 1>), grid, dim3(192), 0, st, p);
+  const dim3 grid(pl.gx, pl.gy, pl.gz);
+#define WG_LAUNCH(id, ...) case id: hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(pl.threads), 0, st, p); break
+#define WG_LAUNCH_SPLIT(id, ...) case id: launch_wgrad_split<__VA_ARGS__>(p, grid, pl.planes, st); break
+  switch (pl.kernel) {
+    WG_LAUNCH(WG_F32_128x128, igemm_wgrad_kernel<128, 128, 2, 2>);
+    WG_LAUNCH(WG_F32_128x64, igemm_wgrad_kernel<128, 64, 2, 2>);
+    WG_LAUNCH(WG_F32_128x32, igemm_wgrad_kernel<128, 32, 4, 1>);
+    WG_LAUNCH(WG_F32_64x64, igemm_wgrad_kernel<64, 64, 2, 2>);
+    WG_LAUNCH(WG_F32_256x128, igemm_wgrad_kernel<256, 128, 4, 2>);
+    WG_LAUNCH(WG_F32_256x256, igemm_wgrad_kernel<256, 256, 4, 4>);
+    WG_LAUNCH(WG_F32_96x64, igemm_wgrad_kernel<96, 64, 3, 1>);
+    WG_LAUNCH(WG_F32_96x32, igemm_wgrad_kernel<96, 32, 3, 1>);
+    WG_LAUNCH(WG_F32IN_128x128, igemm_wgrad_kernel<128, 128, 2, 2, true>);
+    WG_LAUNCH(WG_B16_128x128, igemm_wgrad_b16_kernel<128, 128, 2, 2>);
+    WG_LAUNCH(WG_B16_128x64, igemm_wgrad_b16_kernel<128, 64, 2, 2>);
+    WG_LAUNCH(WG_B16_128x32, igemm_wgrad_b16_kernel<128, 32, 4, 1>);
+    WG_LAUNCH(WG_B16_64x64, igemm_wgrad_b16_kernel<64, 64, 2, 2>);
+    WG_LAUNCH(WG_B16_256x128, igemm_wgrad_b16_kernel<256, 128, 4, 2>);
+    WG_LAUNCH(WG_B16_256x256, igemm_wgrad_b16_kernel<256, 256, 4, 4>);
+    WG_LAUNCH(WG_B16D1_64x64, igemm_wgrad_b16_kernel<64, 64, 2, 2, true>);
+    WG_LAUNCH_SPLIT(WG_SPLIT_128x128, 128, 128, 2, 2);
+    WG_LAUNCH_SPLIT(WG_SPLIT_128x64, 128, 64, 2, 2);
+    WG_LAUNCH_SPLIT(WG_SPLIT_128x32, 128, 32, 4, 1);
+    WG_LAUNCH_SPLIT(WG_SPLIT_64x64, 64, 64, 2, 2);
+    WG_LAUNCH(WG_ROWS3_32x64, wgrad_k3_rows_kernel<32, 64, 3, 1, 3>);
+    WG_LAUNCH(WG_ROWS3_32x32, wgrad_k3_rows_kernel<32, 32, 3, 1, 3>);
+    WG_LAUNCH(WG_ROWS3_64x128, wgrad_k3_rows_kernel<64, 128, 2, 2, 1>);
+    WG_LAUNCH(WG_ROWS3_64x64, wgrad_k3_rows_kernel<64, 64, 2, 2, 1>);
+    WG_LAUNCH(WG_ROWS3_64x32, wgrad_k3_rows_kernel<64, 32, 2, 1, 1>);
+    WG_LAUNCH(WG_SMALLN_16, small_n_wgrad_kernel<4>);
+    WG_LAUNCH(WG_SMALLN_32, small_n_wgrad_kernel<8>);
+    WG_LAUNCH(WG_SMALLN_64, small_n_wgrad_kernel<16>);
+    default: S2I_FAIL("wgrad: the plan names no kernel (%d)", (int)pl.kernel);
+  }
+#undef WG_LAUNCH
+#undef WG_LAUNCH_SPLIT
   S2I_LAUNCH_CHECK("igemm_wgrad");
   {
     const int ncols = d->swap ? d->I : d->O, nrows = d->swap ? d->O : d->I;
@@ -826,9 +802,9 @@ static int conv_wgrad_impl(const s2i_wgrad_desc* d, int planes, const float* a, 
     const size_t shb = (size_t)pl.T * RT * 33 * sizeof(float);
     // two passes (measured: 27 + 17 us against 53 us for one pass that walks the slabs tile by tile): first a
     // float4 stream folds the split slabs into slab 0, then the tile kernel transposes slab 0 into OIHW
-    int S = pl.splitk;
+    int S = pl.slabs;
     const long long kn = (long long)pl.K * d->N;
-    if (pl.small_n || (S >= 32 && (kn % 4) == 0 && kn / 4 < (1 << 18))) {
+    if (pl.kernel >= WG_SMALLN_16 || (S >= 32 && (kn % 4) == 0 && kn / 4 < (1 << 18))) {
       // many slabs of a small K x N: the float4 stream below would run on a handful of blocks
       hipLaunchKernelGGL(slab_sum_tree_kernel, dim3(s2i_cdiv(kn / 4, 4)), dim3(256), 0, st, (float*)ws, S, (int)(kn / 4));
       S2I_LAUNCH_CHECK("slab_sum_tree");
@@ -846,6 +822,14 @@ static int conv_wgrad_impl(const s2i_wgrad_desc* d, int planes, const float* a, 
   }
   S2I_LAUNCH_CHECK("wgrad_finish");
   return 0;
+}
+
+static int conv_wgrad_impl(const s2i_wgrad_desc* d, int planes, const float* a, const float* cvec, const float* g,
+                           float* grad_oihw, void* ws, size_t ws_bytes, void* stream, int a16 = 0, int g16 = 0, const float* a_coef = nullptr) {
+  WgMode mode;
+  WgPlan pl;
+  if (wg_mode(a16, g16, planes, a_coef != nullptr, &mode) || plan_wgrad(d, mode, &pl)) return 1;
+  return launch_wgrad(d, pl, a, cvec, g, grad_oihw, ws, ws_bytes, stream, a16, g16, a_coef);
 }
 
 extern "C" int s2i_conv_wgrad_in(const s2i_wgrad_desc* d, const float* a_raw, const float* a_coef, const float* g,

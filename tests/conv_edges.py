@@ -29,8 +29,8 @@ REACH = (
     "short-last-split",   # split-K whose last split has fewer chunks than the others
     "rowtail-4phase",     # a partly filled row tile in each of the 4 phases of a transposed convolution
     "groups-96",          # grouped BatchNorm statistics on groups of whole 96-row (not 128-row) tiles
-    "wg-pixtail-t0", "wg-pixtail-t1", "wg-pixtail-t3", "wg-pixtail-t4", "wg-pixtail-t5", "wg-pixtail-t8",
-    "wg-pixtail-t9",      # weight gradient: the pixel range ends on a short 32-pixel chunk, per tile shape of plan_wgrad
+    "wg-pixtail-128x128", "wg-pixtail-128x64", "wg-pixtail-64x64", "wg-pixtail-96x64", "wg-pixtail-96x32", "wg-pixtail-256x128",
+    "wg-pixtail-256x256",      # weight gradient: the pixel range ends on a short 32-pixel chunk, per tile shape of plan_wgrad
     "wg-rows3-odd-batch",  # the row-segment kernel (3x3, W >= 32) at its smallest map with a batch that is no power of two
     "b16-ragged-128",     # bf16 forward, 128-pixel kernel: the last tile holds fewer images than the others
     "b16-ragged-256",     # the same on the 256-pixel kernel
@@ -162,27 +162,27 @@ def _table():
                    ["single-partial-tile", "rowtail-128x64"]))
     # ---- fp32 weight gradient ----------------------------------------------------------------------------------------
     t.append(wgrad("k3s1", 5, 4, 160, 64, "M = 80: chunks of 32 + 32 + 16 pixels; 128 x 64 tile; K = 1440 (tail 32)",
-                   ["wg-pixtail-t1"]))
-    t.append(wgrad("k3s1", 3, 4, 40, 136, "M = 48, K = 360, N = 136: pixel, K and column tails together", ["wg-pixtail-t0"]))
-    for bm, f in ((128, "wg-pixtail-t0"), (256, "wg-pixtail-t8")):
+                   ["wg-pixtail-128x64"]))
+    t.append(wgrad("k3s1", 3, 4, 40, 136, "M = 48, K = 360, N = 136: pixel, K and column tails together", ["wg-pixtail-128x128"]))
+    for bm, f in ((128, "wg-pixtail-128x128"), (256, "wg-pixtail-256x128")):
         t.append(wgrad("k4s2", 5, 8, 64, 128, "M = 80, K = 1024", [f], tune=dict(wgrad_bm=bm)))
-    for bm, f in ((128, "wg-pixtail-t0"), (256, "wg-pixtail-t8"), (512, "wg-pixtail-t9")):
+    for bm, f in ((128, "wg-pixtail-128x128"), (256, "wg-pixtail-256x128"), (512, "wg-pixtail-256x256")):
         t.append(wgrad("k3s1", 7, 4, 256, 512, "M = 112, K = 2304, N = 512", [f], tune=dict(wgrad_bm=bm)))
-    t.append(wgrad("k4s2", 1, 8, 4, 64, "the first discriminator conv's 64-row tile at one image, M = 16", ["wg-pixtail-t3"]))
+    t.append(wgrad("k4s2", 1, 8, 4, 64, "the first discriminator conv's 64-row tile at one image, M = 16", ["wg-pixtail-64x64"]))
     t.append(wgrad("k3s1", 5, 8, 32, 64, "K = 288 on 96 x 64 tiles, M = 320", []))
-    t.append(wgrad("k3s1", 5, 4, 32, 64, "K = 288 on 96 x 64 tiles, M = 80", ["wg-pixtail-t4"]))
+    t.append(wgrad("k3s1", 5, 4, 32, 64, "K = 288 on 96 x 64 tiles, M = 80", ["wg-pixtail-96x64"]))
     t.append(wgrad("k3s1", 5, 8, 32, 32, "K = 288 on 96 x 32 tiles, M = 320", []))
-    t.append(wgrad("k3s1", 3, 4, 32, 32, "K = 288 on 96 x 32 tiles, M = 48", ["wg-pixtail-t5"]))
+    t.append(wgrad("k3s1", 3, 4, 32, 32, "K = 288 on 96 x 32 tiles, M = 48", ["wg-pixtail-96x32"]))
     t.append(wgrad("k1", 5, 1, 100, 2048, "the fc's weight gradient at batch 5: one chunk of 5 pixels, broadcast vector",
-                   ["wg-pixtail-t0"], Cc=128))
+                   ["wg-pixtail-128x128"], Cc=128))
     t.append(wgrad("k3s1", 3, 32, 32, 64, "row-segment kernel, W = 32, 3 images", ["wg-rows3-odd-batch"]))
     t.append(wgrad("k3s1", 3, 32, 64, 128, "row-segment kernel, 64 -> 128 channels, W = 32, 3 images", ["wg-rows3-odd-batch"]))
     t.append(wgrad("up", 5, 4, 64, 128, "up-block weight gradient (swap, 4x4 taps folded to 3x3), M = 80, K = 2048",
-                   ["wg-pixtail-t1"]))
-    t.append(wgrad("k3s1", 5, 4, 160, 64, "M = 80, accumulated into a prefilled gradient", ["wg-pixtail-t1"], accumulate=True))
+                   ["wg-pixtail-128x64"]))
+    t.append(wgrad("k3s1", 5, 4, 160, 64, "M = 80, accumulated into a prefilled gradient", ["wg-pixtail-128x64"], accumulate=True))
     t.append(wgrad("k3s1", 3, 4, 40, 136, "M = 48, written into input channels [32, 72) of a wider tensor",
-                   ["wg-pixtail-t0"], i_off=32))
-    t.append(wgrad("k4s2", 5, 8, 64, 128, "M = 80, 256 x 128 tile, accumulated into a slice", ["wg-pixtail-t8"],
+                   ["wg-pixtail-128x128"], i_off=32))
+    t.append(wgrad("k4s2", 5, 8, 64, 128, "M = 80, 256 x 128 tile, accumulated into a slice", ["wg-pixtail-256x128"],
                    accumulate=True, i_off=8, tune=dict(wgrad_bm=256)))
     # ---- bf16 --------------------------------------------------------------------------------------------------------
     t.append(fwd("k3s1", 5, 4, 256, 512, "4x4 maps: a 128-pixel tile spans 8 images, the batch has 5", ["b16-ragged-128"],
@@ -361,6 +361,11 @@ def _bf16_plan(rec, lib, M, nph, Ho, Wo):
     return dict(M=M, nphases=nph, splitk=sk, bm=bm, tb=tb, gridM=grid_m, reach=reach)
 
 
+# K rows x N columns per block of plan_wgrad's tile numbers as restated below (the fp32 kernels' WgKernel shapes; 6 / 7: bf16)
+_WG_TILES = {0: (128, 128), 1: (128, 64), 2: (128, 32), 3: (64, 64), 4: (96, 64), 5: (96, 32), 6: (256, 128), 7: (256, 256),
+             8: (256, 128), 9: (256, 256)}
+
+
 def wgrad_plan(rec):
     """dict(M, K, N, tile, rows3, splitk, reach).  The workspace query gives the split count; the tile shape is restated
     from plan_wgrad: tiles 0 - 5 follow from K and N alone, 8 / 9 (fp32) and 6 / 7 (bf16) are forced through the knobs wgrad_bm /
@@ -397,6 +402,11 @@ def wgrad_plan(rec):
         tile = 7 if (force16 == 512 and N % 256 == 0) else 6
     rows3 = (fp32 and rec["kind"] == ops.CONV_K3S1 and rec["cvec"] == 0 and Ca in (32, 64) and W >= 32 and N % 32 == 0
              and N <= 128)
+    with _lib.tuning(**tune):
+        told = _lib.wgrad_plan(d, int(a16), int(g16))
+    assert told["ws_slabs"] == sk and (told["K"], told["M"]) == (K, M), told
+    if not rows3 and not (a16 and g16) and not (g16 and Ca == 4):
+        assert (told["bm"], told["bn"]) == _WG_TILES[tile], (told, tile)      # the restated tile is the planned one
     reach = set()
     if a16 and g16 or (g16 and Ca == 4):
         if M % 64:
@@ -405,7 +415,7 @@ def wgrad_plan(rec):
         if B & (B - 1):
             reach.add("wg-rows3-odd-batch")
     elif M % 32:
-        reach.add("wg-pixtail-t%d" % tile)
+        reach.add("wg-pixtail-%dx%d" % _WG_TILES[tile])
     return dict(M=M, K=K, N=N, tile=tile, rows3=rows3, splitk=sk, reach=reach)
 
 

@@ -26,8 +26,8 @@ import launch_ref as R  # noqa: E402
 # every feature the table as a whole must reach
 REQUIRED = (
     "rowtail-128", "rowtail-96", "rowtail-128x64", "rowtail-128x32", "single-partial-tile", "coltail", "ktail",
-    "short-last-split", "rowtail-4phase", "groups-96", "wg-pixtail-t0", "wg-pixtail-t1", "wg-pixtail-t3", "wg-pixtail-t4",
-    "wg-pixtail-t5", "wg-pixtail-t8", "wg-pixtail-t9", "wg-rows3-odd-batch", "b16-ragged-128", "b16-ragged-256",
+    "short-last-split", "rowtail-4phase", "groups-96", "wg-pixtail-128x128", "wg-pixtail-128x64", "wg-pixtail-64x64", "wg-pixtail-96x64",
+    "wg-pixtail-96x32", "wg-pixtail-256x128", "wg-pixtail-256x256", "wg-rows3-odd-batch", "b16-ragged-128", "b16-ragged-256",
     "b16-wg-stagetail",
 )
 

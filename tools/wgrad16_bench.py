@@ -42,6 +42,8 @@ for name, kind, ashape, gshape, wshape in CASES:
     for bm in (128, 256, 0) + ((512,) if os.environ.get('TRY512') else ()):
         with _lib.tuning(wgrad16_bm=bm):
             out = torch.zeros(wshape, device=dev)
+            Bq, Hq, Wq, Caq = ashape
+            plan = _lib.wgrad_plan(_lib.WgradDesc(kind, Bq, Hq, Wq, Caq, 0, gshape[3], gshape[3], 0, 0, *wshape), _lib.DT_BF16, _lib.DT_BF16)
             fn = lambda: ops.wgrad_any(kind, a, g, wshape, out=out)
             for _ in range(3):
                 fn()
@@ -56,6 +58,7 @@ for name, kind, ashape, gshape, wshape in CASES:
             res[bm] = out.clone()
         tot[bm] += ms
         line += " | %3d: %6.3f ms %6.1f TF" % (bm, ms, flops / ms / 1e9)
+        line += " %s grid %dx%dx%d" % (plan["kernel"], plan["gx"], plan["gy"], plan["gz"])
     rel = float((res[128] - res[256]).abs().max() / res[128].abs().max())
     print(line + " | max rel diff %.1e" % rel, flush=True)
 print("sum: 128-row tiles %.3f ms, 256-row tiles %.3f ms, planner %.3f ms" % (tot[128], tot[256], tot[0]))

@@ -40,6 +40,8 @@ for name, kind, ashape, gshape, wshape in CASES:
     line = "%-26s" % name
     for bm in BMS:
         with _lib.tuning(wgrad_bm=bm):
+            Bq, Hq, Wq, Caq = ashape
+            plan = _lib.wgrad_plan(_lib.WgradDesc(kind, Bq, Hq, Wq, Caq, 0, gshape[3], gshape[3], 0, 0, *wshape))
             fn = lambda: ops.wgrad_raw(kind, a, None, g, wshape, out=out, accumulate=True)
             for _ in range(3):
                 fn()
@@ -52,4 +54,5 @@ for name, kind, ashape, gshape, wshape in CASES:
             torch.cuda.synchronize()
             ms = e0.elapsed_time(e1) / reps
         line += " | bm %3d: %7.3f ms  %6.1f TF" % (bm, ms, flops / ms / 1e9)
+        line += " %s grid %dx%dx%d" % (plan["kernel"], plan["gx"], plan["gy"], plan["gz"])
     print(line, flush=True)
