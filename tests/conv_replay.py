@@ -16,6 +16,13 @@ GAMMA = {
     "fp32/wgrad": 8e-7,
     "bf16/conv": 1e-7,
     "bf16/wgrad": 3.2e-7,
+    # the split-bf16 matrix modes (ops.MATH_PLANES = 3 / 1), worst of the edge replay and the plane probe of
+    # tests/test_split_planes_gpu.py: three planes forward / input gradient 4.6e-7, weight gradient 5.0e-7 (both held at the
+    # native fp32 constants, which DESIGN.md section 9 claims for them); one plane 3.3e-8 and 9.3e-8
+    "split3/conv": 2 ** -20,
+    "split3/wgrad": 8e-7,
+    "split1/conv": 7e-8,
+    "split1/wgrad": 1.9e-7,
 }
 GAMMA_STATS = 1.5e-7
 
@@ -134,13 +141,21 @@ def conv_ref(rec, op, layer, x, cvec, W, Op, table, bias, mutate=False):
     return pre, y
 
 
-def replay_conv(rec, gen, dev, what, ledger, extra=None):
+def randn_weight(shape, gen, dev):
+    """N(0, 1) / (k sqrt(I)) weights of an (O, I, k, k) layer: full 24-bit significands, where LH.dyadic fits one bf16."""
+    return torch.randn(tuple(shape), generator=gen, device=dev) / (shape[2] * shape[1] ** 0.5)
+
+
+def replay_conv(rec, gen, dev, what, ledger, extra=None, *, weights="dyadic", operands=None, cls=None):
     """extra(ctx), if given, runs before the assertions with the operands, the output and the bound of this replay
     (tests/test_eval_launches_gpu.py and tests/test_conv_edges_gpu.py add their power checks there) and returns a list of
-    failure messages."""
+    failure messages.  Opt-in (tests/test_split_planes_gpu.py): weights = "randn" draws the OIHW weight with randn_weight;
+    operands = dict(x=, cvec=) takes these prepared tensors in place of the drawn ones; cls names the class whose GAMMA
+    bounds the replay and under which the ledger notes it."""
     from speech_to_image_translation_without_text_amd import ops
+    given = operands or {}
     op, layer = R.layer_op(rec)
-    x = _operand(rec["x"], gen, dev)
+    x = given["x"] if "x" in given else _operand(rec["x"], gen, dev)
     # an fp32 image operand with a bf16 output (the first discriminator conv, the input gradient of GET_IMAGE_G) runs on
     # the bf16 matrix cores, which read it as bf16: it is drawn on the bf16 grid
     mixed = _dtname(x) != rec["out_dtype"]
@@ -154,12 +169,14 @@ def replay_conv(rec, gen, dev, what, ledger, extra=None):
     else:
         mode = R.pack_mode(op, layer)
         assert mode == wd["mode"], (what, mode, wd)
-        w = LH.dyadic(wd["oihw"], gen, dev)
+        w = (LH.dyadic if weights == "dyadic" else randn_weight)(wd["oihw"], gen, dev)
         packed = ops.pack_weight(w, mode)
         assert list(packed.shape) == wd["packed"], (what, list(packed.shape), wd)
         W = w.double()
     N = rec["N"]
     cvec = torch.randn((B, rec["cvec"]), generator=gen, device=dev) if rec["cvec"] else None
+    if "cvec" in given:
+        cvec = given["cvec"]
     table = torch.randn((B, 9, N), generator=gen, device=dev) if rec["cls_bias"] else None
     bias = torch.randn((rec["bias"],), generator=gen, device=dev) if rec["bias"] else None
     kw = dict(wmode=rec["wmode"], flip=rec["flip"], bias=bias, act=rec["act"], stats=rec["stats"], groups=rec["groups"],
@@ -191,7 +208,7 @@ def replay_conv(rec, gen, dev, what, ledger, extra=None):
     ref = R.act(ref, rec["act"])
     out = _nchw(y)
     rnd = LH.BF16_ROUND if y.dtype == torch.bfloat16 else 0.0
-    cls = ("bf16" if (rec["fast"] or mixed) else "fp32") + "/conv"
+    cls = cls or ("bf16" if (rec["fast"] or mixed) else "fp32") + "/conv"
     gamma = GAMMA[cls]
     ratio, ok = LH.compare(out, ref, absref, rnd, gamma)
     ledger.note(cls, ratio, what, gamma)
@@ -219,12 +236,14 @@ def replay_conv(rec, gen, dev, what, ledger, extra=None):
     assert sees_channel, "%s: the bound cannot see one input channel's contribution" % what
 
 
-def replay_wgrad(rec, gen, dev, what, ledger, extra=None):
-    """extra(ctx), if given, runs before the assertions, as in replay_conv, and returns a list of failure messages."""
+def replay_wgrad(rec, gen, dev, what, ledger, extra=None, *, operands=None, cls=None):
+    """extra(ctx), if given, runs before the assertions, as in replay_conv, and returns a list of failure messages;
+    operands = dict(a=, g=, cvec=) and cls as in replay_conv."""
     from speech_to_image_translation_without_text_amd import ops
+    given = operands or {}
     op, layer = R.layer_op(rec)
-    a = _operand(rec["a"], gen, dev)
-    g = _operand(rec["g"], gen, dev)
+    a = given["a"] if "a" in given else _operand(rec["a"], gen, dev)
+    g = given["g"] if "g" in given else _operand(rec["g"], gen, dev)
     # one bf16 operand (the first discriminator conv's fp32 image x its bf16 output gradient): the launch runs on the bf16
     # matrix cores and reads the fp32 operand as bf16, so that operand is drawn on the bf16 grid
     mixed = a.dtype != g.dtype
@@ -232,6 +251,8 @@ def replay_wgrad(rec, gen, dev, what, ledger, extra=None):
         a, g = [t if t.dtype == torch.bfloat16 else t.bfloat16().float() for t in (a, g)]
     B = a.shape[0]
     cvec = torch.randn((B, rec["cvec"]), generator=gen, device=dev) if rec["cvec"] else None
+    if "cvec" in given:
+        cvec = given["cvec"]
     gs = rec["grad_shape"]
     O, I = gs[0], gs[1]
     kh = gs[2] if len(gs) == 4 else 1
@@ -275,7 +296,7 @@ def replay_wgrad(rec, gen, dev, what, ledger, extra=None):
     ref = base + dw()
     absref = dw(absval=True)
     rnd = 2 * LH.U if rec["accumulate"] else 0.0      # the one rounding of prefill + gradient
-    cls = ("bf16" if (mixed or a.dtype == torch.bfloat16) else "fp32") + "/wgrad"
+    cls = cls or ("bf16" if (mixed or a.dtype == torch.bfloat16) else "fp32") + "/wgrad"
     gamma = GAMMA[cls]
     ratio, ok = LH.compare(got, ref, absref, rnd, gamma)
     ledger.note(cls, ratio, what, gamma)

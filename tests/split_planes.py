@@ -1,0 +1,233 @@
+"""The split-bf16 matrix modes (ops.MATH_PLANES = 1 / 2 / 3) at the edges of their tile kernels: the
+record table, the plane reference and the probe operands of tests/test_split_planes_cpu.py / test_split_planes_gpu.py.
+
+The records use the schema and the constructors of tests/conv_edges.py (fwd, dgrad, wgrad) with one more key:
+
+  planes     the values of ops.MATH_PLANES the record is replayed under.  Every record runs at 3 planes with weights of
+             full 24-bit significands; the records whose operands can be drawn on the bf16 grid also run at 1 plane
+             (class split1/*), where every product is exact.  A fallback record (reach = ["fallback"]) is one that the
+             dispatch keeps on the native fp32 kernels in a split mode; it must hold the native bound there.
+
+`reach` uses the names of conv_edges.REACH and the ones of REACH below; `split_plan` derives them from the host queries."""
+import ctypes
+
+import torch
+
+import conv_edges as E
+from speech_to_image_translation_without_text_amd import _lib, ops
+
+REACH = E.REACH + (
+    "wg-pixtail-128x32",      # weight gradient: the pixel range ends on a short 32-pixel chunk on the 128 x 32 tile
+    "wg-ktail",               # K = taps x channels is no multiple of the tile's K rows
+    "wg-coltail",             # N is no multiple of the tile's columns
+    "wg-short-last-split",    # the pixel range is split and the last split has fewer chunks than the others
+    "wg-from-vec",            # part of the gathered operand is the broadcast vector
+    "cvec-chunks",            # forward: 32-deep chunks read from the broadcast vector (c0 < Cc)
+    "fallback",               # runs the native kernel in a split mode
+)
+FWD_TILES = ((128, 128), (128, 64), (128, 32))
+WG_TILES = ("split-128x128", "split-128x64", "split-128x32", "split-64x64")
+
+
+# ---- plane reference -------------------------------------------------------------------------------------------------
+def split(v, n):
+    """The n bf16 planes of an fp32 tensor as fp32 tensors, and the residual: what split4 (csrc/s2i_igemm.h) and
+    split_packed_kernel compute, round to nearest even with an exact residual."""
+    assert v.dtype == torch.float32
+    planes = []
+    for _ in range(n):
+        h = v.bfloat16().float()
+        planes.append(h)
+        v = v - h
+    return planes, v
+
+
+def kept(planes):
+    """The plane pairs (i, j), 1-based, whose products the mode accumulates."""
+    return [(i, j) for i in range(1, planes + 1) for j in range(1, planes + 1) if i + j <= planes + 1]
+
+
+def next_order(planes):
+    """The pairs of the first order the mode leaves out (among three planes)."""
+    return [(i, j) for i in range(1, 4) for j in range(1, 4) if i + j == planes + 2]
+
+
+# ---- probe operands --------------------------------------------------------------------------------------------------
+# c = 1 + 3 2^-10 + 3 2^-18 has the planes (1, 3 2^-10 + 2^-16, -2^-18) and no residual; scaling by a power of two scales
+# the planes.  With every operand c 2^e > 0 each cross-product sum is the same fraction of every output element:
+# sum a_i b_j = (c_i c_j / c^2) sum a b.
+PROBE_C = 1.0 + 3 * 2.0 ** -10 + 3 * 2.0 ** -18
+PROBE_PLANES = (1.0, 3 * 2.0 ** -10 + 2.0 ** -16, -2.0 ** -18)
+
+
+def probe_fraction(i, j):
+    return abs(PROBE_PLANES[i - 1] * PROBE_PLANES[j - 1]) / PROBE_C ** 2
+
+
+def probe_operand(shape, gen, dev):
+    e = torch.randint(-2, 3, tuple(shape), generator=gen, device=dev)
+    return torch.full(tuple(shape), PROBE_C, dtype=torch.float32, device=dev) * torch.pow(2.0, e.float())
+
+
+def probe_class(planes, kind):
+    """The class whose gamma bounds a probe launch: against the kept-product reference only the fp32 accumulation is left,
+    which two planes share with three."""
+    return "split%d/%s" % (1 if planes == 1 else 3, kind)
+
+
+def probe_fwd(N, planes):
+    """K1 forward with the smallest eligible reduction (one 32-deep chunk at one plane, where the bound is the bf16 class's;
+    two otherwise) on a 4 x 4 map of 5 images: dict(B, H, Cx, N)."""
+    return dict(B=5, H=4, Cx=32 if planes == 1 else 64, N=N)
+
+
+def probe_wgrad(tile, planes):
+    """K1 weight gradient on the split tile `tile`: dict(B, H, Ca, N).  The reduction runs over M = B H H pixels: one 32-pixel
+    chunk at one plane, 80 pixels (chunks of 32 + 32 + 16) otherwise."""
+    Ca, N = {"split-128x128": (128, 128), "split-128x64": (128, 64), "split-128x32": (128, 32), "split-64x64": (64, 64)}[tile]
+    return dict(B=2 if planes == 1 else 5, H=4, Ca=Ca, N=N)
+
+
+def probe_wgrad_desc(s):
+    return _lib.WgradDesc(ops.CONV_K1, s["B"], s["H"], s["H"], s["Ca"], 0, s["N"], s["N"], 0, 0, s["N"], s["Ca"], 1, 1, 0, 0, 0,
+                          0, 0)
+
+
+# ---- the table -------------------------------------------------------------------------------------------------------
+def _rec(rec, reach, planes=(3, 1), **over):
+    assert set(reach) <= set(REACH), reach
+    rec.update(over)
+    rec.update(reach=sorted(reach), planes=list(planes))
+    return rec
+
+
+def _table():
+    f = lambda *a, **k: E.fwd(*a, [], tile_rows=128, **k)
+    d = lambda *a, **k: E.dgrad(*a, [], tile_rows=128, **k)
+    w = lambda *a, **k: E.wgrad(*a, [], **k)
+    t = []
+    # ---- forward -----------------------------------------------------------------------------------------------------
+    t.append(_rec(f("k3s1", 5, 8, 64, 128, "128 x 128, M = 320: 64-row last tile; K split with a short last split; statistics "
+                    "from the slab reduction"), ["rowtail-128", "short-last-split"]))
+    t.append(_rec(f("k3s1", 5, 8, 32, 136, "128 x 128, column tail of 8; row tail in per-tile statistics"),
+                  ["rowtail-128", "coltail"]))
+    t.append(_rec(f("k4s2", 3, 16, 64, 64, "128 x 64, M = 192"), ["rowtail-128x64"]))
+    t.append(_rec(f("k4s2", 3, 16, 32, 40, "128 x 64, column tail"), ["rowtail-128x64", "coltail"]))
+    t.append(_rec(f("k3s1", 5, 8, 32, 32, "128 x 32, M = 320"), ["rowtail-128x32"]))
+    t.append(_rec(f("k3s1", 5, 8, 32, 24, "128 x 32, column tail"), ["rowtail-128x32", "coltail"]))
+    # the packed weights of an up layer are sums of four taps: at one plane they are drawn as LH.dyadic, exact in bf16
+    t.append(_rec(f("up", 5, 4, 64, 128, "transposed conv, M = 80: one partly filled tile in each of the 4 phases"),
+                  ["rowtail-4phase", "single-partial-tile"]))
+    t.append(_rec(f("up", 3, 8, 64, 136, "transposed conv, M = 192, N = 136: column tail under phases"),
+                  ["rowtail-4phase", "rowtail-128", "coltail"]))
+    t.append(_rec(f("k3s1", 1, 4, 512, 128, "M = 16; broadcast-vector chunks; deep K split", Cc=32),
+                  ["single-partial-tile", "short-last-split", "cvec-chunks"]))
+    t.append(_rec(f("k1", 5, 1, 96, 2048, "the generator's fc at batch 5 with 32 | Ca: M = 5, 16 column tiles", Cc=128),
+                  ["single-partial-tile", "cvec-chunks"]))
+    t.append(_rec(f("k4s2", 6, 16, 64, 128, "three stacked BatchNorm batches of 2 images: groups of one 128-row tile", groups=3),
+                  []))
+    t.append(_rec(f("k4s2", 3, 16, 64, 64, "128 x 64 with a bias and LeakyReLU in the epilogue", stats=False),
+                  ["rowtail-128x64"], bias=64, act=_lib.ACT_LRELU))
+    # ---- input gradient (wmode = 1: the [plane][T][R][C] weight layout) ----------------------------------------------
+    t.append(_rec(d("k3s1", 5, 8, 128, 64, "flipped 3x3 input gradient, M = 320"), ["rowtail-128", "short-last-split"]))
+    t.append(_rec(d("k3s1", 5, 8, 136, 64, "flipped 3x3 input gradient, N = 136: column tail"),
+                  ["rowtail-128", "short-last-split", "coltail"]))
+    t.append(_rec(d("k4s2", 5, 8, 128, 64, "stride-2 input gradient: 4 phases, M = 80 each"),
+                  ["rowtail-4phase", "single-partial-tile"]))
+    t.append(_rec(d("up", 5, 4, 64, 128, "up-block input gradient: stride-2 gather on the folded weights, 128 x 64"),
+                  ["single-partial-tile", "rowtail-128x64"]))
+    # ---- weight gradient ---------------------------------------------------------------------------------------------
+    t.append(_rec(w("k3s1", 5, 4, 160, 64, "128 x 64; pixel chunks 32 + 32 + 16; K = 1440 (row tail of 32)"),
+                  ["wg-pixtail-128x64", "wg-ktail"]))
+    t.append(_rec(w("k3s1", 3, 4, 40, 136, "128 x 128; pixel, K and column tails together"),
+                  ["wg-pixtail-128x128", "wg-ktail", "wg-coltail"]))
+    t.append(_rec(w("k4s2", 5, 8, 64, 128, "128 x 128, M = 80"), ["wg-pixtail-128x128"]))
+    t.append(_rec(w("k3s1", 3, 4, 32, 32, "128 x 32: K = 288 takes 96-row tiles in fp32 but 128-row tiles here"),
+                  ["wg-pixtail-128x32", "wg-ktail"]))
+    t.append(_rec(w("k3s1", 3, 4, 32, 24, "128 x 32 with a column tail"), ["wg-pixtail-128x32", "wg-ktail", "wg-coltail"]))
+    t.append(_rec(w("k4s2", 1, 8, 4, 64, "64 x 64, M = 16"), ["wg-pixtail-64x64"]))
+    t.append(_rec(w("k1", 5, 1, 100, 2048, "the fc's weight gradient at batch 5: broadcast vector", Cc=128),
+                  ["wg-pixtail-128x128", "wg-ktail", "wg-from-vec"]))
+    t.append(_rec(w("up", 5, 4, 64, 128, "up-block weight gradient: swap, 4x4 taps folded to 3x3"), ["wg-pixtail-128x64"]))
+    t.append(_rec(w("k3s1", 5, 4, 160, 64, "accumulated into a prefilled gradient", accumulate=True),
+                  ["wg-pixtail-128x64", "wg-ktail"]))
+    t.append(_rec(w("k3s1", 3, 4, 40, 136, "written into input channels [32, 72) of a wider tensor", i_off=32),
+                  ["wg-pixtail-128x128", "wg-ktail", "wg-coltail"]))
+    t.append(_rec(w("k3s1", 7, 8, 64, 128, "M = 448: the planner splits the pixel range with a short last split"),
+                  ["wg-short-last-split", "wg-ktail"]))
+    # ---- fallbacks: the native kernel under a split mode, at the native bound ----------------------------------------
+    t.append(_rec(f("k3s1", 5, 8, 40, 136, "Ca % 32 != 0: not eligible"), ["fallback"], planes=(3,)))
+    t.append(_rec(f("k3s1", 5, 16, 32, 64, "class-bias table: w_offset != 0", cls=32), ["fallback"], planes=(3,)))
+    t.append(_rec(w("k3s1", 2, 128, 16, 4, "3x3 -> 4 channels, M = 32768: the fp32 stream kernel"), ["fallback"], planes=(3,)))
+    return t
+
+
+RECORDS = _table()
+
+
+def cases():
+    """(index, planes) of every replay."""
+    return [(i, p) for i, rec in enumerate(RECORDS) for p in rec["planes"]]
+
+
+def case_id(index, planes):
+    return "%s-p%d" % (E.record_id(index, RECORDS[index]), planes)
+
+
+def is_conv(rec):
+    return rec["fn"].startswith("conv")
+
+
+def class_of(rec, planes):
+    """The class of conv_replay.GAMMA that bounds the replay of rec under `planes`."""
+    if "fallback" in rec["reach"]:
+        return "fp32/" + ("conv" if is_conv(rec) else "wgrad")
+    return "split%d/%s" % (planes, "conv" if is_conv(rec) else "wgrad")
+
+
+# ---- what a record's plan reaches in a split mode, from the host queries ---------------------------------------------
+def conv_eligible(rec):
+    """The condition of ops.conv_raw for the split entry point, on a weight packed by ops.pack_weight."""
+    lib = _lib.load()
+    T, R, C = rec["w"]["packed"]
+    kp = R if rec["wmode"] == 0 else C
+    return bool(rec["w_offset"] == 0 and kp % 8 == 0 and lib.s2i_conv_split_eligible(ctypes.byref(E.conv_desc(rec))))
+
+
+def split_plan(rec, planes):
+    """dict(split (the split kernel launches), tile, reach, ...) of rec under ops.MATH_PLANES = planes."""
+    if is_conv(rec):
+        assert rec["tile_rows"] == 128, "ops.conv_raw plans 128-row tiles in a split mode"
+        plan = E.conv_plan(rec)
+        ok = conv_eligible(rec)
+        reach = set(plan["reach"])
+        # the split kernels have 128-row tiles only (conv_forward_impl requires it), so a row tail follows from M alone, also
+        # where conv_plan cannot tell the tile height from the statistics rows (M = 192: two tiles under either height)
+        M, N = plan["M"], rec["N"]
+        if M > 128 and M % 128:
+            reach.add("rowtail-128" if N > 64 else "rowtail-128x%d" % plan["BN"])
+            if plan["nphases"] == 4:
+                reach.add("rowtail-4phase")
+        Ca = rec["x"][0][3] + rec["cvec"]
+        if rec["cvec"] and rec["cvec"] % 32 == 0 and Ca % 32 == 0:
+            reach.add("cvec-chunks")
+        return dict(plan, split=ok, tile=(128, plan["BN"]), reach=reach if ok else {"fallback"})
+    d = E.wgrad_desc(rec)
+    told = _lib.wgrad_plan(d, planes=planes)
+    assert told is not None, _lib.load().s2i_last_error()
+    ok = told["kernel"].startswith("split-")
+    M, K, N = told["M"], told["K"], d.N
+    nchunks = -(-M // told["stage"])
+    cps = -(-nchunks // told["gz"])
+    reach = set()
+    if M % 32:
+        reach.add("wg-pixtail-%dx%d" % (told["bm"], told["bn"]))
+    if K % told["bm"]:
+        reach.add("wg-ktail")
+    if N % told["bn"]:
+        reach.add("wg-coltail")
+    if told["gz"] > 1 and nchunks % cps:
+        reach.add("wg-short-last-split")
+    if rec["cvec"]:
+        reach.add("wg-from-vec")
+    return dict(told, split=ok, tile=told["kernel"], nchunks=nchunks, cps=cps, reach=reach if ok else {"fallback"})
