@@ -731,6 +731,18 @@ int s2i_pcm_resample(const void* raw, const long long* byte_offsets, const int* 
    mirrors the upper triangle.  rows = 0 is a no-op.  No atomics, no workspace, no synchronisation. */
 int s2i_moments_accumulate(const float* x, int rows, int D, long long ldx, double* colsum, double* gram, void* stream);
 
+/* ---- nearest-row search: the k best of every score row, chunk by chunk --------------------------------------------
+ * A gallery is scored a chunk of rows at a time with the fp32 1x1 matrix kernel; this folds each [Q, chunk] block of
+ * scores into a running [Q][k] result, so the [Q, N] matrix of the whole gallery never exists
+ * (speech_to_image_translation_without_text_amd/retrieval.py, Gallery). */
+/* For every query row q: the k best of scores[q][0..N) (row stride lds floats), row id = base + j, merged with the k
+ * entries already in best_score / best_row [Q][k] when merge != 0 (otherwise those are overwritten).
+ * Order: score descending; equal scores by ascending row id; NaN ranks as -inf.  Output rows are sorted in that order;
+ * slots beyond the number of candidates hold (-inf, -1).  1 <= k <= 64, N <= 2^30.  No arithmetic on the scores:
+ * bit-exact.  One block per query; no atomics, no workspace, no synchronisation. */
+int s2i_topk_rows(const float* scores, int Q, int N, int lds, int base, int k, float* best_score, int* best_row,
+                  int merge, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ LOGMEL_TILE_FRAMES = 64
 PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = 0, 1, 2, 3, 4, 5
 RESAMPLE_TILE = 1024
 RESAMPLE_MAX_WINDOW = 13826
+TOPK_MAX = 64
 ABI_VERSION = 5
 # s2i_wgrad_plan_query: the WgKernel values of csrc/s2i_igemm.h in order, and the twelve outputs
 WGRAD_KERNELS = ("f32-128x128", "f32-128x64", "f32-128x32", "f32-64x64", "f32-256x128", "f32-256x256", "f32-96x64", "f32-96x32",
@@ -191,6 +192,7 @@ _SIGNATURES = {
     "s2i_logmel_gather": (c_int, [P, P, P, c_int, c_int, P, P]),
     "s2i_pcm_resample": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, P, P]),
     "s2i_moments_accumulate": (c_int, [P, c_int, c_int, c_ll, P, P, P]),
+    "s2i_topk_rows": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -13,6 +13,7 @@ Each Function stands in for a group of stock torch ops of the reference
   ToNHWC / ToNCHW               layout changes at the module boundary
   LstmSentence, EncoderLoss     the speech encoder's LSTM head and loss (Audio_to_Image/train_audio_encoder.py)
   TemporalConvBnRelu, InputBatchNorm, MaxPoolW3S2, conv_stack_train   its conv stack in training mode
+  score_rows, topk_rows         one gallery chunk's scores and their fold into a running top k (retrieval.Gallery)
 
 Activations between these ops are NHWC; parameters stay in the reference's OIHW layout and are
 re-packed to the kernels' layout when their version counter changes.  There is no CPU fallback.
@@ -1807,3 +1808,61 @@ def logmel_gather(pool, row_offsets, frames, T):
     check(lib.s2i_logmel_gather(ptr(pool.detach()), ptr(row_offsets.contiguous()), ptr(frames.contiguous()), B, T,
                                 ptr(out), stream()), "s2i_logmel_gather")
     return out
+
+
+# ---- nearest-row search -------------------------------------------------------------------------------------------------
+def score_rows(x, packed, n, out):
+    """out[:Q * n] viewed [Q, n] = x [Q, Cp] times the first n rows of a gallery chunk packed with
+    pack_weight(chunk, PACK_PLAIN): one launch of the fp32 1x1 matrix kernel, written compactly (row stride n) into the
+    caller's flat fp32 buffer, which a search reuses for every chunk.  Q goes in as Q images of one pixel (_step_rows)."""
+    lib = _lib_ready()
+    Q, Cp = x.shape
+    n = int(n)
+    if (x.dtype != torch.float32 or not x.is_contiguous() or Cp % 4 or packed.dim() != 3 or packed.shape[0] != 1
+            or packed.shape[1] < Cp or packed.shape[2] < n or out.dtype != torch.float32 or out.numel() < Q * n):
+        raise ValueError("score_rows: x %s, packed %s, n %d and %d output floats do not fit"
+                         % (tuple(x.shape), tuple(packed.shape), n, out.numel()))
+    d = ConvDesc(CONV_K1, Q, 1, 1, Cp, 0, n, 0, 0, packed.shape[1], packed.shape[2], ACT_NONE, 0, n, 1, 0, 0, 0, 0,
+                 TILE_ROWS, 0, 0)
+    _log_exec("scores [%d,%d]x[%d,%d]" % (Q, Cp, n, Cp), Q, n, Cp, x.numel(), Cp * n, Q * n)
+    wsb = lib.s2i_conv_workspace_bytes(ctypes.byref(d))
+    ws = _ws.get(wsb, x.device)
+    check(lib.s2i_conv_forward_cls(ctypes.byref(d), ptr(x), None, ptr(packed), None, None, ptr(out), None, ptr(ws),
+                                   ws.numel() * 4, stream()), "s2i_conv_forward")
+    return out[:Q * n].view(Q, n)
+
+
+def topk_rows(scores, k, base=0, best=None, out=None):
+    """(best_score [Q, k] fp32, best_row [Q, k] int32): for every row of `scores` ([Q, N] fp32, unit column stride, any
+    row stride >= N) its k best entries, best first, as (score, base + column).  Higher scores first, equal scores by
+    ascending row id, NaN ranked as -inf; slots beyond the candidates hold (-inf, -1); the scores come back bit for bit.
+    `best` is a pair from an earlier call on other rows of the same queries: it is merged into, in place, and returned.
+    `out` is a pair to overwrite instead of fresh tensors.  1 <= k <= 64.  No autograd."""
+    k, base = int(k), int(base)
+    if not torch.is_tensor(scores) or scores.dim() != 2 or scores.dtype != torch.float32:
+        raise ValueError("topk_rows: scores must be an fp32 [Q, N] tensor")
+    Q, N = scores.shape
+    if Q < 1 or N < 1 or scores.stride(1) != 1 or scores.stride(0) < N:
+        raise ValueError("topk_rows: scores %s with strides %s: need Q, N >= 1, unit column stride and row stride >= N"
+                         % (tuple(scores.shape), tuple(scores.stride())))
+    if not 1 <= k <= _lib.TOPK_MAX:
+        raise ValueError("topk_rows: k %d outside 1..%d" % (k, _lib.TOPK_MAX))
+    if base < 0 or base + N > 2 ** 31 - 1:
+        raise ValueError("topk_rows: row ids %d .. %d leave int32" % (base, base + N - 1))
+    if best is not None and out is not None:
+        raise ValueError("topk_rows: give `best` (merge into) or `out` (overwrite), not both")
+    if not scores.is_cuda:
+        raise _lib.S2IError("topk_rows runs on the MI355X kernel: there is no CPU fallback (scores on %s)" % scores.device)
+    lib = _lib_ready()
+    pair = best if best is not None else out
+    if pair is None:
+        pair = (torch.empty((Q, k), dtype=torch.float32, device=scores.device),
+                torch.empty((Q, k), dtype=torch.int32, device=scores.device))
+    bs, br = pair
+    if (bs.dtype != torch.float32 or br.dtype != torch.int32 or tuple(bs.shape) != (Q, k) or tuple(br.shape) != (Q, k)
+            or not bs.is_contiguous() or not br.is_contiguous() or bs.device != scores.device or br.device != scores.device):
+        raise ValueError("topk_rows: the result pair must be contiguous fp32 and int32 [%d, %d] tensors on %s"
+                         % (Q, k, scores.device))
+    check(lib.s2i_topk_rows(ptr(scores.detach()), Q, N, scores.stride(0), base, k, ptr(bs), ptr(br),
+                            1 if best is not None else 0, stream()), "s2i_topk_rows")
+    return bs, br

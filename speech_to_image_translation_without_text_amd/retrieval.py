@@ -6,7 +6,13 @@ float64 (the sizes are a few thousand rows of 1024).
         --image data/birds/test/image_features_googlenet_caffe.pickle --data_dir data/birds --split test [--seed 0]
 
 prints and writes (``--out``, default ``<audio pickle dir>/retrieval_<split>.json``) one JSON line with ``accu`` and
-``ap50`` in percent.
+``ap50`` in percent.  With ``--recall`` the line also carries ``recall@1``, ``recall@5``, ``recall@10`` and ``recall@50``:
+the instance-level score, every one of the ten utterances of every item against the mean-of-views image rows, ranked on the
+GPU (`Gallery`, `recall_at_k`).
+
+`Gallery` keeps image-feature rows in HBM and answers "which rows does this embedding score highest against": the scores
+of one chunk of rows at a time come from the fp32 1x1 matrix kernel and are folded into a running top k by s2i_topk_rows,
+so the [queries, rows] matrix never exists.  `eval_class` stays on the host as it was.
 """
 import argparse
 import json
@@ -19,6 +25,10 @@ import numpy as np
 from . import datasets
 
 TOPK = 50
+RECALL_KS = (1, 5, 10, 50)
+# Gallery rows scored per matrix launch, and queries per launch (DESIGN.md section 8b7 has the measurements behind them)
+GALLERY_CHUNK_ROWS = 65536
+QUERY_BLOCK = 4096
 
 
 def eval_class(query, target, labels, topk=TOPK):
@@ -82,6 +92,124 @@ def eval_feature_files(audio_pickle, image_pickle, labels, seed=0, topk=TOPK):
                          labels, seed, topk)
 
 
+class Gallery:
+    """Feature rows resident on `device`, searched by dot product (the score of the embedding loss and of eval_class) or,
+    with cosine=True, by cosine similarity.
+
+    features   [N, V, C] (a list of N arrays [V, C], the image-feature pickles) or [N, C]
+    views      "mean": one row per item, the mean of its V views, formed in float64 on the host and stored as fp32;
+               "all": N * V rows, row i * V + v.  [N, C] features are one row per item either way.
+    cosine     rows (float64, on the host, before the fp32 store) and queries (fp32, on the device) are divided by their
+               L2 norms; an all-zero row stays zero.
+    chunk_rows rows per matrix launch.  Every chunk is packed once here (ops.pack_weight, PACK_PLAIN) and stays in HBM:
+               4 * C bytes per row, C rounded up to a multiple of 4.
+
+    rows, items, nviews (V where views="all", else None), dim, nbytes.  There is no CPU fallback."""
+
+    def __init__(self, features, device, views="mean", cosine=False, chunk_rows=GALLERY_CHUNK_ROWS):
+        import torch
+        from . import _lib, ops
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.S2IError("the gallery is packed for and searched by the MI355X kernels: there is no CPU fallback "
+                                "(device %s)" % self.device)
+        if views not in ("mean", "all"):
+            raise ValueError("Gallery: views must be 'mean' or 'all', got %r" % (views,))
+        self.chunk_rows = int(chunk_rows)
+        if self.chunk_rows < 1:
+            raise ValueError("Gallery: chunk_rows must be >= 1")
+        rows, self.items, self.nviews = gallery_rows(features, views, cosine)
+        self.cosine = bool(cosine)
+        self.rows, self.dim = rows.shape
+        self.cpad = (self.dim + 3) & ~3
+        if self.chunk_rows * self.cpad * 4 >= 0x7ff00000:
+            raise ValueError("Gallery: a chunk of %d rows of %d floats exceeds the matrix kernel's 2 GiB operand window"
+                             % (self.chunk_rows, self.cpad))
+        self.chunks = []
+        with torch.cuda.device(self.device):
+            for s in range(0, self.rows, self.chunk_rows):
+                part = np.zeros((min(self.chunk_rows, self.rows - s), self.cpad), dtype=np.float32)
+                part[:, :self.dim] = rows[s:s + self.chunk_rows]
+                self.chunks.append((s, part.shape[0], ops.pack_weight(torch.from_numpy(part).to(self.device), ops.PACK_PLAIN)))
+        self.nbytes = sum(c[2].numel() * 4 for c in self.chunks)
+        self._scores = None
+
+    def search(self, queries, k):
+        """(scores [Q, k] fp32, items [Q, k] int64, views [Q, k] int64 or None) on the device: for each query row its k
+        best gallery rows, best first; equal scores by ascending row.  k is clipped to the number of rows (64 at the most
+        after that: the kernel's limit)."""
+        import torch
+        from . import ops
+        q = torch.as_tensor(queries)
+        if q.dim() != 2 or q.shape[1] != self.dim or q.shape[0] < 1:
+            raise ValueError("Gallery.search: queries must be [Q >= 1, %d], got %s" % (self.dim, tuple(q.shape)))
+        k = min(int(k), self.rows)
+        if not 1 <= k <= 64:
+            raise ValueError("Gallery.search: k must lie in 1..64 after clipping to the %d rows, got %d" % (self.rows, k))
+        q = q.detach().to(device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            if self.cosine:
+                norm = torch.linalg.vector_norm(q, dim=1, keepdim=True)
+                q = q / torch.where(norm > 0, norm, torch.ones_like(norm))
+            if self.cpad != self.dim:
+                q = torch.nn.functional.pad(q, (0, self.cpad - self.dim))
+            q = q.contiguous()
+            Q = q.shape[0]
+            best = (torch.empty((Q, k), dtype=torch.float32, device=self.device),
+                    torch.empty((Q, k), dtype=torch.int32, device=self.device))
+            need = min(Q, QUERY_BLOCK) * min(self.chunk_rows, self.rows)
+            if self._scores is None or self._scores.numel() < need:
+                self._scores = torch.empty(need, dtype=torch.float32, device=self.device)
+            for q0 in range(0, Q, QUERY_BLOCK):
+                qb = q[q0:q0 + QUERY_BLOCK]
+                pair = (best[0][q0:q0 + QUERY_BLOCK], best[1][q0:q0 + QUERY_BLOCK])
+                for i, (start, n, packed) in enumerate(self.chunks):
+                    sc = ops.score_rows(qb, packed, n, self._scores)
+                    if i == 0:
+                        ops.topk_rows(sc, k, base=start, out=pair)
+                    else:
+                        ops.topk_rows(sc, k, base=start, best=pair)
+            row = best[1].to(torch.int64)
+        if self.nviews is None:
+            return best[0], row, None
+        return best[0], torch.div(row, self.nviews, rounding_mode="floor"), row % self.nviews
+
+
+def gallery_rows(features, views="mean", cosine=False):
+    """(rows [R, C] fp32, items N, V or None): the host side of Gallery -- the rows it stores, in its order."""
+    feats = np.asarray(features if isinstance(features, np.ndarray) else [np.asarray(f) for f in features])
+    if feats.ndim not in (2, 3) or feats.shape[0] < 1 or feats.shape[-1] < 1 or (feats.ndim == 3 and feats.shape[1] < 1):
+        raise ValueError("Gallery: features must be [N, V, C] or [N, C], got %s" % (feats.shape,))
+    items, nviews = feats.shape[0], None
+    if feats.ndim == 3:
+        if views == "mean":
+            feats = feats.astype(np.float64).mean(axis=1)
+        else:
+            nviews = feats.shape[1]
+            feats = feats.reshape(items * nviews, feats.shape[2])
+    if cosine:
+        feats = feats.astype(np.float64)
+        norm = np.sqrt((feats * feats).sum(axis=1, keepdims=True))
+        feats = feats / np.where(norm > 0, norm, 1.0)
+    return feats.astype(np.float32), items, nviews
+
+
+def recall_at_k(audio, gallery, ks=RECALL_KS):
+    """{k: percent} instance-level recall: every utterance audio[i][u] of every item i is a query, and it is a hit at k
+    when any of its k best gallery rows belongs to item i.  One Gallery.search at max(ks)."""
+    a = np.asarray(audio if isinstance(audio, np.ndarray) else [np.asarray(f) for f in audio], dtype=np.float32)
+    if a.ndim != 3 or a.shape[0] != gallery.items:
+        raise ValueError("recall_at_k: audio %s does not give [N, U, C] utterances for the gallery's %d items"
+                         % (a.shape, gallery.items))
+    ks = [int(k) for k in ks]
+    if not ks or min(ks) < 1:
+        raise ValueError("recall_at_k: ks must be positive, got %s" % (ks,))
+    n, u, c = a.shape
+    _, items, _ = gallery.search(a.reshape(n * u, c), max(ks))
+    hit = items.cpu().numpy() == np.repeat(np.arange(n), u)[:, None]
+    return {k: float(hit[:, :k].any(axis=1).mean() * 100.0) for k in ks}
+
+
 def get_parser():
     p = argparse.ArgumentParser(description="speech-to-image retrieval accuracy and AP@50")
     p.add_argument("--audio", required=True, help="audio_features_<switch>.pickle (N, 10, D)")
@@ -92,6 +220,9 @@ def get_parser():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--topk", type=int, default=TOPK)
     p.add_argument("--out", default=None, help="JSON output (default <audio dir>/retrieval_<split>.json)")
+    p.add_argument("--recall", action="store_true", default=False,
+                   help="add recall@1/5/10/50: all ten utterances of each item against the mean-of-views image rows, "
+                        "ranked on the GPU")
     return p
 
 
@@ -104,7 +235,13 @@ def main(argv=None):
     else:
         raise SystemExit("give --data_dir (split JSON) or --filenames for the labels")
     accu, ap = eval_feature_files(args.audio, args.image, labels, args.seed, args.topk)
-    line = json.dumps({"split": args.split, "items": len(labels), "seed": args.seed, "accu": accu, "ap50": ap})
+    result = {"split": args.split, "items": len(labels), "seed": args.seed, "accu": accu, "ap50": ap}
+    if args.recall:
+        import torch
+        gallery = Gallery(datasets.load_embedding_pickle(args.image), torch.device("cuda", torch.cuda.current_device()))
+        recall = recall_at_k(datasets.load_embedding_pickle(args.audio), gallery)
+        result.update(("recall@%d" % k, v) for k, v in recall.items())
+    line = json.dumps(result)
     out = args.out or os.path.join(os.path.dirname(os.path.abspath(args.audio)), "retrieval_%s.json" % args.split)
     with open(out, "w") as f:
         f.write(line + "\n")
