@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define S2I_ABI_VERSION 5
+#define S2I_ABI_VERSION 6
 
 /* conv geometry kinds */
 #define S2I_CONV_K1      0  /* 1x1 / nn.Linear (model.py:179, 217)                              */
@@ -91,7 +91,11 @@ typedef struct s2i_conv_desc {
   int in_groups; /* ... and the number of BatchNorm groups of its coefficient table (0 or 1 = one)               */
 } s2i_conv_desc;
 
-/* scratch bytes s2i_conv_forward needs for this descriptor (split-K slabs; 0 when not split) */
+/* scratch bytes the s2i_conv_forward* entry points need for this descriptor, whatever dtypes, bias or weight planes the
+   call passes (split-K slabs, or the weight table / fragment buffer of a thin-layer kernel; 0: none).  The kernel a launch
+   takes follows from the descriptor and the operands alone, never from the workspace: a call that passes less than its
+   plan needs (s2i_conv_plan_query says how much, never more than this) returns non-zero with the error text set and
+   launches nothing. */
 size_t s2i_conv_workspace_bytes(const s2i_conv_desc* d);
 /* number of partial rows the stats epilogue writes: part is [2][nparts][N] floats */
 int    s2i_conv_stat_parts(const s2i_conv_desc* d);
@@ -118,6 +122,15 @@ int s2i_conv_forward_cls(const s2i_conv_desc* d, const float* x, const float* cv
    with in_groups > 1 the rows of one producer group must be whole row tiles (as for `groups`). */
 int s2i_conv_forward_in(const s2i_conv_desc* d, const float* x_raw, const float* in_coef, const float* w, float* y,
                         float* part, void* ws, size_t ws_bytes, void* stream);
+/* What a forward convolution of this descriptor launches (host only; tools and the plan tests).  The operands are those of
+   the entry point that would run it: x_dtype / y_dtype as for s2i_conv_forward_dt, planes as for s2i_conv_forward_split
+   (0 = fp32 weights), whether a bias / class-bias table is passed, and d->in_act != 0 for s2i_conv_forward_in.
+   out = { kernel id (FwdKernel of csrc/s2i_igemm.h), output rows and columns per block, threads per block, grid x / y / z of
+   the main launch, K splits, 32-deep K chunks per split, K chunks, elements a table / fragment preparation launch writes
+   first (0 = none), reduction after a split (0 none, 1 sum, 2 sum then column statistics, 3 sum fused with the statistics),
+   workspace bytes the launch asks for, M, K }.  Non-zero, with out zeroed, where the plan refuses the layer in this mode. */
+int s2i_conv_plan_query(const s2i_conv_desc* d, int x_dtype, int y_dtype, int planes, int has_bias, int has_cls_bias,
+                        int out[15]);
 
 /* ---- spatially constant channels of a 3x3 conv (c_code broadcast, model.py:272-279) -----------
  * A channel that is constant over space contributes sum over the IN-BOUNDS taps of c*W: a bias that

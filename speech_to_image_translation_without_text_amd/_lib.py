@@ -26,13 +26,21 @@ PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = 0, 1, 2, 3, 4, 5
 RESAMPLE_TILE = 1024
 RESAMPLE_MAX_WINDOW = 13826
 TOPK_MAX = 64
-ABI_VERSION = 5
+ABI_VERSION = 6
 # s2i_wgrad_plan_query: the WgKernel values of csrc/s2i_igemm.h in order, and the twelve outputs
 WGRAD_KERNELS = ("f32-128x128", "f32-128x64", "f32-128x32", "f32-64x64", "f32-256x128", "f32-256x256", "f32-96x64", "f32-96x32",
                  "f32in-128x128", "b16-128x128", "b16-128x64", "b16-128x32", "b16-64x64", "b16-256x128", "b16-256x256",
                  "b16d1-64x64", "split-128x128", "split-128x64", "split-128x32", "split-64x64", "rows3-32x64", "rows3-32x32",
                  "rows3-64x128", "rows3-64x64", "rows3-64x32", "smalln-16", "smalln-32", "smalln-64")
 WGRAD_PLAN_FIELDS = ("kernel", "bm", "bn", "threads", "gx", "gy", "gz", "stage", "slabs", "ws_slabs", "K", "M")
+# s2i_conv_plan_query: the FwdKernel values of csrc/s2i_igemm.h in order, the fifteen outputs and its reduction kinds
+FWD_KERNELS = ("f32-128x128", "f32-128x64", "f32-128x32", "f32-96x128", "f32in-128x128", "f32in-128x64", "f32in-128x32",
+               "f32in-96x128", "split-128x128", "split-128x64", "split-128x32", "smalln-4", "smalln-8", "smalln-16",
+               "tconv-n4-64", "conv3-n4-16", "conv3-n4-32", "rgb-out-4", "rgb-out-8", "rgb-out-9", "rgb-out-16", "rgb-out-18",
+               "rgb-out-36", "rgb-in-1x3", "rgb-in-2x3", "rgb-in-1x4", "rgb-in-2x4", "thin-out", "thin-in-16", "thin-in-32")
+FWD_PLAN_FIELDS = ("kernel", "bm", "bn", "threads", "gx", "gy", "gz", "splitk", "cps", "nchunks", "prep_elems", "reduce",
+                   "ws_bytes", "M", "K")
+FWD_REDUCE_NONE, FWD_REDUCE_PLAIN, FWD_REDUCE_COLSTATS, FWD_REDUCE_STATS = 0, 1, 2, 3
 
 c_int, c_float, c_void_p, c_size_t, c_ll = (ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
                                             ctypes.c_size_t, ctypes.c_longlong)
@@ -73,6 +81,7 @@ _SIGNATURES = {
     "s2i_get_tuning": (c_int, [ctypes.c_char_p, ctypes.POINTER(c_int)]),
     "s2i_conv_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc)]),
     "s2i_conv_stat_parts": (c_int, [ctypes.POINTER(ConvDesc)]),
+    "s2i_conv_plan_query": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int * 15)]),
     "s2i_conv_forward": (c_int, [ctypes.POINTER(ConvDesc), P, P, P, P, P, P, P, c_size_t, P]),
     "s2i_conv_forward_cls": (c_int, [ctypes.POINTER(ConvDesc), P, P, P, P, P, P, P, P, c_size_t, P]),
     "s2i_conv_forward_in": (c_int, [ctypes.POINTER(ConvDesc), P, P, P, P, P, P, c_size_t, P]),
@@ -264,6 +273,18 @@ def wgrad_plan(d, a_dtype=DT_F32, g_dtype=DT_F32, planes=0, in_act=0):
         return None
     plan = dict(zip(WGRAD_PLAN_FIELDS, out))
     plan["kernel"] = WGRAD_KERNELS[plan["kernel"]]
+    return plan
+
+
+def conv_plan(d, x_dtype=DT_F32, y_dtype=DT_F32, planes=0, bias=False, cls_bias=False):
+    """What the forward convolution of ConvDesc d launches with these operands (s2i_conv_plan_query, host only; d.in_act
+    says apply-on-load): a dict of FWD_PLAN_FIELDS with the kernel as its FWD_KERNELS name, or None where the plan refuses
+    (s2i_last_error says why)."""
+    out = (c_int * 15)()
+    if load().s2i_conv_plan_query(ctypes.byref(d), x_dtype, y_dtype, planes, int(bool(bias)), int(bool(cls_bias)), ctypes.byref(out)):
+        return None
+    plan = dict(zip(FWD_PLAN_FIELDS, out))
+    plan["kernel"] = FWD_KERNELS[plan["kernel"]]
     return plan
 
 

@@ -675,58 +675,52 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const float* _
   }
 }
 
+// the instantiations of one tile shape: the fp32 kernel by its WT / CA32 flags, apply-on-load (plan_fwd admits it for
+// !wt && ca32 only), or the split-bf16 kernel by its plane count
 template <int BM, int BN, int WM, int WN>
-void launch_fwd(const IgemmP& p, dim3 grid, bool wt, bool ca32, hipStream_t st) {
-  if (p.in_coef) {   // apply-on-load (conv_forward_impl admits it for !wt && ca32 only)
+void launch_fwd(const FwdPlan& pl, const IgemmP& p, dim3 grid, hipStream_t st) {
+  if (pl.kernel >= FWD_F32IN_128x128) {
     hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, false, true, true>), grid, dim3(256), 0, st, p);
-    return;
-  }
-  if (wt) {
-    if (ca32) hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, true, true>), grid, dim3(256), 0, st, p);
+  } else if (pl.wt) {
+    if (pl.ca32) hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, true, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, true, false>), grid, dim3(256), 0, st, p);
   } else {
-    if (ca32) hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, false, true>), grid, dim3(256), 0, st, p);
+    if (pl.ca32) hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, false, true>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((igemm_fwd_kernel<BM, BN, WM, WN, false, false>), grid, dim3(256), 0, st, p);
   }
 }
 
 template <int BM, int BN, int WM, int WN>
-static void launch_split(const IgemmP& p, dim3 grid, int planes, hipStream_t st) {
-  if (planes == 1) hipLaunchKernelGGL((igemm_fwd_split_kernel<BM, BN, WM, WN, 1>), grid, dim3(256), 0, st, p);
-  else if (planes == 2) hipLaunchKernelGGL((igemm_fwd_split_kernel<BM, BN, WM, WN, 2>), grid, dim3(256), 0, st, p);
+void launch_split(const FwdPlan& pl, const IgemmP& p, dim3 grid, hipStream_t st) {
+  if (pl.planes == 1) hipLaunchKernelGGL((igemm_fwd_split_kernel<BM, BN, WM, WN, 1>), grid, dim3(256), 0, st, p);
+  else if (pl.planes == 2) hipLaunchKernelGGL((igemm_fwd_split_kernel<BM, BN, WM, WN, 2>), grid, dim3(256), 0, st, p);
   else hipLaunchKernelGGL((igemm_fwd_split_kernel<BM, BN, WM, WN, 3>), grid, dim3(256), 0, st, p);
 }
 
 }  // namespace
 
-int launch_igemm_fwd(const FwdPlan& pl, const IgemmP& p, dim3 grid, bool wt, bool ca32, hipStream_t st) {
-  if (pl.bm == 96) launch_fwd<96, 128, 1, 4>(p, grid, wt, ca32, st);
-  else if (pl.tile == 0) launch_fwd<128, 128, 2, 2>(p, grid, wt, ca32, st);
-  else if (pl.tile == 1) launch_fwd<128, 64, 2, 2>(p, grid, wt, ca32, st);
-  else launch_fwd<128, 32, 4, 1>(p, grid, wt, ca32, st);
+int launch_igemm_fwd(const FwdPlan& pl, const IgemmP& p, hipStream_t st) {
+  const dim3 grid(pl.gx, pl.gy, pl.gz);
+  switch (pl.kernel) {
+    case FWD_F32_128x128: case FWD_F32IN_128x128: launch_fwd<128, 128, 2, 2>(pl, p, grid, st); break;
+    case FWD_F32_128x64: case FWD_F32IN_128x64: launch_fwd<128, 64, 2, 2>(pl, p, grid, st); break;
+    case FWD_F32_128x32: case FWD_F32IN_128x32: launch_fwd<128, 32, 4, 1>(pl, p, grid, st); break;
+    case FWD_F32_96x128: case FWD_F32IN_96x128: launch_fwd<96, 128, 1, 4>(pl, p, grid, st); break;
+    case FWD_SPLIT_128x128: launch_split<128, 128, 2, 2>(pl, p, grid, st); break;
+    case FWD_SPLIT_128x64: launch_split<128, 64, 2, 2>(pl, p, grid, st); break;
+    case FWD_SPLIT_128x32: launch_split<128, 32, 4, 1>(pl, p, grid, st); break;
+    default: S2I_FAIL("igemm_fwd: kernel %d is no matrix kernel", (int)pl.kernel);
+  }
   S2I_LAUNCH_CHECK("igemm_fwd");
   return 0;
 }
 
-int launch_igemm_fwd_split(const FwdPlan& pl, const IgemmP& p, dim3 grid, int planes, hipStream_t st) {
-  if (pl.tile == 0) launch_split<128, 128, 2, 2>(p, grid, planes, st);
-  else if (pl.tile == 1) launch_split<128, 64, 2, 2>(p, grid, planes, st);
-  else launch_split<128, 32, 4, 1>(p, grid, planes, st);
-  S2I_LAUNCH_CHECK("igemm_fwd_split");
-  return 0;
-}
-
-int launch_small_n_conv(const s2i_conv_desc* d, const FwdPlan& pl, IgemmP p, hipStream_t st) {
-  // HBM-bound RGB-sized layers: VALU kernel instead of a 32-wide MFMA tile that is 7/8 padding
-  p.wt = d->wmode != 0;
-  const int lpp = pl.Ca / 4, ppw = 64 / lpp;
-  int sblocks = s2i_cdiv(pl.M, 4 * ppw);
-  if (sblocks > 2048 / pl.nphases) sblocks = 2048 / pl.nphases;   // 8 blocks per CU; the kernel strides over the rest
-  dim3 sgrid(sblocks, 1, pl.nphases);
+int launch_small_n_conv(const FwdPlan& pl, const IgemmP& p, hipStream_t st) {
+  const dim3 grid(pl.gx, pl.gy, pl.gz);
   const size_t shb = (size_t)pl.T * pl.Ca * 4 * sizeof(float);
-  if (lpp == 4) hipLaunchKernelGGL((small_n_conv_kernel<4>), sgrid, dim3(256), shb, st, p);
-  else if (lpp == 8) hipLaunchKernelGGL((small_n_conv_kernel<8>), sgrid, dim3(256), shb, st, p);
-  else hipLaunchKernelGGL((small_n_conv_kernel<16>), sgrid, dim3(256), shb, st, p);
+  if (pl.kernel == FWD_SMALLN_4) hipLaunchKernelGGL((small_n_conv_kernel<4>), grid, dim3(256), shb, st, p);
+  else if (pl.kernel == FWD_SMALLN_8) hipLaunchKernelGGL((small_n_conv_kernel<8>), grid, dim3(256), shb, st, p);
+  else hipLaunchKernelGGL((small_n_conv_kernel<16>), grid, dim3(256), shb, st, p);
   S2I_LAUNCH_CHECK("small_n_conv");
   return 0;
 }
@@ -734,7 +728,7 @@ int launch_small_n_conv(const s2i_conv_desc* d, const FwdPlan& pl, IgemmP p, hip
 int launch_splitk_reduce(const s2i_conv_desc* d, const FwdPlan& pl, const float* bias, float* y, float* part, void* ws,
                          int y16, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (d->stats && (d->N % 4) == 0 && (d->ldy % 4) == 0) {
+  if (pl.reduce == FWD_REDUCE_STATS) {
     const int Q = d->N / 4;
     int cpb = 1;
     while (cpb < Q && cpb < 256) cpb <<= 1;
@@ -752,8 +746,7 @@ int launch_splitk_reduce(const s2i_conv_desc* d, const FwdPlan& pl, const float*
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)ws, pl.splitk,
                      pl.Mrows, d->N, bias, d->act, y, d->ldy, y16);
   S2I_LAUNCH_CHECK("splitk_reduce");
-  S2I_REQUIRE(!(d->stats && y16), "conv: bf16 output with statistics needs N %% 4 == 0 on a split-K layer");
-  if (d->stats) return s2i_colstats(y, pl.Mrows, d->N, d->ldy, part, stat_parts(pl, 1), stream);
+  if (pl.reduce == FWD_REDUCE_COLSTATS) return s2i_colstats(y, pl.Mrows, d->N, d->ldy, part, stat_parts(pl, 1), stream);
   return 0;
 }
 

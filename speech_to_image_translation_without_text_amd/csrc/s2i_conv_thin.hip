@@ -1,5 +1,5 @@
 // Thin-layer and RGB kernels: convolutions with 3 (4) channels on one side, which the 32-wide matrix tiles would pad 7/8.
-// Interface: launch_thin, thin_workspace_bytes (s2i_igemm.h).
+// Interface: launch_thin (s2i_igemm.h); which layer runs on which of them is decided in s2i_conv_plan.hip.
 #include "s2i_igemm.h"
 
 namespace {
@@ -463,142 +463,48 @@ __global__ __launch_bounds__(256) void rgb_in_kernel(IgemmP p, const unsigned sh
 
 }  // namespace
 
-// thin layers (one lane per output pixel, weights as a scalar table in the workspace): 1 = few outputs, 2 = 4 inputs
-static int thin_kind(const s2i_conv_desc* d, const FwdPlan& pl) {
-  if (d->Cc != 0 || d->stats || pl.M < 4096 || pl.splitk != 1) return 0;
-  // measured (bf16 mode, batch 48): few outputs from 16 / 32 channels 113 / 66 us against 273 / 135 us for the
-  // lanes-per-pixel kernel; from 64 channels the lane-per-pixel reads (128-byte pixels, one 16-byte piece per instruction)
-  // thrash L1: 703 against 280 us, so that case stays with small_n_conv_kernel.  4 inputs to 16 / 32 outputs 78 / 43 us
-  // against 225 / 64 us on the matrix kernel; to 64 outputs (first discriminator conv, 4096 FMAs per pixel) the vector
-  // units tie with the fp32 matrix kernel (310 vs 315 us) and lose at batch 48 (152 vs 113): not taken.
-  if (d->N <= 4 && (d->kind == S2I_CONV_K3S1 || d->kind == S2I_TCONV_K4S2) && (pl.Ca % 8) == 0 && pl.Ca <= 32) return 1;
-  if (pl.Ca == 4 && d->kind == S2I_CONV_K3S1 && (d->N == 16 || d->N == 32) && (d->ldy % 8) == 0) return 2;
-  return 0;
-}
-// transposed conv to <= 4 channels from 64 stored channels on maps of whole 8 x 8 tiles: tconv_n4_tile_kernel
-static bool tile_n4_ok(const s2i_conv_desc* d, const FwdPlan& pl) {
-  return d->kind == S2I_TCONV_K4S2 && d->N <= 4 && d->Cc == 0 && !d->stats && pl.Ca == 64 && (d->H % 8) == 0 && (d->W % 8) == 0 &&
-         pl.M >= 4096 && pl.splitk == 1;
-}
-// conv3x3 to <= 4 channels from 16 / 32 / 64 stored channels on maps of whole 16 x 16 tiles: conv3_n4_tile_kernel
-static bool tile3_n4_ok(const s2i_conv_desc* d, const FwdPlan& pl) {
-  return d->kind == S2I_CONV_K3S1 && d->N <= 4 && d->Cc == 0 && !d->stats && (pl.Ca == 16 || pl.Ca == 32 || pl.Ca == 64) &&
-         (d->H % 16) == 0 && (d->W % 16) == 0 && pl.M >= 4096 && pl.splitk == 1;
-}
-static size_t thin_table_floats(const s2i_conv_desc* d, const FwdPlan& pl, int tk) {
-  return tk == 1 ? (size_t)pl.nphases * pl.T * pl.Ca * 4 : (size_t)pl.T * 4 * d->N;
-}
 
-// bf16-mode image layers on the matrix cores with pixels as columns: 1 = few outputs from bf16 input, 2 = fp32 NHWC4 input to
-// bf16 output (the dtype combination decides: these are the edges of the bf16 activation mode only)
-static int rgb_kind(const s2i_conv_desc* d, const FwdPlan& pl, int x16, int y16) {
-  if (d->Cc != 0 || d->stats || pl.M < 4096) return 0;
-  if (x16 && !y16 && d->N <= 4 && (d->kind == S2I_CONV_K3S1 || d->kind == S2I_TCONV_K4S2) &&
-      (pl.Ca == 16 || pl.Ca == 32 || pl.Ca == 64))
-    return 1;
-  if (!x16 && y16 && pl.Ca == 4 && (d->kind == S2I_CONV_K3S1 || d->kind == S2I_CONV_K4S2) &&
-      (d->N == 16 || d->N == 32 || d->N == 64) && (d->ldy % 4) == 0)
-    return 2;
-  return 0;
-}
-static size_t rgb_afrag_elems(const s2i_conv_desc* d, const FwdPlan& pl, int rk) {
-  if (rk == 1) return (size_t)pl.nphases * (pl.T * pl.Ca / 16) * 64 * 8;
-  return (size_t)((d->N + 31) / 32) * (d->kind == S2I_CONV_K4S2 ? 4 : 3) * 64 * 8;
-}
-
-size_t thin_workspace_bytes(const s2i_conv_desc* d, const FwdPlan& pl) {
-  const int tk = thin_kind(d, pl);
-  // the dtype-dependent rgb kernels need at most this much as well (bf16 fragments; sized for either)
-  size_t rgb = 0;
-  if (rgb_kind(d, pl, 1, 0)) rgb = rgb_afrag_elems(d, pl, 1) * 2;
-  if (rgb_kind(d, pl, 0, 1)) rgb = rgb_afrag_elems(d, pl, 2) * 2;
-  // the caller does not know which kernel the dtypes will select: the largest requirement of the candidates
-  size_t need = 0;
-  if (tk) { const size_t tb = thin_table_floats(d, pl, tk) * sizeof(float); need = tb > need ? tb : need; }
-  if (tile_n4_ok(d, pl)) { const size_t tb = (size_t)4 * 4 * 64 * 4 * sizeof(float); need = tb > need ? tb : need; }
-  if (tile3_n4_ok(d, pl)) { const size_t tb = (size_t)9 * pl.Ca * 4 * sizeof(float); need = tb > need ? tb : need; }
-  return rgb > need ? rgb : need;
-}
-
-int launch_thin(const s2i_conv_desc* d, const FwdPlan& pl, IgemmP p, void* ws, size_t ws_bytes, hipStream_t st) {
-  // the dispatcher's names for what it has put into p
-  const float *w = p.w, *bias = p.bias, *cls_bias = p.cls_bias, *in_coef = p.in_coef;
-  const unsigned short* wsp = p.wsp;
-  const int x16 = p.x16, y16 = p.y16;
-  if (!wsp && !cls_bias && !in_coef && tile_n4_ok(d, pl) && !y16 && ws && ws_bytes >= (size_t)4 * 4 * 64 * 4 * sizeof(float)) {
-    float* table = (float*)ws;
-    const int total = 4 * 4 * 64 * 4;
-    hipLaunchKernelGGL(thin_table_kernel, dim3(s2i_cdiv(total, 256)), dim3(256), 0, st, w, table, d->kind, d->flip, pl.T,
-                       d->wmode != 0 ? 1 : 0, d->wR, d->ldw, 64, 4, 4);
-    S2I_LAUNCH_CHECK("thin_table");
-    hipLaunchKernelGGL((tconv_n4_tile_kernel<64>), dim3((d->H / 8) * (d->W / 8) * d->B), dim3(256), 0, st, p, (const float*)table);
-    S2I_LAUNCH_CHECK("tconv_n4_tile");
-    return 0;
-  }
-  if (!wsp && !cls_bias && !in_coef && tile3_n4_ok(d, pl) && !y16 && ws && ws_bytes >= (size_t)9 * pl.Ca * 4 * sizeof(float)) {
-    float* table = (float*)ws;
-    const int total = 9 * pl.Ca * 4;
-    hipLaunchKernelGGL(thin_table_kernel, dim3(s2i_cdiv(total, 256)), dim3(256), 0, st, w, table, d->kind, d->flip, pl.T,
-                       d->wmode != 0 ? 1 : 0, d->wR, d->ldw, pl.Ca, 4, 1);
-    S2I_LAUNCH_CHECK("thin_table");
-    const dim3 g3((d->H / 16) * (d->W / 16) * d->B);
-    if (pl.Ca == 16) hipLaunchKernelGGL((conv3_n4_tile_kernel<16>), g3, dim3(256), 0, st, p, (const float*)table);
-    else hipLaunchKernelGGL((conv3_n4_tile_kernel<32>), g3, dim3(256), 0, st, p, (const float*)table);
-    S2I_LAUNCH_CHECK("conv3_n4_tile");
-    return 0;
-  }
-  const int rk = (!wsp && !cls_bias && !in_coef) ? rgb_kind(d, pl, x16, y16) : 0;
-  if (rk && ws && ws_bytes >= rgb_afrag_elems(d, pl, rk) * 2 && !(rk == 2 && bias)) {
-    unsigned short* afrag = (unsigned short*)ws;
-    const int total = (int)rgb_afrag_elems(d, pl, rk);
+int launch_thin(const s2i_conv_desc* d, const FwdPlan& pl, const IgemmP& p, void* ws, hipStream_t st) {
+  const dim3 grid(pl.gx, pl.gy, pl.gz), prep(s2i_cdiv(pl.prep_elems, 256));
+  const int wt = d->wmode != 0 ? 1 : 0;
+  if (pl.kernel >= FWD_RGB_OUT_4 && pl.kernel <= FWD_RGB_IN_2x4) {
+    // A fragments [phase][mt][ks][lane][8]: rgb_out has one row tile and k-steps of 16 (tap, channel) pairs, rgb_in a k-step
+    // per kernel row
+    const unsigned short* afrag = (const unsigned short*)ws;
+    const bool out = pl.kernel <= FWD_RGB_OUT_36;
     const int KW = d->kind == S2I_CONV_K4S2 ? 4 : 3;
-    const int MT = rk == 1 ? 1 : (d->N + 31) / 32, KS = rk == 1 ? pl.T * pl.Ca / 16 : (d->kind == S2I_CONV_K4S2 ? 4 : 3);
-    hipLaunchKernelGGL(rgb_afrag_kernel, dim3(s2i_cdiv(total, 256)), dim3(256), 0, st, w, afrag, rk == 1 ? 0 : 1, d->kind, d->flip,
-                       pl.T, d->wmode != 0 ? 1 : 0, d->wR, d->ldw, pl.Ca, KW, MT, KS, rk == 1 ? pl.nphases : 1, d->N);
+    hipLaunchKernelGGL(rgb_afrag_kernel, prep, dim3(256), 0, st, p.w, (unsigned short*)ws, out ? 0 : 1, d->kind, d->flip, pl.T, wt,
+                       d->wR, d->ldw, pl.Ca, KW, out ? 1 : (d->N + 31) / 32, out ? pl.T * pl.Ca / 16 : KW, pl.nphases, d->N);
     S2I_LAUNCH_CHECK("rgb_afrag");
-    int blocks = s2i_cdiv(pl.M, 128);
-    if (blocks > 2048) blocks = 2048;
-    if (rk == 1) {
-      dim3 g(blocks > 2048 / pl.nphases ? 2048 / pl.nphases : blocks, 1, pl.nphases);
-      if (KS == 9) hipLaunchKernelGGL((rgb_out_kernel<9>), g, dim3(256), 0, st, p, (const unsigned short*)afrag);
-      else if (KS == 18) hipLaunchKernelGGL((rgb_out_kernel<18>), g, dim3(256), 0, st, p, (const unsigned short*)afrag);
-      else if (KS == 36) hipLaunchKernelGGL((rgb_out_kernel<36>), g, dim3(256), 0, st, p, (const unsigned short*)afrag);
-      else if (KS == 4) hipLaunchKernelGGL((rgb_out_kernel<4>), g, dim3(256), 0, st, p, (const unsigned short*)afrag);
-      else if (KS == 8) hipLaunchKernelGGL((rgb_out_kernel<8>), g, dim3(256), 0, st, p, (const unsigned short*)afrag);
-      else if (KS == 16) hipLaunchKernelGGL((rgb_out_kernel<16>), g, dim3(256), 0, st, p, (const unsigned short*)afrag);
-      else S2I_FAIL("rgb_out: unexpected k-step count %d", KS);
-    } else {
-      dim3 g(blocks);
-      if (KS == 4 && MT == 2) hipLaunchKernelGGL((rgb_in_kernel<2, 4>), g, dim3(256), 0, st, p, (const unsigned short*)afrag);
-      else if (KS == 4) hipLaunchKernelGGL((rgb_in_kernel<1, 4>), g, dim3(256), 0, st, p, (const unsigned short*)afrag);
-      else if (MT == 2) hipLaunchKernelGGL((rgb_in_kernel<2, 3>), g, dim3(256), 0, st, p, (const unsigned short*)afrag);
-      else hipLaunchKernelGGL((rgb_in_kernel<1, 3>), g, dim3(256), 0, st, p, (const unsigned short*)afrag);
+    switch (pl.kernel) {
+      case FWD_RGB_OUT_4: hipLaunchKernelGGL((rgb_out_kernel<4>), grid, dim3(256), 0, st, p, afrag); break;
+      case FWD_RGB_OUT_8: hipLaunchKernelGGL((rgb_out_kernel<8>), grid, dim3(256), 0, st, p, afrag); break;
+      case FWD_RGB_OUT_9: hipLaunchKernelGGL((rgb_out_kernel<9>), grid, dim3(256), 0, st, p, afrag); break;
+      case FWD_RGB_OUT_16: hipLaunchKernelGGL((rgb_out_kernel<16>), grid, dim3(256), 0, st, p, afrag); break;
+      case FWD_RGB_OUT_18: hipLaunchKernelGGL((rgb_out_kernel<18>), grid, dim3(256), 0, st, p, afrag); break;
+      case FWD_RGB_OUT_36: hipLaunchKernelGGL((rgb_out_kernel<36>), grid, dim3(256), 0, st, p, afrag); break;
+      case FWD_RGB_IN_1x3: hipLaunchKernelGGL((rgb_in_kernel<1, 3>), grid, dim3(256), 0, st, p, afrag); break;
+      case FWD_RGB_IN_2x3: hipLaunchKernelGGL((rgb_in_kernel<2, 3>), grid, dim3(256), 0, st, p, afrag); break;
+      case FWD_RGB_IN_1x4: hipLaunchKernelGGL((rgb_in_kernel<1, 4>), grid, dim3(256), 0, st, p, afrag); break;
+      default: hipLaunchKernelGGL((rgb_in_kernel<2, 4>), grid, dim3(256), 0, st, p, afrag); break;
     }
     S2I_LAUNCH_CHECK("rgb_conv");
     return 0;
   }
-  const int tk = (!wsp && !cls_bias && !in_coef) ? thin_kind(d, pl) : 0;
-  if (tk && ws && ws_bytes >= thin_table_floats(d, pl, tk) * sizeof(float)) {
-    p.wt = d->wmode != 0;
-    float* table = (float*)ws;
-    const int Kk = tk == 1 ? pl.Ca : 4, Nn = tk == 1 ? 4 : d->N;
-    const int total = (tk == 1 ? pl.nphases : 1) * pl.T * Kk * Nn;
-    hipLaunchKernelGGL(thin_table_kernel, dim3(s2i_cdiv(total, 256)), dim3(256), 0, st, w, table, d->kind, d->flip, pl.T,
-                       d->wmode != 0 ? 1 : 0, d->wR, d->ldw, Kk, Nn, tk == 1 ? pl.nphases : 1);
-    S2I_LAUNCH_CHECK("thin_table");
-    int blocks = s2i_cdiv(pl.M, 256);
-    if (tk == 1) {
-      if (blocks > 4096 / pl.nphases) blocks = 4096 / pl.nphases;
-      // the table has 4 columns per (tap, channel); columns beyond N read the zero padding of the packed weights
-      hipLaunchKernelGGL(thin_out_kernel, dim3(blocks, 1, pl.nphases), dim3(256), 0, st, p, (const float*)table);
-    } else {
-      if (blocks > 4096) blocks = 4096;
-      // thin_kind admits 16 and 32 outputs only (64 ties with the matrix kernel, see there)
-      if (d->N == 16) hipLaunchKernelGGL((thin_in_kernel<16>), dim3(blocks), dim3(256), 0, st, p, (const float*)table);
-      else hipLaunchKernelGGL((thin_in_kernel<32>), dim3(blocks), dim3(256), 0, st, p, (const float*)table);
-    }
-    S2I_LAUNCH_CHECK("thin_conv");
-    return 0;
+  // the weight table [phase][tap][k][n]: 4 columns per gathered channel, or thin_in's N columns per input channel
+  const float* table = (const float*)ws;
+  const bool in = pl.kernel == FWD_THIN_IN_16 || pl.kernel == FWD_THIN_IN_32;
+  hipLaunchKernelGGL(thin_table_kernel, prep, dim3(256), 0, st, p.w, (float*)ws, d->kind, d->flip, pl.T, wt, d->wR, d->ldw, pl.Ca,
+                     in ? d->N : 4, pl.nphases);
+  S2I_LAUNCH_CHECK("thin_table");
+  switch (pl.kernel) {
+    case FWD_TCONV_N4_64: hipLaunchKernelGGL((tconv_n4_tile_kernel<64>), grid, dim3(256), 0, st, p, table); break;
+    case FWD_CONV3_N4_16: hipLaunchKernelGGL((conv3_n4_tile_kernel<16>), grid, dim3(256), 0, st, p, table); break;
+    case FWD_CONV3_N4_32: hipLaunchKernelGGL((conv3_n4_tile_kernel<32>), grid, dim3(256), 0, st, p, table); break;
+    case FWD_THIN_OUT: hipLaunchKernelGGL(thin_out_kernel, grid, dim3(256), 0, st, p, table); break;
+    case FWD_THIN_IN_16: hipLaunchKernelGGL((thin_in_kernel<16>), grid, dim3(256), 0, st, p, table); break;
+    default: hipLaunchKernelGGL((thin_in_kernel<32>), grid, dim3(256), 0, st, p, table); break;
   }
-  return -1;
+  S2I_LAUNCH_CHECK("thin_conv");
+  return 0;
 }

@@ -194,10 +194,55 @@ __device__ __forceinline__ void split4(const f32x4 v, u32x2 (&out)[NP]) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------
+// What the operands of a forward convolution are (derived once from the entry point's arguments by fwd_mode)
+struct FwdMode {
+  int x16, y16;         // x / y stored as bf16 (s2i_conv_forward_dt)
+  int planes;           // bf16 planes of pre-split weights (s2i_conv_forward_split), 0 = fp32 weights
+  bool bias, cls_bias;  // a bias / class-bias table is passed
+  bool in_act;          // x is the producer's raw output, activated while it is staged (s2i_conv_forward_in)
+};
+
+// The kernel a planned forward convolution launches.  The matrix families list their tile shapes in one order (F32 and
+// F32IN all four, SPLIT the first three), so a family's first value + the shape's index is the kernel; the WT / CA32 template
+// flags of igemm_fwd_kernel and the plane count are plan fields.  fwd_kernels[] (s2i_conv_plan.hip) holds each one's rows and
+// columns per block and its block size; s2i_conv_plan_query reports these values.
+enum FwdKernel {
+  FWD_F32_128x128, FWD_F32_128x64, FWD_F32_128x32, FWD_F32_96x128,           // igemm_fwd_kernel<BM, BN, ..., WT, CA32>
+  FWD_F32IN_128x128, FWD_F32IN_128x64, FWD_F32IN_128x32, FWD_F32IN_96x128,   // ... <..., false, true, INACT>: apply-on-load
+  FWD_SPLIT_128x128, FWD_SPLIT_128x64, FWD_SPLIT_128x32,                     // igemm_fwd_split_kernel<..., planes>
+  FWD_SMALLN_4, FWD_SMALLN_8, FWD_SMALLN_16,                                 // small_n_conv_kernel<Ca / 4>
+  FWD_TCONV_N4_64,                                                           // tconv_n4_tile_kernel<64>
+  FWD_CONV3_N4_16, FWD_CONV3_N4_32,                                          // conv3_n4_tile_kernel<CCH>; Ca = 64: <32>, two chunks
+  FWD_RGB_OUT_4, FWD_RGB_OUT_8, FWD_RGB_OUT_9, FWD_RGB_OUT_16, FWD_RGB_OUT_18, FWD_RGB_OUT_36,   // rgb_out_kernel<KSTEPS>
+  FWD_RGB_IN_1x3, FWD_RGB_IN_2x3, FWD_RGB_IN_1x4, FWD_RGB_IN_2x4,            // rgb_in_kernel<MT, KH>
+  FWD_THIN_OUT,                                                              // thin_out_kernel
+  FWD_THIN_IN_16, FWD_THIN_IN_32,                                            // thin_in_kernel<NOUT>
+  FWD_KERNEL_COUNT
+};
+struct FwdKernelInfo { int bm, bn, threads; };   // output rows (pixels of one phase) and columns per block, block size
+
+// What follows the main launch where K is split
+enum FwdReduce {
+  FWD_REDUCE_NONE,       // K is not split, or the kernel does not split it
+  FWD_REDUCE_PLAIN,      // splitk_reduce_kernel
+  FWD_REDUCE_COLSTATS,   // splitk_reduce_kernel, then s2i_colstats over y (statistics where N or ldy is no multiple of 4)
+  FWD_REDUCE_STATS       // splitk_reduce_stats_kernel
+};
+
+// Everything a forward launch needs, decided by plan_fwd; the launchers take it as const
 struct FwdPlan {
-  int T, K, Ca, Ho, Wo, M, nphases, tile, bm, gridM, gridN, nchunks, splitk, cps;
-  int small_n;   // <= 4 output channels of a 3x3 / transposed layer: small_n_conv_kernel where no thin kernel takes the layer
+  int T, K, Ca, Ho, Wo, M, nphases;
   long long Mrows;
+  // the matrix tiling of the layer (plan_fwd_tiles): the statistics rows and the split eligibility follow from it alone.
+  // A vector-unit kernel that takes the layer ignores the split but the workspace still holds its slabs, as it always has.
+  int bm, gridM, gridN, nchunks, splitk, cps;
+  FwdKernel kernel;
+  bool wt, ca32;        // template flags of igemm_fwd_kernel
+  int planes;           // bf16 planes of the SPLIT family (else 0)
+  int threads, gx, gy, gz;
+  int prep_elems;       // elements thin_table_kernel / rgb_afrag_kernel writes into the workspace before the main launch (0: none)
+  FwdReduce reduce;
+  size_t ws_bytes;      // the larger of the split-K slabs and the table / fragment buffer; the launch refuses less
 };
 
 // What the operands of a weight gradient are (derived once from the entry point's dtypes, planes and coefficient table)
@@ -241,16 +286,19 @@ static inline size_t wg_workspace_bytes(const WgPlan& pl, int N) { return (size_
 
 // Unit interfaces.  A launch_* function returns 0 after a launch, 1 with the error text set.  None of them is exported.
 #pragma GCC visibility push(hidden)
-// s2i_conv_fwd.hip: grid and the byte windows of p come from the dispatcher (conv_forward_impl)
-int launch_igemm_fwd(const FwdPlan& pl, const IgemmP& p, dim3 grid, bool wt, bool ca32, hipStream_t st);
-int launch_igemm_fwd_split(const FwdPlan& pl, const IgemmP& p, dim3 grid, int planes, hipStream_t st);
-int launch_small_n_conv(const s2i_conv_desc* d, const FwdPlan& pl, IgemmP p, hipStream_t st);
+// s2i_conv_plan.hip: both return 0, or 1 with the error text set.  fwd_mode names the operands of an entry point's
+// arguments; plan_fwd decides the launch, or refuses a layer that no kernel takes in this mode.
+int fwd_mode(int x16, int y16, int planes, bool bias, bool cls_bias, bool in_coef, FwdMode* mode);
+int plan_fwd(const s2i_conv_desc* d, const FwdMode& mode, FwdPlan* pl);
+// s2i_conv_fwd.hip: the matrix families (the byte windows of p come from conv_forward_impl), small_n_conv_kernel and the
+// reduction of a split
+int launch_igemm_fwd(const FwdPlan& pl, const IgemmP& p, hipStream_t st);
+int launch_small_n_conv(const FwdPlan& pl, const IgemmP& p, hipStream_t st);
 int launch_splitk_reduce(const s2i_conv_desc* d, const FwdPlan& pl, const float* bias, float* y, float* part, void* ws,
                          int y16, void* stream);
-// s2i_conv_thin.hip: launch_thin tries the thin-layer and RGB kernels in dispatch order and returns -1 when none of them
-// takes the layer; thin_workspace_bytes is the largest table / fragment buffer any of them could ask for (0: none applies)
-int launch_thin(const s2i_conv_desc* d, const FwdPlan& pl, IgemmP p, void* ws, size_t ws_bytes, hipStream_t st);
-size_t thin_workspace_bytes(const s2i_conv_desc* d, const FwdPlan& pl);
+// s2i_conv_thin.hip: the thin-layer and RGB kernels (FWD_TCONV_N4_64 ... FWD_THIN_IN_32) after their table / fragment
+// preparation in ws
+int launch_thin(const s2i_conv_desc* d, const FwdPlan& pl, const IgemmP& p, void* ws, hipStream_t st);
 // s2i_wgrad_plan.hip: both return 0, or 1 with the error text set.  wg_mode names the operands of an entry point's
 // arguments; plan_wgrad decides the launch, or refuses a layer that no kernel takes in this mode.
 int wg_mode(int a16, int g16, int planes, bool a_coef, WgMode* mode);

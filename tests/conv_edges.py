@@ -7,7 +7,8 @@ census schema, so conv_replay.replay_conv / replay_wgrad run them unchanged, and
 
   why        one line on what the shape is for
   reach      the plan features the record claims (REACH below); tests/test_conv_edges_cpu.py derives them from the
-             planners' host queries and asserts them, tests/test_conv_edges_gpu.py replays the record in fp64
+             planners' host queries (conv_plan / wgrad_plan below) and asserts them, tests/test_conv_edges_gpu.py replays
+             the record in fp64
   tile_rows  the value of ops.TILE_ROWS the replay runs under (0 = the planner's choice)
   tune       planner knobs (_lib.tuning) the replay runs under
 
@@ -109,18 +110,18 @@ def _tiles(make, heights):
 def _table():
     t = []
     # ---- fp32 forward ------------------------------------------------------------------------------------------------
-    t += _tiles(lambda tr: fwd("k3s1", 5, 8, 64, 128, "M = 320: 96-row tiles end on 32 rows, 128-row tiles on 64; K split "
-                               "with a short last split", {0: ["short-last-split"], 96: ["rowtail-96", "short-last-split"],
+    t += _tiles(lambda tr: fwd("k3s1", 5, 8, 64, 128, "M = 320: 96-row tiles (the planner's choice) end on 32 rows, 128-row tiles on 64; "
+                               "K split with a short last split", {0: ["rowtail-96", "short-last-split"], 96: ["rowtail-96", "short-last-split"],
                                                            128: ["rowtail-128", "short-last-split"]}[tr], tile_rows=tr),
                 (0, 96, 128))
     t += _tiles(lambda tr: fwd("k3s1", 11, 8, 64, 256, "M = 704: row tail under both heights, two column tiles",
-                               {0: ["short-last-split"], 96: ["rowtail-96", "short-last-split"],
+                               {0: ["rowtail-96", "short-last-split"], 96: ["rowtail-96", "short-last-split"],
                                 128: ["rowtail-128", "short-last-split"]}[tr], tile_rows=tr), (0, 96, 128))
     t += _tiles(lambda tr: fwd("k3s1", 5, 8, 40, 136, "row tail, K = 360 (tail 8), N = 136 (tail 8); Cx % 32 != 0 takes the "
                                "general gather", {0: ["rowtail-96", "coltail", "ktail"], 96: ["rowtail-96", "coltail", "ktail"],
                                                   128: ["rowtail-128", "coltail", "ktail"]}[tr], tile_rows=tr), (0, 96, 128))
     t += _tiles(lambda tr: fwd("k4s2", 7, 16, 64, 128, "M = 448: five 96-row or four 128-row tiles, 64 rows in the last",
-                               {0: [], 96: ["rowtail-96"], 128: ["rowtail-128"]}[tr], tile_rows=tr), (0, 96, 128))
+                               {0: ["rowtail-96"], 96: ["rowtail-96"], 128: ["rowtail-128"]}[tr], tile_rows=tr), (0, 96, 128))
     t.append(fwd("k4s2", 3, 16, 64, 64, "128 x 64 tile, M = 192: the second row tile half filled, K split", ["rowtail-128x64"]))
     t.append(fwd("k3s1", 5, 8, 32, 32, "128 x 32 tile, M = 320, unsplit: per-tile partial sums with a 64-row last tile",
                  ["rowtail-128x32"]))
@@ -149,7 +150,7 @@ def _table():
                  tile_rows=96))
     # ---- fp32 input gradient -----------------------------------------------------------------------------------------
     t += _tiles(lambda tr: dgrad("k3s1", 5, 8, 128, 64, "flipped 3x3 input gradient, M = 320",
-                                 {0: ["short-last-split"], 96: ["rowtail-96", "short-last-split"],
+                                 {0: ["rowtail-96", "short-last-split"], 96: ["rowtail-96", "short-last-split"],
                                   128: ["rowtail-128", "short-last-split"]}[tr], tile_rows=tr), (0, 96, 128))
     t += _tiles(lambda tr: dgrad("k3s1", 11, 8, 136, 40, "flipped 3x3 input gradient, M = 704, N = 136 (column tail), K = "
                                  "360 (K tail)", {96: ["rowtail-96", "coltail", "ktail"],
@@ -232,7 +233,8 @@ def record_id(i, rec):
 
 
 # ---- what a record's plan reaches, from the planners' host queries ---------------------------------------------------
-# The library loads and plans without a device.  What the queries cannot tell is restated from the planner and marked so.
+# The library loads and plans without a device: s2i_conv_plan_query and s2i_wgrad_plan_query name the kernel, tile and split
+# of a launch.  What the bf16 unit's queries cannot tell is restated from its planner and marked so.
 def _cdiv(a, b):
     return -(-a // b)
 
@@ -265,8 +267,8 @@ def wgrad_desc(rec):
 
 
 def conv_plan(rec):
-    """dict(M, nphases, K, nchunks, splitk, cps, bm or None, BN, reach) of a conv_raw / conv_any record under its own
-    tile_rows and knobs."""
+    """dict(M, nphases, K, nchunks, splitk, cps, bm, BN, reach) of a conv_raw / conv_any record under its own tile_rows and
+    knobs: the fp32 path's tile, K split and chunk counts are what s2i_conv_plan_query says."""
     import ctypes
     from speech_to_image_translation_without_text_amd import _lib
     lib = _lib.load()
@@ -281,30 +283,14 @@ def conv_plan(rec):
         if rec["fast"]:
             return _bf16_plan(rec, lib, M, nph, Ho, Wo)
         d = conv_desc(rec)
-        ws = lib.s2i_conv_workspace_bytes(ctypes.byref(d))
-        slab = M * nph * N * 4
-        assert ws % slab == 0, (ws, slab)                 # no thin-kernel table at these sizes
-        sk = max(ws // slab, 1)
-        # rows per tile: the statistics rows of an unsplit plan are gridM x nphases.  A forced height does not depend on the
-        # K split, so it is read from the unsplit twin of the descriptor; the planner's own choice does, so it is known only
-        # where the record itself is unsplit and has statistics.  N <= 64 has 128-row tiles only (plan_fwd: "96 x 128 only").
-        bm = None
-        if N <= 64:
-            bm = 128
-        elif rec.get("tile_rows", 0) or (sk == 1 and rec["stats"]):
-            parts = lib.s2i_conv_stat_parts(ctypes.byref(conv_desc(rec, stats=1, nosplit=1, act=0)))
-            assert parts > 0 and parts % nph == 0, parts
-            c128, c96 = _cdiv(M, 128), _cdiv(M, 96)
-            if c128 != c96:
-                bm = 128 if parts // nph == c128 else 96
-                assert parts // nph == _cdiv(M, bm), (parts, M)
+        told = _lib.conv_plan(d, int(rec["x"][1] == "bf16"), int(rec["out_dtype"] == "bf16"), 0, rec["bias"], rec["cls_bias"])
+        assert told is not None, lib.s2i_last_error()
+        assert told["kernel"].startswith("f32-") and (told["M"], told["K"]) == (M, K), told      # the matrix tiles at these sizes
         if rec["stats"]:
             assert lib.s2i_conv_stat_parts(ctypes.byref(d)) > 0, lib.s2i_last_error()
-    BN = 128 if N > 64 else (64 if N > 32 else 32)
-    nchunks = _cdiv(K, 32)
-    cps = _cdiv(nchunks, sk)
+    bm, BN, sk, cps, nchunks = (told[f] for f in ("bm", "bn", "splitk", "cps", "nchunks"))
     one_tile = M < (96 if N > 64 else 128)
-    tail = bm is not None and M % bm != 0 and not one_tile
+    tail = M % bm != 0 and not one_tile
     if tail:
         reach.add("rowtail-%d" % bm if N > 64 else "rowtail-128x%d" % BN)
     if one_tile:

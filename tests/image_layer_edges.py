@@ -1,15 +1,15 @@
 """Hand-written launches of the image-layer convolutions -- 3 (4) channels on one side -- on every branch of their dispatch.
 
 GET_IMAGE_G's conv3x3 -> RGB, the first discriminator conv, the input gradients of both and the RGB conv's weight gradient
-do not run on the matrix tiles that tests/conv_edges.py covers but on a family of hand-written kernels, which launch_thin()
-(csrc/s2i_conv_thin.hip), conv_forward_impl() (csrc/s2i_conv.hip) and plan_wgrad() choose between on shape and dtype alone.
+do not run on the matrix tiles that tests/conv_edges.py covers but on a family of hand-written kernels, which plan_fwd()
+(csrc/s2i_conv_plan.hip) and plan_wgrad() (csrc/s2i_wgrad_plan.hip) choose between on shape and dtype alone.
 Every production shape has maps of 64 x 64 and larger, where the tile kernels and the matrix tiles win, so the step, ragged
 and eval censuses launch only part of the family, and all of it on square maps with whole blocks.  The records below use
 the census schema (conv_replay.replay_conv / replay_wgrad run them unchanged) with the extra keys of tests/conv_edges.py:
 
   why        one line on what the shape is for
   reach      the dispatch branch (BRANCHES) and the edges (EDGES) the record claims; tests/test_image_layer_edges_cpu.py
-             derives both from the restated dispatch below, pinned to the library's workspace queries, and asserts them;
+             derives both from the library's plan queries (conv_plan / wgrad_plan below) and asserts them;
              tests/test_image_layer_edges_gpu.py replays the record in fp64
   ldy        (n3 records only) the row stride of the output, 4 floats for N = 3: ops.py always launches with ldy = N, so
              these records are launched through the C ABI by the GPU test
@@ -21,9 +21,8 @@ discriminator conv's input gradient in bf16 activation mode, fp32 NHWC4 in / bf1
 GET_IMAGE_G's input gradient.
 
 small_n_conv_kernel<4> and <8> (16 and 32 channels) have no record: thin_out_kernel takes every such launch at or above
-the M >= 4096 gate both sit behind, whatever the dtypes, bias or map size, as long as the caller passes the workspace that
-s2i_conv_workspace_bytes asks for -- which ops.py always does.  They stay in the library as the path of a C caller that
-passes none; the tags small-n-4 / small-n-8 are not claimed.  The tile kernels own whole 8 x 8 / 16 x 16 tiles and the
+the M >= 4096 gate both sit behind, whatever the dtypes, bias or map size, so no plan names them (they used to be what a C
+caller got who passed no workspace; such a call is refused now).  The tags small-n-4 / small-n-8 are not claimed.  The tile kernels own whole 8 x 8 / 16 x 16 tiles and the
 weight-gradient stream whole pixel groups (W >= 16), so neither has a pixel tail; their edge is the odd batch and the
 odd last trip."""
 import conv_edges as E
@@ -258,85 +257,50 @@ def in_family(rec):
     return rec["kind"] != ops.CONV_K1 and rec["g"][0][3] == 4 and not rec["swap"]
 
 
-# ---- the dispatch, restated --------------------------------------------------------------------------------------------
-# RESTATED from launch_thin / thin_kind / tile_n4_ok / tile3_n4_ok / rgb_kind (csrc/s2i_conv_thin.hip), conv_forward_impl
-# (csrc/s2i_conv.hip), launch_small_n_conv (csrc/s2i_conv_fwd.hip) and plan_wgrad (csrc/s2i_wgrad_plan.hip); no host query
-# names the kernel a launch takes.  The restatement is pinned to the library where a query can tell: the workspace of an
-# unsplit plan is the largest table / fragment buffer among the candidate kernels, and the weight gradient's workspace holds
-# 512 slabs exactly when the stream kernel applies.
+# ---- what a record's plan reaches, from the planners' host queries -----------------------------------------------------
+# s2i_conv_plan_query / s2i_wgrad_plan_query (_lib.conv_plan / wgrad_plan) name the kernel, its pixels per block and its grid;
+# the library loads and plans without a device.  The tags below only rename the kernels and describe the input.
 def _cdiv(a, b):
     return -(-a // b)
 
 
+def _branch(kernel, N, Ca, nph):
+    """The BRANCHES tag of a FWD_KERNELS name."""
+    if kernel.startswith("f32-"):
+        return "n4-igemm" if N <= 4 else "igemm"
+    if kernel == "thin-out":
+        return "thin-out-4phase" if nph == 4 else "thin-out"
+    if kernel == "tconv-n4-64":
+        return "tile-tconv64"
+    if kernel.startswith("conv3-n4-"):
+        return "tile3-%d" % Ca                           # conv3-n4-32 runs 64 channels in two chunks
+    for prefix, tag in (("rgb-out-", "rgb-out-k"), ("smalln-", "small-n-")):
+        if kernel.startswith(prefix):
+            return tag + kernel[len(prefix):]
+    return kernel                                        # rgb-in-MTxKH, thin-in-N
+
+
 def conv_plan(rec):
-    """dict(branch, reach, M, nphases, splitk, ppb, blocks) of a conv_raw / conv_any record."""
-    import ctypes
+    """dict(branch, reach, M, nphases, splitk, ppb, blocks, Ho, Wo) of a conv_raw / conv_any record."""
     from speech_to_image_translation_without_text_amd import _lib
-    lib = _lib.load()
     B, H, W, Ca = rec["x"][0]
     kind, N = rec["kind"], rec["N"]
     ldy = rec.get("ldy", N)
-    x16, y16 = rec["x"][1] == "bf16", rec["out_dtype"] == "bf16"
     nph = 4 if kind == ops.TCONV_K4S2 else 1
     Ho, Wo = E._geom(kind, H, W)
-    M = B * Ho * Wo
-    T = 4 if kind == ops.TCONV_K4S2 else ops._TAPS[kind]
     assert not rec["fast"] and not rec["cvec"] and not rec["cls_bias"], rec
-    d = E.conv_desc(rec, ldy=ldy)
-    ws = lib.s2i_conv_workspace_bytes(ctypes.byref(d))
-    assert ws > 0 or M < 4096, (lib.s2i_last_error(), rec)
-    gate = not rec["stats"] and M >= 4096
-    few = N <= 4 and kind in (ops.CONV_K3S1, ops.TCONV_K4S2)
-    # candidates that do not depend on the K split
-    rgb1 = gate and few and Ca in (16, 32, 64)
-    rgb2 = gate and Ca == 4 and kind in (ops.CONV_K3S1, ops.CONV_K4S2) and N in (16, 32, 64) and ldy % 4 == 0
-    rgb_bytes = 0
-    if rgb1:
-        rgb_bytes = nph * (T * Ca // 16) * 64 * 8 * 2
-    if rgb2:
-        rgb_bytes = _cdiv(N, 32) * (4 if kind == ops.CONV_K4S2 else 3) * 64 * 8 * 2
-    # the K split: a workspace that is a whole number (>= 2) of output slabs is the split plan's.  A split plan is pinned by
-    # ws >= rgb_bytes only: the query says nothing on which of small-n-16 / rgb-out / the matrix tiles such a launch takes,
-    # that part is restatement alone.  Likewise the n4-igemm tail counts 128-row tiles, the only height plan_fwd has for
-    # N <= 64.
-    slab = M * nph * N * 4
-    sk = ws // slab if (ws % slab == 0 and ws >= 2 * slab) else 1
-    one = gate and sk == 1
-    tile_t = one and kind == ops.TCONV_K4S2 and N <= 4 and Ca == 64 and H % 8 == 0 and W % 8 == 0
-    tile_3 = one and kind == ops.CONV_K3S1 and N <= 4 and Ca in (16, 32, 64) and H % 16 == 0 and W % 16 == 0
-    thin1 = one and few and Ca % 8 == 0 and Ca <= 32
-    thin2 = one and Ca == 4 and kind == ops.CONV_K3S1 and N in (16, 32) and ldy % 8 == 0
-    need = max(nph * T * Ca * 4 * 4 if thin1 else 0, T * 4 * N * 4 if thin2 else 0, 4 * 4 * 64 * 4 * 4 if tile_t else 0,
-               9 * Ca * 4 * 4 if tile_3 else 0, rgb_bytes)
-    if sk == 1:
-        assert ws == need, ("workspace %d, the candidates' largest table %d" % (ws, need), rec)
-    else:
-        assert ws >= rgb_bytes, (ws, rgb_bytes, rec)
-    # the order of launch_thin, then conv_forward_impl
-    ppb, cap = None, None
-    if tile_t and not y16:
-        branch = "tile-tconv64"
-    elif tile_3 and not y16:
-        branch = "tile3-%d" % Ca
-    elif rgb1 and x16 and not y16:
-        branch, ppb, cap = "rgb-out-k%d" % (T * Ca // 16), 128, 2048 // nph
-    elif rgb2 and not x16 and y16 and not rec["bias"]:
-        branch, ppb, cap = "rgb-in-%dx%d" % (_cdiv(N, 32), 4 if kind == ops.CONV_K4S2 else 3), 128, 2048
-    elif thin1:
-        branch, ppb, cap = "thin-out" + ("-4phase" if nph == 4 else ""), 256, 4096 // nph
-    elif thin2:
-        branch, ppb, cap = "thin-in-%d" % N, 256, 4096
-    elif few and not rec["stats"] and Ca in (16, 32, 64) and M >= 4096:
-        branch, ppb, cap = "small-n-%d" % (Ca // 4), 4 * (64 // (Ca // 4)), 2048 // nph
-    elif N <= 4:
-        branch, ppb, cap = "n4-igemm", 128, None
-    else:
-        branch = "igemm"
-    reach = {branch}
+    told = _lib.conv_plan(E.conv_desc(rec, ldy=ldy), int(rec["x"][1] == "bf16"), int(rec["out_dtype"] == "bf16"), 0, rec["bias"])
+    assert told is not None, (_lib.load().s2i_last_error(), rec)
+    M = told["M"]
+    assert M == B * Ho * Wo, told
+    branch = _branch(told["kernel"], N, Ca, nph)
+    # pixels per block of the kernels with a pixel loop; the grid-stride loop runs more than once where the grid is capped
+    ppb = told["bm"] if branch in PIXEL_LOOP else None
     blocks = None if ppb is None else _cdiv(M, ppb)
+    reach = {branch}
     if ppb is not None and M % ppb:
         reach.add("pixtail")
-    if cap is not None and blocks > cap:
+    if ppb is not None and told["gx"] < blocks:
         reach.add("grid-cap")
     if H != W:
         reach.add("nonsquare")
@@ -346,30 +310,24 @@ def conv_plan(rec):
         reach.add("n3")
     if M == 4096 and branch not in ("n4-igemm", "igemm"):
         reach.add("threshold")
-    return dict(branch=branch, reach=reach, M=M, nphases=nph, splitk=sk, ppb=ppb, blocks=blocks, Ho=Ho, Wo=Wo)
+    return dict(branch=branch, reach=reach, M=M, nphases=nph, splitk=told["splitk"], ppb=ppb, blocks=blocks, Ho=Ho, Wo=Wo)
 
 
 def wgrad_plan(rec):
-    import ctypes
     from speech_to_image_translation_without_text_amd import _lib
-    lib = _lib.load()
     d = E.wgrad_desc(rec)
     a16, g16 = rec["a"][1] == "bf16", rec["g"][1] == "bf16"
     B, H, W, Ca = rec["a"][0]
     N = rec["g"][0][3]
-    Ho, Wo = ops._geom(rec["kind"], H, W)
-    M = B * Ho * Wo
-    K = ops._TAPS[rec["kind"]] * (Ca + rec["cvec"])
-    ws = lib.s2i_wgrad_workspace_bytes_dt(ctypes.byref(d), int(a16), int(g16))
-    assert ws > 0 and ws % (K * N * 4) == 0, (ws, K, N, lib.s2i_last_error())
-    small = (rec["kind"] == ops.CONV_K3S1 and not rec["cvec"] and N == 4 and Ca in (16, 32, 64) and W >= 16 and M >= 32768)
-    assert (ws // (K * N * 4) == 512) == small, ("slabs %d, stream kernel expected: %s" % (ws // (K * N * 4), small), rec)
+    told = _lib.wgrad_plan(d, int(a16), int(g16))
+    assert told is not None, (_lib.load().s2i_last_error(), rec)
+    M, K = told["M"], told["K"]
     reach = set()
-    if small:
+    if told["kernel"].startswith("smalln-"):
         assert not g16
         branch = "wg-small-n-%d" % (Ca // 4)
         ppw = 64 // (Ca // 4)
-        ngroups, stride = M // ppw, 512 * 4
+        ngroups, stride = M // ppw, told["gx"] * 4
         assert M % ppw == 0
         # a wave starts at group g0 < stride, takes pairs (g, g + stride) while g + stride < ngroups, then one more if g < ngroups
         for g0 in range(stride):
@@ -386,7 +344,7 @@ def wgrad_plan(rec):
     reach.add(branch)
     if H != W:
         reach.add("nonsquare")
-    return dict(branch=branch, reach=reach, M=M, K=K, N=N, splitk=ws // (K * N * 4))
+    return dict(branch=branch, reach=reach, M=M, K=K, N=N, splitk=told["ws_slabs"])
 
 
 def plan(rec):

@@ -201,8 +201,7 @@ def split_plan(rec, planes):
         plan = E.conv_plan(rec)
         ok = conv_eligible(rec)
         reach = set(plan["reach"])
-        # the split kernels have 128-row tiles only (conv_forward_impl requires it), so a row tail follows from M alone, also
-        # where conv_plan cannot tell the tile height from the statistics rows (M = 192: two tiles under either height)
+        # the split kernels have 128-row tiles only (plan_fwd requires it), so a row tail follows from M alone
         M, N = plan["M"], rec["N"]
         if M > 128 and M % 128:
             reach.add("rowtail-128" if N > 64 else "rowtail-128x%d" % plan["BN"])

@@ -1,10 +1,9 @@
 """The edge table (tests/conv_edges.py) reaches what it claims, and the train step's census does not.
 
-The planners are host code and the library loads without a device, so every record's plan is derived here from the
-queries that ops.py itself uses (workspace bytes -> K split, statistics rows of an unsplit plan -> row tiles and tile
-height, bf16 statistics rows / weight layout -> pixels and images per tile); conv_edges.conv_plan / wgrad_plan say which
-few facts are restated from the planner instead (the weight gradient's tile shape, which no query reports, and the
-persistent form of the 256-pixel kernel).  No GPU."""
+The planners are host code and the library loads without a device, so every record's plan is asked of them here: the
+fp32 forward's tile, K split and chunk counts of s2i_conv_plan_query, the weight gradient's of s2i_wgrad_plan_query; the
+bf16 unit has no such query yet, so conv_edges._bf16_plan derives pixels and images per tile from its statistics rows /
+weight layout and restates the persistent form of the 256-pixel kernel, and says so.  No GPU."""
 import json
 import os
 import sys

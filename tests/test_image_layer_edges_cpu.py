@@ -1,10 +1,10 @@
 """The image-layer table (tests/image_layer_edges.py) reaches the dispatch branches it claims, and the censuses do not.
 
-No host query names the kernel a launch takes, so image_layer_edges.conv_plan / wgrad_plan restate the dispatch order of
-launch_thin / conv_forward_impl / plan_wgrad and pin the restatement to the library's own queries (the library loads and
-plans without a device): the workspace of an unsplit plan must equal the largest table or fragment buffer among the
-candidate kernels, and the weight gradient's workspace must hold 512 slabs exactly when the stream kernel applies.
-No GPU."""
+image_layer_edges.conv_plan / wgrad_plan ask the library which kernel a launch takes (s2i_conv_plan_query,
+s2i_wgrad_plan_query: the library loads and plans without a device) and only rename it and describe the input: pixel tail
+and strided grid from the reported pixels per block and grid, H != W, bias, N = 3, the gate M.  What the Python restatement
+of the dispatch said of every forward record before the query existed is kept in tests/golden/fwd_record_plans.json and
+compared in tests/test_fwd_plan_cpu.py.  No GPU."""
 import os
 import sys
 

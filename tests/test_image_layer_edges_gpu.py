@@ -2,8 +2,8 @@
 suites.
 
 The convolutions with 3 (4) channels on one side run on ten hand-written kernels (csrc/s2i_conv_thin.hip, small_n_conv_kernel
-in s2i_conv_fwd.hip, small_n_wgrad_kernel in s2i_wgrad.hip) that launch_thin / conv_forward_impl / plan_wgrad choose between
-on shape and dtype alone.  tests/test_image_layer_edges_cpu.py derives the branch of every launch of the step census and of
+in s2i_conv_fwd.hip, small_n_wgrad_kernel in s2i_wgrad.hip) that plan_fwd / plan_wgrad choose between on shape and dtype
+alone.  tests/test_image_layer_edges_cpu.py derives the branch of every launch of the step census and of
 the B = 23 census: production runs the tile kernels (conv3_n4_tile<16|32>, tconv_n4_tile<64>), thin_in_kernel<16|32>,
 rgb_in_kernel<1,3>, <2,3>, <2,4> and small_n_wgrad_kernel, all on square maps of 32 x 32 and larger with whole blocks and
 without bias.  Asserted there:
@@ -43,8 +43,9 @@ No class needed a wider bound and no kernel was found wrong: all 98 records hold
 gradients sit far below their bound because K x N = (9 Ca) x 4 sums are split over 512 slabs.  The 98 replays take about 3 s;
 the pixel-tail mutant was rejected in all 29 replays that have one, H and W exchanged in all 31, exchanged phases in all 21,
 the missing bias in all 5, the zeroed tap in all 75.  The one dead instantiation the table turned up, thin_in_kernel<64>
-(thin_kind admits 16 and 32 outputs only), is removed from the library; small_n_conv_kernel<4> / <8> are reachable only by
-a C caller that passes no workspace (tests/image_layer_edges.py) and stay.
+(thin_kind admits 16 and 32 outputs only), is removed from the library; small_n_conv_kernel<4> / <8> were reachable only by
+a C caller that passed no workspace (tests/image_layer_edges.py); no plan names them now, and the last test below holds the
+rule that replaced that fallback: a short workspace is refused.
 """
 import ctypes
 import os
@@ -111,9 +112,11 @@ def _output_of(rec):
     return (tuple(rec["grad_shape"]), torch.float32)
 
 
-def _launch_ldy(rec, stash):
+def _launch_ldy(rec, stash, contract=None):
     """Stands in for ops.conv_raw / conv_any for a record with ldy > N: the same descriptor with the record's row stride,
-    launched through s2i_conv_forward_dt into a sentinel-filled buffer.  Returns the N written columns as a view."""
+    launched through s2i_conv_forward_dt into a sentinel-filled buffer.  Returns the N written columns as a view.
+    contract = a FWD_KERNELS name: the launch gets exactly the workspace s2i_conv_plan_query asks for and must be planned
+    onto that kernel; before it, the same call four bytes short must be refused and write nothing."""
     from speech_to_image_translation_without_text_amd import _lib, ops
 
     def run(kind, x, *args, bias=None, out_dtype=torch.float32, **kw):
@@ -127,10 +130,24 @@ def _launch_ldy(rec, stash):
         d = E.conv_desc(rec, ldy=ldy)
         n = B * Ho * Wo * ldy
         buf = torch.full((n + GUARD,), SENTINEL, device=x.device)
-        ws = _torch_empty((max(lib.s2i_conv_workspace_bytes(ctypes.byref(d)), 16) // 4,), device=x.device)
-        _lib.check(lib.s2i_conv_forward_dt(ctypes.byref(d), x.data_ptr(), ops._dt(x), None, packed.data_ptr(), LH.P(bias), None,
-                                           buf.data_ptr(), _lib.DT_F32, None, ws.data_ptr(), ws.numel() * 4, _lib.stream()),
-                   "s2i_conv_forward_dt")
+        ws_bytes = max(lib.s2i_conv_workspace_bytes(ctypes.byref(d)), 16)
+        if contract is not None:
+            told = _lib.conv_plan(d, ops._dt(x), _lib.DT_F32, 0, bias is not None)
+            assert told["kernel"] == contract and 4 < told["ws_bytes"] <= ws_bytes and told["ws_bytes"] % 4 == 0, told
+            ws_bytes = told["ws_bytes"]
+        ws = _torch_empty((ws_bytes // 4,), device=x.device)
+
+        def launch(y, nbytes):
+            return lib.s2i_conv_forward_dt(ctypes.byref(d), x.data_ptr(), ops._dt(x), None, packed.data_ptr(), LH.P(bias), None,
+                                           y.data_ptr(), _lib.DT_F32, None, ws.data_ptr(), nbytes, _lib.stream())
+        if contract is not None:
+            untouched = torch.full((n + GUARD,), float("nan"), device=x.device)
+            assert launch(untouched, ws_bytes - 4) != 0, "a workspace four bytes short was accepted"
+            assert b"workspace" in lib.s2i_last_error(), lib.s2i_last_error()
+            torch.cuda.synchronize()
+            assert bool(torch.isnan(untouched).all()), "the refused launch wrote into y"
+            stash["refused"] = True
+        _lib.check(launch(buf, ws_bytes), "s2i_conv_forward_dt")
         torch.cuda.synchronize()
         stash.update(buf=buf, y=buf[:n].view(B, Ho, Wo, ldy))
         return stash["y"][..., :N], None, 0
@@ -240,3 +257,25 @@ def test_image_layer_replay_matches_fp64(gpu, index):
     if "ldy" not in rec:
         assert _output_of(rec) in made, "%s: the output was not allocated through the sentinel wrapper: %s" % (what, made)
     torch.cuda.empty_cache()
+
+
+def test_short_workspace_is_refused_and_the_planned_one_suffices(gpu):
+    """The plan never looks at the workspace.  GET_IMAGE_G's 3x3 to 3 channels in rows of four floats, one 64 x 64 image of
+    16 channels (M = 4096, the smallest M the thin kernels take), is planned onto conv3_n4_tile_kernel<16>, the parent's
+    branch tile3-16, whatever the caller passes: four bytes under the planned workspace the call returns non-zero, names the
+    workspace and leaves a NaN-filled y untouched (it used to run silently on another kernel); with exactly the planned
+    bytes it holds the fp64 bound of the table above."""
+    from speech_to_image_translation_without_text_amd import ops
+    from speech_to_image_translation_without_text_amd._lib import ACT_TANH
+    _default_planner()
+    rec = IE.fwd("k3s1", 1, 64, 64, 16, 3, "one 64 x 64 image: the workspace contract", ["tile3-16", "n3", "threshold"], act=ACT_TANH,
+                 N=3, ldy=4)
+    plan = IE.plan(rec)
+    assert plan["reach"] == set(rec["reach"]) and plan["M"] == 4096, plan
+    stash = {}
+    with torch.no_grad(), pytest.MonkeyPatch.context() as mp:
+        mp.setattr(torch, "empty", _sentinel_empty([]))
+        mp.setattr(ops, "conv_raw", _launch_ldy(rec, stash, contract="conv3-n4-16"))
+        mp.setattr(ops, "conv_any", _launch_ldy(rec, stash, contract="conv3-n4-16"))
+        C.replay_conv(rec, LH.gen_rec(gpu, rec), gpu, "workspace-contract", LEDGER, extra=_conv_extra(plan, stash))
+    assert stash.get("refused"), "the replay did not go through the contract launch"

@@ -1,6 +1,7 @@
 """The split-mode table (tests/split_planes.py) reaches what it claims, its plane reference and probe operands are what the
 GPU module takes them for, and the train step's census reaches none of it.  Everything is derived from the planners' host
-queries (conv_edges.conv_plan under tile_rows = 128, s2i_conv_split_eligible, s2i_wgrad_plan_query with planes).  No GPU."""
+queries (conv_edges.conv_plan under tile_rows = 128, which asks s2i_conv_plan_query; s2i_conv_split_eligible;
+s2i_wgrad_plan_query with planes).  No GPU."""
 import ctypes
 import json
 import os
@@ -43,7 +44,7 @@ def test_record_reaches_what_it_claims(index, planes):
     assert plan["split"] == ("fallback" not in rec["reach"]), plan
     if S.is_conv(rec):
         assert plan["tile"] in S.FWD_TILES
-        if plan["split"] and rec["N"] > 64 and plan["bm"] is not None:
+        if plan["split"] and rec["N"] > 64:
             assert plan["bm"] == 128, plan
         if rec["cls_bias"]:
             assert rec["w_offset"] != 0 and plan["splitk"] == 1
