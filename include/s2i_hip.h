@@ -385,6 +385,31 @@ int s2i_spatial_sum(const float* src, int ld, int B, int HW, int C, float* dst, 
                     size_t ws_bytes, void* stream);
 size_t s2i_spatial_sum_workspace_bytes(int B, int HW, int C);
 
+/* ---- differentiable augmentation of discriminator inputs, fused into the image layout conversion (csrc/s2i_diffaug.hip) ----
+   x: fp32 NCHW [N][3][H][W], H == W, H even; table: DEVICE fp32 [N][8] of uniforms in [0, 1), row n =
+   (u_b, u_s, u_c, u_tx, u_ty, u_cx, u_cy, unused); policy: a mask of the bits below; y: fp32 NHWC4 [N][H][W][4], channel 3
+   exactly 0.  The stages apply in the order colour, translation, cutout; a stage whose bit is clear is the identity, and
+   policy 0 writes what s2i_nchw_to_nhwc(.., Cp = 4) writes, bit for bit.  All arithmetic is fp32.
+   colour:      b = u_b - 0.5, s = 2 u_s, k = u_c + 0.5; m = mean of the image's 3 H W raw values, p = mean of the pixel's
+                three raw channels;  y_c = ((x_c + b) - (p + b)) s + (p + b);  z_c = (y_c - (m + b)) k + (m + b)
+   translation: S = int(H / 8 + 0.5), n_t = 2 S + 1; tx = min(int(u_tx * n_t), n_t - 1) - S (one fp32 multiply, truncated),
+                ty likewise; out[r][q] = z[r + ty][q + tx] where that source lies inside the image, exactly 0 elsewhere
+   cutout:      c = int(H / 2 + 0.5), n_c = H + 1 - c % 2; oy = min(int(u_cy * n_c), n_c - 1), ox likewise; rows
+                [oy - c / 2, oy - c / 2 + c) x columns [ox - c / 2, ox - c / 2 + c) of the translated image become exactly 0
+   s2i_diffaug_backward is the exact adjoint: dy is the gradient of y as NHWC rows of `dtype` with pixel stride ld >= 4
+   (the convention of s2i_nhwc_to_nchw_dt), dx fp32 NCHW [N][3][H][W];  g_z[r][q] = dy[r - ty][q - tx] where that pixel
+   exists and is not cut out, else 0;  g_y = k g_z + (1 - k) mean_image(g_z);  g_x_c = s g_y_c + (1 - s) mean_c(g_y).
+   Each direction is one launch, or two with S2I_DIFFAUG_COLOR (a per-image reduction into the caller's workspace of
+   s2i_diffaug_workspace_bytes(N, H, W) bytes, summed in a fixed order: the same inputs give the same bits; ws may be NULL
+   without the colour bit).  x and y must be 16-byte aligned.  Bad arguments (a null pointer, N < 1, H != W, H odd, an
+   unknown policy bit, ld < 4, a workspace too small) return non-zero before any launch. */
+enum { S2I_DIFFAUG_COLOR = 1, S2I_DIFFAUG_TRANSLATION = 2, S2I_DIFFAUG_CUTOUT = 4, S2I_DIFFAUG_ALL = 7 };
+size_t s2i_diffaug_workspace_bytes(int N, int H, int W);
+int s2i_diffaug_forward(const float* x, const float* table, int policy, float* y, int N, int H, int W, void* ws,
+                        size_t ws_bytes, void* stream);
+int s2i_diffaug_backward(int dtype, const void* dy, int ld, const float* table, int policy, float* dx, int N, int H, int W,
+                         void* ws, size_t ws_bytes, void* stream);
+
 /* ---- CA_NET reparameterisation + KL (model.py:182-200, trainer.py:54-58) -------------------- */
 /* h = GLU output [B][2E] = [mu | logvar];  c = eps*exp(0.5*logvar) + mu */
 int s2i_reparam_forward(const float* h, const float* eps, int B, int E, float* c, void* stream);

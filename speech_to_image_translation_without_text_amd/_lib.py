@@ -26,6 +26,7 @@ PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = 0, 1, 2, 3, 4, 5
 RESAMPLE_TILE = 1024
 RESAMPLE_MAX_WINDOW = 13826
 TOPK_MAX = 64
+DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4
 ABI_VERSION = 6
 # s2i_wgrad_plan_query: the WgKernel values of csrc/s2i_igemm.h in order, and the twelve outputs
 WGRAD_KERNELS = ("f32-128x128", "f32-128x64", "f32-128x32", "f32-64x64", "f32-256x128", "f32-256x256", "f32-96x64", "f32-96x32",
@@ -141,6 +142,9 @@ _SIGNATURES = {
     "s2i_image_grid_u8": (c_int, [P, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll, c_int, c_int, P, P, P]),
     "s2i_spatial_sum": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_size_t, P]),
     "s2i_spatial_sum_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "s2i_diffaug_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "s2i_diffaug_forward": (c_int, [P, P, c_int, P, c_int, c_int, c_int, P, c_size_t, P]),
+    "s2i_diffaug_backward": (c_int, [c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_size_t, P]),
     "s2i_reparam_forward": (c_int, [P, P, c_int, c_int, P, P]),
     "s2i_reparam_backward": (c_int, [P, P, P, P, P, c_int, c_int, P, P]),
     "s2i_kl_forward": (c_int, [P, c_int, P, c_int, c_int, c_int, P, P]),

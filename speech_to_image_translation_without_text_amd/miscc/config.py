@@ -50,6 +50,7 @@ def _defaults():
             "INCEPTION_WEIGHTS": "",   # local Inception-v3 state_dict file: '' = no IS / FID / NLPP during training
             "STATE": "",               # Model/state.pt of an earlier run: continue it exactly (trainer.load_state)
             "STATE_EVERY": 0,          # write Model/state.pt every this many epochs and after the last; 0 = never
+            "DIFFAUG": "",             # 'color,translation,cutout' (any subset): augment every discriminator input; '' = off
         },
         "GAN": {"EMBEDDING_DIM": 128, "DF_DIM": 64, "GF_DIM": 64, "Z_DIM": 100,
                 "NETWORK_TYPE": "default", "R_NUM": 2, "B_CONDITION": True},

@@ -325,12 +325,15 @@ class _DNet(nn.Module):
             self.jointConv = Block3x3_leakRelu(ndf * 8 + self.ef_dim, ndf * 8)
             self.uncond_logits = nn.Sequential(nn.Conv2d(ndf * 8, 1, kernel_size=4, stride=4), nn.Sigmoid())
 
-    def forward(self, x_var, c_code=None, groups=1, need_features=True, taps=None):
+    def forward(self, x_var, c_code=None, groups=1, need_features=True, taps=None, aug=None):
         """`groups` > 1 (not part of the reference signature): x_var stacks that many independent batches
         along dim 0 — the real / wrong / fake passes of trainer.py:390-392 in one launch per layer — and
         every BatchNorm keeps separate statistics per batch, updating its running statistics in that order.
-        `taps` (a list, tests only) receives the NHWC output of every LeakyReLU block in forward order."""
-        x = ops.ToNHWC.apply(x_var, 4)
+        `taps` (a list, tests only) receives the NHWC output of every LeakyReLU block in forward order.
+        `aug` = (table, policy): differentiable augmentation of the input inside the layout conversion
+        (ops.DiffAugToNHWC); the fp32 device table has one row of 8 uniforms per image of x_var, so 3 B rows in
+        real | wrong | fake order for a stacked pass."""
+        x = ops.ToNHWC.apply(x_var, 4) if aug is None else ops.DiffAugToNHWC.apply(x_var, aug[0], aug[1])
         x_code = self.img_code_s16(x, groups, taps, defer_last=bool(self._tower))
         hook = getattr(self, 'after_s16_hook', None)
         if hook is not None and x_code.requires_grad:

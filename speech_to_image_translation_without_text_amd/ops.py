@@ -1194,6 +1194,72 @@ class ToNHWC(torch.autograd.Function):
         return dx, None
 
 
+_DIFFAUG_BITS = {"color": _lib.DIFFAUG_COLOR, "translation": _lib.DIFFAUG_TRANSLATION, "cutout": _lib.DIFFAUG_CUTOUT}
+
+
+def diffaug_policy(spec):
+    """'color,translation,cutout' (any order, any subset; '' = none) -> the policy mask of s2i_diffaug_forward."""
+    policy = 0
+    for token in str(spec).split(","):
+        token = token.strip()
+        if not token:
+            continue
+        if token not in _DIFFAUG_BITS:
+            raise ValueError("unknown augmentation %r: expected a comma-separated subset of %s"
+                             % (token, ", ".join(sorted(_DIFFAUG_BITS))))
+        policy |= _DIFFAUG_BITS[token]
+    return policy
+
+
+def _diffaug_workspace(lib, policy, B, H, W, device):
+    """(pointer, bytes) of the per-image partial sums: only the colour stage reduces."""
+    if not policy & _lib.DIFFAUG_COLOR:
+        return None, 0
+    ws = _ws.get(lib.s2i_diffaug_workspace_bytes(B, H, W), device)
+    return ptr(ws), ws.numel() * 4
+
+
+class DiffAugToNHWC(torch.autograd.Function):
+    """ToNHWC of a (B,3,H,H) image batch to NHWC4 with differentiable augmentation applied on the way (s2i_diffaug_forward):
+    colour, translation and cutout as `policy` (diffaug_policy) selects, drawn per image from row b of the fp32 device
+    `table` (B, 8) of uniforms.  The backward is the exact adjoint, to x only, and launches nothing when x needs no
+    gradient (the real and wrong batches)."""
+
+    @staticmethod
+    def forward(ctx, x, table, policy):
+        lib = _lib_ready()
+        x = x.contiguous()
+        B, C, H, W = x.shape
+        policy = int(policy)
+        if C != 3:
+            raise _lib.S2IError("DiffAugToNHWC takes 3-channel images, got %d channels" % C)
+        if table.dtype != torch.float32 or tuple(table.shape) != (B, 8) or table.device != x.device:
+            raise _lib.S2IError("DiffAugToNHWC: the table must be fp32 (%d, 8) on %s, got %s %s on %s"
+                                % (B, x.device, table.dtype, tuple(table.shape), table.device))
+        table = table.detach().contiguous()
+        out = torch.empty((B, H, W, 4), dtype=torch.float32, device=x.device)
+        ws, wsb = _diffaug_workspace(lib, policy, B, H, W, x.device)
+        check(lib.s2i_diffaug_forward(ptr(x), ptr(table), policy, ptr(out), B, H, W, ws, wsb, stream()),
+              "s2i_diffaug_forward")
+        ctx.policy = policy
+        ctx.save_for_backward(table)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        lib = _lib_ready()
+        table, = ctx.saved_tensors
+        dk, ld = _rows_view(dout)
+        B, H, W, _ = dout.shape
+        dx = torch.empty((B, 3, H, W), dtype=torch.float32, device=dout.device)
+        ws, wsb = _diffaug_workspace(lib, ctx.policy, B, H, W, dout.device)
+        check(lib.s2i_diffaug_backward(_dt(dk), ptr(dk), ld, ptr(table), ctx.policy, ptr(dx), B, H, W, ws, wsb, stream()),
+              "s2i_diffaug_backward")
+        return dx, None, None
+
+
 class ToNCHW(torch.autograd.Function):
     """(B,H,W,Cp) -> (B,C,H,W), dropping padding channels."""
 

@@ -33,6 +33,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from ._lib import S2IError
 from .miscc.config import cfg
 from .miscc.utils import mkdir_p
 from .model import D_NET64, D_NET128, D_NET256, D_NET512, D_NET1024, G_NET, INCEPTION_V3  # noqa: F401
@@ -384,6 +385,7 @@ class condGANTrainer(object):
         self._graph = None
         self._labels_dev = None
         self._g_pass = []
+        self._aug = None      # (uniforms (num_Ds, 4, B, 8), policy mask) of the current step while TRAIN.DIFFAUG is set
         if os.environ.get("S2I_GRAPH", "0") == "1":
             self.enable_graph()
         # Inception-v3 scoring (off by default): per step, (softmax, pool3) device rows of [fake; real]
@@ -513,6 +515,36 @@ class condGANTrainer(object):
                 return None
             d.after_s16_hook = hook
 
+    # -- differentiable augmentation of the discriminators' inputs (TRAIN.DIFFAUG) ----------------
+    def draw_aug(self, B, device):
+        """The step's uniforms while TRAIN.DIFFAUG names a policy, else None (and nothing is drawn): (num_Ds, 4, B, 8) from
+        the device generator; [d, 0 / 1 / 2] are the tables of discriminator d's real / wrong / fake pass in train_Dnet and
+        [d, 3] the table of its pass of the generator update."""
+        if not ops.diffaug_policy(cfg.TRAIN.DIFFAUG):
+            return None
+        return torch.rand(self.num_Ds, 4, B, 8, device=device)
+
+    def _set_aug(self, aug, B):
+        policy = ops.diffaug_policy(cfg.TRAIN.DIFFAUG)
+        if aug is None:
+            if policy:
+                raise ValueError("TRAIN.DIFFAUG = %r: train_step needs the step's uniforms (draw_aug)" % cfg.TRAIN.DIFFAUG)
+            self._aug = None
+            return
+        if not policy:
+            raise ValueError("train_step was given augmentation uniforms but TRAIN.DIFFAUG is empty")
+        if tuple(aug.shape) != (self.num_Ds, 4, B, 8) or aug.dtype != torch.float32:
+            raise ValueError("augmentation uniforms must be fp32 %s, got %s %s"
+                             % ((self.num_Ds, 4, B, 8), aug.dtype, tuple(aug.shape)))
+        self._aug = (aug.detach().contiguous(), policy)
+
+    def _aug_of(self, idx, slot, slots=1):
+        """(table, policy) of discriminator idx: the rows of `slots` consecutive passes from `slot` on, or None."""
+        if self._aug is None:
+            return None
+        table, policy = self._aug
+        return table[idx, slot:slot + slots].reshape(-1, 8), policy
+
     # -- D update (trainer.py:375-427) ----------------------------------------------------------------------------
     def _d_logits(self, idx):
         """Conditional/unconditional probabilities of the real, wrong and fake batches.  When the batch is a
@@ -526,12 +558,13 @@ class condGANTrainer(object):
             self._d_expected[idx] = 1 if stacked else 3     # backward firings of the img_code_s16 hook
         if stacked:
             x = torch.cat((self.real_imgs[idx], self.wrong_imgs[idx], self.fake_imgs[idx].detach()), 0)
-            logits, _ = _unwrap(netD)(x, mu.repeat(3, 1), groups=3, need_features=False)
+            logits, _ = _unwrap(netD)(x, mu.repeat(3, 1), groups=3, need_features=False, aug=self._aug_of(idx, 0, 3))
             self._stacked_logits = logits
             return [[l[g * B:(g + 1) * B] for l in logits] for g in range(3)]
         self._stacked_logits = None
-        return [netD(self.real_imgs[idx], mu)[0], netD(self.wrong_imgs[idx], mu)[0],
-                netD(self.fake_imgs[idx].detach(), mu)[0]]
+        return [netD(self.real_imgs[idx], mu, aug=self._aug_of(idx, 0))[0],
+                netD(self.wrong_imgs[idx], mu, aug=self._aug_of(idx, 1))[0],
+                netD(self.fake_imgs[idx].detach(), mu, aug=self._aug_of(idx, 2))[0]]
 
     def _d_loss(self, idx):
         u = cfg.TRAIN.COEFF.UNCOND_LOSS
@@ -601,7 +634,7 @@ class condGANTrainer(object):
         try:
             fake = self.fake_imgs[i].detach().requires_grad_(True)
             mu = self.mu.detach().requires_grad_(True)
-            outputs, x_active = self.netsD[i](fake, mu)
+            outputs, x_active = self.netsD[i](fake, mu, aug=self._aug_of(i, 3))
             errG = ops.BCELoss.apply(outputs[0], 1.0, 1.0)
             if len(outputs) > 1 and u > 0:
                 errG = errG + ops.BCELoss.apply(outputs[1], 1.0, u)
@@ -693,7 +726,11 @@ class condGANTrainer(object):
         their kernel nodes are re-issued as plain launches from one C call per piece (s2i_plan_replay, include/s2i_hip.h):
         hipGraphLaunch itself is slower than the Python step it replaces on ROCm 7.2.
         executor="graph": hipGraphLaunch of each piece.  Single process only: an RCCL all-reduce inside a recording is
-        not exercised here."""
+        not exercised here.  Not with TRAIN.DIFFAUG: a recording would replay the uniforms it was captured with, so this
+        raises S2IError while a policy is set, and so does a step that is given uniforms after enable_graph()."""
+        if ops.diffaug_policy(cfg.TRAIN.DIFFAUG):
+            raise S2IError("enable_graph: TRAIN.DIFFAUG = %r draws new uniforms every step, which a recorded step "
+                                    "would not see; run the eager step" % cfg.TRAIN.DIFFAUG)
         # warm-up and capture run on one private stream: autograd's AccumulateGrad nodes remember the stream they were
         # created on, and one that lives on the (non-capturing) default stream invalidates the capture
         if executor not in ("plan", "graph"):
@@ -860,7 +897,11 @@ class condGANTrainer(object):
                 f.write(json.dumps(rec) + '\n')
         return rec
 
-    def train_step(self, real_imgs, wrong_imgs, txt_embedding, class_labels, noise, eps=None):
+    def train_step(self, real_imgs, wrong_imgs, txt_embedding, class_labels, noise, eps=None, aug=None):
+        """`aug`: the step's augmentation uniforms (draw_aug) while TRAIN.DIFFAUG is set, None otherwise."""
+        self._set_aug(aug, noise.shape[0])
+        if self._aug is not None and self._graph is not None:
+            raise S2IError("TRAIN.DIFFAUG cannot run under enable_graph(): a recorded step would replay stale uniforms")
         out = self._dispatch_step(real_imgs, wrong_imgs, txt_embedding, class_labels, noise, eps)
         if self.inception_model is not None:
             self._inception_pass(real_imgs[-1])
@@ -1008,7 +1049,8 @@ class condGANTrainer(object):
             for step, data in enumerate(self.data_loader, 0):
                 _, real, wrong, emb, labels = self.prepare_data(data)
                 noise.normal_(0, 1)
-                errD_total, errG_total, kl_loss = self.train_step(real, wrong, emb, labels, noise[:emb.shape[0]])
+                aug = self.draw_aug(emb.shape[0], dev)      # after the noise; nothing is drawn while TRAIN.DIFFAUG is empty
+                errD_total, errG_total, kl_loss = self.train_step(real, wrong, emb, labels, noise[:emb.shape[0]], aug=aug)
                 if step == 0 and self.gpus[0] == 0:
                     print('[%d/%d][%d/%d] Loss_D: %.2f Loss_G: %.2f'
                           % (epoch, self.max_epoch, step, self.num_batches, errD_total.item(), errG_total.item()))
