@@ -410,6 +410,40 @@ int s2i_diffaug_forward(const float* x, const float* table, int policy, float* y
 int s2i_diffaug_backward(int dtype, const void* dy, int ld, const float* table, int policy, float* dx, int N, int H, int W,
                          void* ws, size_t ws_bytes, void* stream);
 
+/* ---- SpecAugment of a log-mel training batch: masks drawn and applied on the device (csrc/s2i_specaug.hip) -------------
+   x, y: fp32 [B][T][40] (the S2I_LOGMEL_NHWC batch), 16-byte aligned; they may be the same buffer.  valid: DEVICE int32
+   [B]; n = valid[b] (clamped to [0, T]) is the number of leading rows of utterance b the masks may touch; rows at or after
+   n are copied unchanged.  freq_masks, time_masks in [0, 8]; freq_width in [0, 20]; time_width >= 0; time_ratio in (0, 1];
+   T <= 419430 (40 T < 2^24: the fp32 conversions below are exact).
+   draws:  utterance b has 2 (freq_masks + time_masks) uniforms u_0, u_1, ...; nothing is uploaded.  Group g of four is
+           Philox4x32-10 on key (seed mod 2^32, seed div 2^32) and counter (step mod 2^32, step div 2^32, b, g): ten rounds
+           (c0, c1, c2, c3) -> (hi(0xCD9E8D57 c2) ^ c1 ^ k0, lo(0xCD9E8D57 c2), hi(0xD2511F53 c0) ^ c3 ^ k1, lo(0xD2511F53 c0)),
+           hi / lo the halves of the 64-bit product, with k0 += 0x9E3779B9, k1 += 0xBB67AE85 (mod 2^32) between rounds.
+           Output word r_i of group g gives u_{4g+i} = (float)(r_i >> 8) * 2^-24, in [0, 1).  Mask k (frequency masks
+           first, then time masks) takes u = u_{2k}, u' = u_{2k+1}.  The same (seed, step, b) gives the same masks on any
+           grid and in any batch.
+   masks:  int() truncates one fp32 product.
+           frequency: f = min(int(u (float)(freq_width + 1)), freq_width); f0 = min(int(u' (float)(40 - f + 1)), 40 - f);
+                      bins [f0, f0 + f) of rows [0, n)
+           time:      W = min(time_width, int(time_ratio (float)n)); t = min(int(u (float)(W + 1)), W);
+                      t0 = min(int(u' (float)(n - t + 1)), n - t); rows [t0, t0 + t), all bins; n == 0 or W == 0: nothing
+   value:  every masked cell of utterance b becomes m_b = S_b / (float)(40 n), S_b the fp32 sum of its 40 n unmasked inputs
+           in a fixed order (no atomics; the same inputs give the same bits): the 10 n sixteen-byte pieces of rows [0, n)
+           are cut into segs = min(64, max(1, 10 T div 1024)) runs of chunk = ceil(10 n / segs) consecutive pieces; thread j
+           of a run's 256 adds pieces j, j + 256, ... in that order into four lanes starting at 0; the lanes fold
+           (a0 + a1) + (a2 + a3); a wave's 64 lanes by an xor butterfly (offsets 32 .. 1); the four waves ((w0 + w1) + w2)
+           + w3; the segs run sums, zero-padded to 64, by the same butterfly.  A term passes through at most
+           d(T) = ceil(ceil(10 T / segs) / 256) + 17 additions (22 at T = 128, 21 at T = 2048).
+   At most two launches on `stream` with no host round trip: the run sums into the caller's workspace of
+   s2i_specaug_workspace_bytes(B) bytes, then a copy-or-mask in 16-byte pieces, four per thread; with x == y only pieces
+   that hold a masked cell are written.  freq_masks == time_masks == 0 writes y = x bit for bit (one launch, none with
+   x == y; ws may be NULL).  Bad arguments (a null pointer, B < 1, T < 1, T too large, misalignment, a count, width or
+   ratio outside its range, a workspace too small) return non-zero before any launch. */
+size_t s2i_specaug_workspace_bytes(int B);
+int s2i_specaug(const float* x, const int* valid, int B, int T, float* y, int freq_masks, int freq_width, int time_masks,
+                int time_width, float time_ratio, unsigned long long seed, unsigned long long step, void* ws,
+                size_t ws_bytes, void* stream);
+
 /* ---- CA_NET reparameterisation + KL (model.py:182-200, trainer.py:54-58) -------------------- */
 /* h = GLU output [B][2E] = [mu | logvar];  c = eps*exp(0.5*logvar) + mu */
 int s2i_reparam_forward(const float* h, const float* eps, int B, int E, float* c, void* stream);

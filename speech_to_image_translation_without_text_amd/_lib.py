@@ -145,6 +145,9 @@ _SIGNATURES = {
     "s2i_diffaug_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "s2i_diffaug_forward": (c_int, [P, P, c_int, P, c_int, c_int, c_int, P, c_size_t, P]),
     "s2i_diffaug_backward": (c_int, [c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_size_t, P]),
+    "s2i_specaug_workspace_bytes": (c_size_t, [c_int]),
+    "s2i_specaug": (c_int, [P, P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_float, ctypes.c_ulonglong,
+                            ctypes.c_ulonglong, P, c_size_t, P]),
     "s2i_reparam_forward": (c_int, [P, P, c_int, c_int, P, P]),
     "s2i_reparam_backward": (c_int, [P, P, P, P, P, c_int, c_int, P, P]),
     "s2i_kl_forward": (c_int, [P, c_int, P, c_int, c_int, c_int, P, P]),

@@ -24,6 +24,15 @@ statistics stay per rank, as under DDP; rank 0's running statistics are the ones
 
 state_dict() / load_state_dict() carry the whole training state (weights, Adam moments and step counts in torch.optim.Adam's
 own state_dict form for either optimiser, the epoch and the learning rate): a fresh trainer that loads it continues bit for bit.
+
+`specaug='freq=2x8,time=2x40,ratio=0.2'` (ops.specaug_policy; default '': off, and then no draw, launch or allocation is
+added) masks every training batch in front of features(): SpecAugment's frequency and time masks over the
+64 * cap_lens[b] frames the LSTM consumes, masked cells set to the utterance's mean (ops.specaug).  The masks of a step
+are a function of (specaug_seed, steps, b) alone, `steps` being the counter before the step's increment, so there is no
+generator state: `steps` is already in state_dict(), and a trainer that loads a state continues the mask sequence exactly.
+A checkpoint without training state (save(); the CLIs' plain --resume epoch_N.pth) restarts the counter at 0, so its
+masks repeat the run's first ones: that path carries no Adam moments either and was never exact.  step_features, embed,
+evaluate and save never see a mask.
 """
 import copy
 import warnings
@@ -36,13 +45,15 @@ from . import _lib, ops, retrieval
 
 class HeadTrainer:
     def __init__(self, model, lr=1e-3, weight_decay=1e-5, step_size=30, gamma=0.2, loss_diff=1, loss_same=1, jel=True,
-                 l1=False, lambda_l1=1, distill=False, distill_T=2, lambda_distill=1, fused_adam=False, distributed=False):
+                 l1=False, lambda_l1=1, distill=False, distill_T=2, lambda_distill=1, fused_adam=False, distributed=False,
+                 specaug='', specaug_seed=0):
         if model.rnn_layers != 1:
             raise _lib.S2IError("HeadTrainer supports rnn_layers=1 (the reference's default)")
         self.model = model.eval()
         self.distributed = bool(distributed)
         self.world = torch.distributed.get_world_size() if self.distributed else 1
         self.step_size, self.gamma, self.epoch, self.steps = int(step_size), gamma, 0, 0
+        self.specaug, self.specaug_seed = ops.specaug_policy(specaug), int(specaug_seed)      # None: off
         self.flat = self.optimizer = self.scheduler = None
         if fused_adam or self.distributed:
             from .trainer import FlatNet
@@ -117,7 +128,12 @@ class HeadTrainer:
 
     def step(self, mel_nhwc, cap_lens, image_feature, label):
         """Sort by length, conv features, lstm_sentence, the loss, backward, Adam.  Returns the loss dict (device tensors:
-        loss, loss_jel, loss_l1, loss_distill, accu)."""
+        loss, loss_jel, loss_l1, loss_distill, accu).  With a `specaug` policy the batch is masked first (ops.specaug, into a
+        new tensor: the caller's batch is left alone) over each utterance's 64 * cap_lens[b] frames, the ones the LSTM
+        consumes, with the step counter as the generator's counter."""
+        if self.specaug is not None:
+            mel_nhwc = ops.specaug(mel_nhwc.detach().float().contiguous(), [64 * int(n) for n in cap_lens], self.specaug,
+                                   self.specaug_seed, self.steps)
         return self.step_features(self.features(mel_nhwc), cap_lens, image_feature, label)
 
     def end_epoch(self):

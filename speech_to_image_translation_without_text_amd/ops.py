@@ -1876,6 +1876,97 @@ def logmel_gather(pool, row_offsets, frames, T):
     return out
 
 
+# ---- SpecAugment of a log-mel batch -------------------------------------------------------------------------------------
+SPECAUG_MAX_MASKS, SPECAUG_MAX_FREQ_WIDTH = 8, 20
+
+
+def _specaug_count_width(token, value, max_width):
+    count, sep, width = value.partition("x")
+    try:
+        if not sep:
+            raise ValueError
+        count, width = int(count), int(width)
+    except ValueError:
+        raise ValueError("bad augmentation %r: expected COUNTxWIDTH, two integers" % token) from None
+    if not 0 <= count <= SPECAUG_MAX_MASKS:
+        raise ValueError("bad augmentation %r: the mask count must lie in [0, %d]" % (token, SPECAUG_MAX_MASKS))
+    if width < 0 or (max_width is not None and width > max_width):
+        raise ValueError("bad augmentation %r: the width must be %s" %
+                         (token, ">= 0" if max_width is None else "in [0, %d]" % max_width))
+    return count, width
+
+
+def specaug_policy(spec):
+    """'freq=2x8,time=2x40,ratio=0.2' (any order, any subset; '' = off -> None) -> (freq_masks, freq_width, time_masks,
+    time_width, time_ratio) of s2i_specaug: count x maximum width per kind, at most 8 masks of a kind, frequency masks at
+    most 20 bins wide; `ratio` (default 1.0, in (0, 1]) caps a time mask at that share of the utterance's frames."""
+    values = {"freq": (0, 0), "time": (0, 0), "ratio": 1.0}
+    seen = set()
+    for token in str(spec).split(","):
+        token = token.strip()
+        if not token:
+            continue
+        key, sep, value = token.partition("=")
+        key = key.strip()
+        if not sep or key not in values:
+            raise ValueError("unknown augmentation %r: expected a comma-separated subset of freq=NxW, time=NxW, ratio=R" % token)
+        if key in seen:
+            raise ValueError("augmentation %r given twice" % token)
+        seen.add(key)
+        if key == "ratio":
+            try:
+                ratio = float(value)
+            except ValueError:
+                raise ValueError("bad augmentation %r: expected ratio=R, a number" % token) from None
+            if not 0.0 < ratio <= 1.0:      # a NaN fails both
+                raise ValueError("bad augmentation %r: the ratio must lie in (0, 1]" % token)
+            values[key] = ratio
+        else:
+            values[key] = _specaug_count_width(token, value.strip(), SPECAUG_MAX_FREQ_WIDTH if key == "freq" else None)
+    if not seen:
+        return None
+    return values["freq"] + values["time"] + (values["ratio"],)
+
+
+def specaug(mel, valid, policy, seed, step, out=None):
+    """SpecAugment of a log-mel batch [B, 1, T, 40] (s2i_specaug; include/s2i_hip.h has the definitions): `policy`
+    (specaug_policy's tuple, or its spec string) frequency and time masks per utterance over its first valid[b] rows, the
+    masked cells set to the mean of those rows, everything else copied bit for bit.  The masks are a function of
+    (seed, step, b) alone, drawn on the device by a counter-based generator: nothing random is uploaded and no generator
+    state exists.  `valid`: B frame counts in [0, T], a sequence or an int32 device vector.  Returns a new tensor, or `out`
+    (`out=mel` works in place).  One reduction and one apply launch; no autograd, no CPU fallback."""
+    lib = _lib_ready()
+    if isinstance(policy, str):
+        policy = specaug_policy(policy) or (0, 0, 0, 0, 1.0)
+    fm, fw, tm, tw, ratio = policy
+    if not mel.is_cuda:
+        raise _lib.S2IError("specaug runs on the MI355X kernel: mel is on %s" % mel.device)
+    if mel.dtype != torch.float32 or mel.dim() != 4 or mel.shape[1] != 1 or mel.shape[3] != 40 or not mel.is_contiguous():
+        raise ValueError("specaug: mel must be a contiguous fp32 [B, 1, T, 40] tensor, got %s %s"
+                         % (mel.dtype, tuple(mel.shape)))
+    B, T = mel.shape[0], mel.shape[2]
+    if B < 1 or T < 1:
+        raise ValueError("specaug: empty batch %s" % (tuple(mel.shape),))
+    if not torch.is_tensor(valid):
+        valid = [int(v) for v in valid]
+        if len(valid) != B or min(valid) < 0 or max(valid) > T:
+            raise ValueError("specaug: valid must hold %d frame counts in [0, %d], got %s" % (B, T, valid))
+        valid = torch.tensor(valid, dtype=torch.int32, device=mel.device)
+    elif valid.dtype != torch.int32 or tuple(valid.shape) != (B,) or valid.device != mel.device:
+        raise ValueError("specaug: valid must be an int32 vector of %d entries on %s, got %s %s on %s"
+                         % (B, mel.device, valid.dtype, tuple(valid.shape), valid.device))
+    if out is None:
+        out = torch.empty_like(mel)
+    elif out.dtype != mel.dtype or out.shape != mel.shape or out.device != mel.device or not out.is_contiguous():
+        raise ValueError("specaug: out must match mel (contiguous fp32 %s on %s)" % (tuple(mel.shape), mel.device))
+    ws = _ws.get(lib.s2i_specaug_workspace_bytes(B), mel.device)
+    mask64 = (1 << 64) - 1
+    check(lib.s2i_specaug(ptr(mel.detach()), ptr(valid.contiguous()), B, T, ptr(out), int(fm), int(fw), int(tm), int(tw),
+                          float(ratio), int(seed) & mask64, int(step) & mask64, ptr(ws), ws.numel() * 4, stream()),
+          "s2i_specaug")
+    return out
+
+
 # ---- nearest-row search -------------------------------------------------------------------------------------------------
 def score_rows(x, packed, n, out):
     """out[:Q * n] viewed [Q, n] = x [Q, Cp] times the first n rows of a gallery chunk packed with

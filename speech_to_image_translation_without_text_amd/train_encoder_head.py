@@ -39,6 +39,12 @@ rank r takes every world-th item of it from the r-th on (`shard_order`: Distribu
 ranks run ceil(N / world / batch_size) steps.  The global `random`, which draws views and utterances, is seeded seed + rank.
 Rank 0 alone prints, evaluates and writes checkpoints while the others wait at a barrier.  --resident keeps the WHOLE pool
 on every rank.
+--specaug 'freq=2x8,time=2x40,ratio=0.2' masks every training batch on the GPU (SpecAugment: count x maximum width of the
+frequency and time masks, masked cells set to the utterance's mean; encoder_train.py, ops.specaug).  The masks come from a
+counter-based generator keyed by --seed (plus the rank under --distributed) and counted by the trainer's step counter:
+they take nothing from `random`, so the batches drawn are the same with and without the option, and a --state_every state
+continues the mask sequence exactly.  A plain --resume epoch_N.pth restarts the counter at 0.  Evaluation and the
+checkpoints never see a mask.  Default '': off.
 """
 import argparse
 import json
@@ -50,7 +56,7 @@ import time
 import numpy as np
 import torch
 
-from . import audio, datasets
+from . import audio, datasets, ops
 from .encoder_train import HeadTrainer
 from .extract_audio_feature import MIN_FRAMES, load_encoder
 
@@ -178,6 +184,10 @@ def get_parser(description="fine-tune the speech encoder's LSTM head (conv stack
     p.add_argument("--state_every", type=int, default=0,
                    help="every this many epochs and after the last, replace <output_dir>/state.pth with the full training "
                         "state (weights, Adam moments, learning rate, best accuracy, every rank's `random`); 0 = never")
+    p.add_argument("--specaug", type=str, default="",
+                   help="SpecAugment of every training batch on the GPU, e.g. 'freq=2x8,time=2x40,ratio=0.2': count x maximum "
+                        "width of the frequency and time masks, `ratio` the largest share of an utterance one time mask "
+                        "may take (ops.specaug_policy); default '': off")
     return p
 
 
@@ -186,13 +196,23 @@ def check_args(args):
         raise SystemExit("--batch_size, --epoch and --eval_every must be >= 1")
     if args.state_every < 0:
         raise SystemExit("--state_every must be >= 0")
+    try:
+        ops.specaug_policy(getattr(args, "specaug", ""))
+    except ValueError as e:
+        raise SystemExit("--specaug: %s" % e)
 
 
 def trainer_kwargs(args):
+    """HeadTrainer's keywords.  The mask generator's seed is --seed, plus the rank under --distributed (once the process
+    group exists), as seed_draws seeds `random`: the ranks mask independently."""
+    specaug_seed = args.seed or 0
+    if args.distributed and torch.distributed.is_available() and torch.distributed.is_initialized():
+        specaug_seed += torch.distributed.get_rank()
     return dict(lr=args.learning_rate, weight_decay=1e-5, step_size=args.lr_scheduler_step_size,
                 gamma=args.lr_scheduler_gamma, loss_diff=args.loss_diff, loss_same=args.loss_same, jel=args.jel_flag,
                 l1=args.l1_flag, lambda_l1=args.lambda_l1, distill=args.distill_flag, distill_T=args.distill_T,
-                lambda_distill=args.lambda_distill, fused_adam=args.fused_adam, distributed=args.distributed)
+                lambda_distill=args.lambda_distill, fused_adam=args.fused_adam, distributed=args.distributed,
+                specaug=getattr(args, "specaug", ""), specaug_seed=specaug_seed)
 
 
 def make_resident(split, name, dev, workers, say=print, resample=False):
