@@ -815,6 +815,30 @@ int s2i_moments_accumulate(const float* x, int rows, int D, long long ldx, doubl
 int s2i_topk_rows(const float* scores, int Q, int N, int lds, int base, int k, float* best_score, int* best_row,
                   int merge, void* stream);
 
+/* ---- the rank of one candidate among the candidates of other classes, chunk by chunk --------------------------------
+ * The speech-image consistency score (R-precision and recall@k of generated images against the test utterances;
+ * retrieval.Gallery.rank, gan_metrics.ConsistencyScorer) needs, for every query, how many gallery rows of OTHER classes
+ * score above its own designated row.  That rank can be in the thousands, so a top k does not give it; like
+ * s2i_topk_rows this folds one [Q, N] block of scores (row stride lds floats, column j = gallery row base + j) at a
+ * time, and the [Q, rows] matrix never exists. */
+#define S2I_RANK_GATHER 0
+#define S2I_RANK_COUNT 1
+/* mode S2I_RANK_GATHER: for every q with base <= own_row[q] < base + N, own_score[q] = scores[q][own_row[q] - base]
+ *   (the bits, a NaN included); every other q, own_row[q] = -1 ("no own row") among them, is left untouched.  Reads
+ *   scores and own_row, writes own_score; query_label, row_label, gt and eq are not touched and may be null.
+ * mode S2I_RANK_COUNT: for every q, over the columns j whose row_label[base + j] != query_label[q]:
+ *   gt[q] += #{j : scores[q][j] > own_score[q]},  eq[q] += #{j : scores[q][j] == own_score[q]}   (float comparisons).
+ *   A NaN score counts in neither.  A NaN own_score[q] makes EVERY column of another class count in gt (a NaN one too),
+ *   so that query ranks last.  Rows of the query's own class are never counted, its own row included.  own_row is not
+ *   read.  gt and eq are int32 [Q], accumulated in place across chunks; the caller zeroes them.
+ * row_label is int32 over the whole gallery (n_labels entries, indexed by global row: base + N <= n_labels);
+ * query_label and own_row are int32 [Q].  N <= 2^30, base + N <= INT_MAX.  Any row stride lds >= N, base and pointer
+ * are taken (16-byte loads where the addresses allow, single loads before and after).  No arithmetic on the scores,
+ * integer counters: exact, and identical from run to run.  One block per query when counting; no atomics, no
+ * workspace, no synchronisation. */
+int s2i_rank_rows(const float* scores, int Q, int N, int lds, int base, const int* own_row, const int* query_label,
+                  const int* row_label, int n_labels, float* own_score, int* gt, int* eq, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@ PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32, PCM_F64 = 0, 1, 2, 3, 4, 5
 RESAMPLE_TILE = 1024
 RESAMPLE_MAX_WINDOW = 13826
 TOPK_MAX = 64
+RANK_GATHER, RANK_COUNT = 0, 1      # s2i_rank_rows modes (S2I_RANK_*)
 DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4
 ABI_VERSION = 6
 # s2i_wgrad_plan_query: the WgKernel values of csrc/s2i_igemm.h in order, and the twelve outputs
@@ -209,6 +210,7 @@ _SIGNATURES = {
     "s2i_pcm_resample": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P, P, P]),
     "s2i_moments_accumulate": (c_int, [P, c_int, c_int, c_ll, P, P, P]),
     "s2i_topk_rows": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P]),
+    "s2i_rank_rows": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -4,6 +4,7 @@ trainer.py:88-159, whose evaluate() computes them only in dead code after its ea
     python -m speech_to_image_translation_without_text_amd.gan_metrics --cfg cfg/birds_3stages.yml \\
         --netG output/Model/netG_600.pth --inception inception_v3_google-1a9a5a14.pth --data_dir data/birds \\
         [--real_stats stats.npz] [--save_images] [--seed S] [--max_items K] [--out metrics.json]
+        [--googlenet bvlc_googlenet.caffemodel [--consistency_cosine]]
 
 G runs in .eval() over every embedding column of every test item, its last-stage images go through the native
 Inception-v3 (inception.py), and the pool3 rows of each pass are folded into fp64 moments on the device
@@ -11,6 +12,12 @@ Inception-v3 (inception.py), and the pool3 rows of each pass are folded into fp6
 of D (D + 1) doubles.  The softmax rows, which the split-wise IS and NLPP need in order, are kept on the device.
 The values are those of torchvision's Inception-v3 weights: the paper used TF Inception models, so they are not
 comparable to its numbers.
+
+With --googlenet the record also says whether the pictures show what was said (`ConsistencyScorer`): every fake image,
+quantised as its PNG would be, goes through BVLC GoogLeNet on the device (googlenet.GoogLeNetFeatures.rows), and its
+ten-view pool5 row is ranked against the speech embeddings of the whole split (retrieval.Gallery.rank, s2i_rank_rows):
+recall@1/5/10, the median rank and the closed-form R-precision under `fake_*` keys, with the same scores of the real
+images under `real_*` keys as the ceiling the speech encoder allows.
 """
 import argparse
 import json
@@ -28,6 +35,7 @@ from .trainer import (_frechet_from_moments, compute_inception_score, negative_l
                       save_singleimages)
 
 POOL3, CLASSES = 2048, 1000
+GOOGLENET_FEATURES = 1024      # googlenet.FEATURES: pool5/7x7_s1
 # Sentences of one batch are stacked into one G launch up to this many images.  The largest G tensor at
 # cfg/birds_3stages.yml widths is the stage-3 joint input, 128 x 128 x 160 fp32 = 10.5 MB per image, so 96 images stay
 # at 1.0 GB, half of the 2 GiB that the kernels' 32-bit byte offsets reach.
@@ -170,6 +178,101 @@ class GeneratorScorer:
                     fid=fid, n_fake=int(fake[2]), n_real=int(real[2]), fake_stats=fake, real_stats=real)
 
 
+class ConsistencyScorer:
+    """Speech-image consistency of generated images: image query, utterance candidates.
+
+    The gallery holds every utterance embedding of the split (embeddings [N, S, C], row i * S + s, Gallery(views="all")),
+    C = 1024: the space the speech encoder is trained to share with GoogLeNet's pool5.  The image generated from
+    utterance s of item i is a query whose own candidate is row i * S + s; it is ranked against the rows of OTHER
+    classes (labels [N]; another description of the same species is not a wrong answer, and a tie counts against the
+    query): retrieval.Gallery.rank and retrieval.rank_metrics have the definitions.  The real image of each item, queried
+    once per sentence, gives the `real_*` scores: the ceiling the encoder allows, without which the fake scores cannot be
+    read.  `googlenet` is a googlenet.GoogLeNetFeatures on `device` (None where only add_rows is used).  The fp32 rows are
+    kept on the device (4 KB each).  There is no CPU fallback."""
+
+    def __init__(self, googlenet, embeddings, labels, device=None, cosine=False, chunk_rows=None):
+        from . import retrieval
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        emb = np.asarray(embeddings if isinstance(embeddings, np.ndarray) else [np.asarray(e) for e in embeddings],
+                         dtype=np.float32)
+        if emb.ndim != 3:
+            raise ValueError("ConsistencyScorer: embeddings must be [N, S, C], got %s" % (emb.shape,))
+        labels = np.asarray(labels).reshape(-1)
+        if labels.shape[0] != emb.shape[0]:
+            raise ValueError("ConsistencyScorer: %d labels for %d items" % (labels.shape[0], emb.shape[0]))
+        self.gallery = retrieval.Gallery(emb, self.device, views="all", cosine=cosine,
+                                         chunk_rows=chunk_rows or retrieval.GALLERY_CHUNK_ROWS)
+        self.net = googlenet
+        self.items, self.sentences, self.dim = emb.shape
+        if googlenet is not None and self.dim != GOOGLENET_FEATURES:
+            raise ValueError("ConsistencyScorer: the embeddings are %d wide, GoogLeNet's pool5 rows %d"
+                             % (self.dim, GOOGLENET_FEATURES))
+        self.labels = np.unique(labels, return_inverse=True)[1].reshape(-1).astype(np.int32)
+        self.row_labels = np.repeat(self.labels, self.sentences)
+        self._fake, self._real = [], []
+
+    def _index(self, name, values, n, limit):
+        v = np.asarray(values.cpu() if torch.is_tensor(values) else values).reshape(-1).astype(np.int64)
+        if v.shape[0] != n or (n and (v.min() < 0 or v.max() >= limit)):
+            raise ValueError("ConsistencyScorer: %d rows need %d %s in 0..%d" % (n, n, name, limit - 1))
+        return v
+
+    def add_rows(self, rows, items, sentences=None, real=False):
+        """Precomputed feature rows [n, C] (kept as fp32 on the device): fake rows of (items[j], sentences[j]), or with
+        real=True the real rows of items[j] (`sentences` is not used)."""
+        rows = torch.as_tensor(rows)
+        if rows.dim() != 2 or rows.shape[1] != self.dim:
+            raise ValueError("ConsistencyScorer: rows must be [n, %d], got %s" % (self.dim, tuple(rows.shape)))
+        n = rows.shape[0]
+        it = self._index("items", items, n, self.items)
+        rows = rows.detach().to(device=self.device, dtype=torch.float32)
+        if real:
+            self._real.append((rows, it))
+        else:
+            self._fake.append((rows, it, self._index("sentences", sentences, n, self.sentences)))
+
+    def _features(self, u8):
+        if self.net is None:
+            raise ValueError("ConsistencyScorer: built without a GoogLeNet: only add_rows is available")
+        return self.net.rows(u8)
+
+    def add_fake(self, img_nhwc, items, sentences):
+        """G's last-stage NHWC images in [-1, 1] (B, H, W, C >= 3), generated from (items[j], sentences[j]): quantised as
+        the PNG writer quantises them (ops.images_to_uint8_hwc), then GoogLeNet's ten-view mean rows."""
+        self.add_rows(self._features(ops.images_to_uint8_hwc(img_nhwc)), items, sentences)
+
+    def add_real(self, images, items):
+        """The real image of every items[j]: uint8 (B, H, W, 3) RGB, or fp32 (B, 3, H, W) in [-1, 1] (quantised as the
+        fake ones are)."""
+        images = images.to(self.device)
+        if images.dtype != torch.uint8:
+            images = ops.images_to_uint8_hwc(images.float().permute(0, 2, 3, 1).contiguous())
+        self.add_rows(self._features(images.contiguous()), items, real=True)
+
+    def _rank(self, rows, items, sentences):
+        from . import retrieval
+        qlab = self.labels[items]
+        gt, eq = self.gallery.rank(rows, items * self.sentences + sentences, qlab, self.row_labels)
+        return retrieval.rank_metrics(gt, eq, retrieval.other_class_counts(qlab, self.row_labels))
+
+    def result(self):
+        """{fake_recall@1, fake_recall@5, fake_recall@10, fake_median_rank, fake_r_precision, fake_n_queries,
+        fake_n_skipped} over the fake rows in arrival order, and the same under real_* with each real row queried once per
+        sentence of its item.  A side that received no rows is left out."""
+        out = {}
+        if self._fake:
+            rows = torch.cat([f[0] for f in self._fake])
+            res = self._rank(rows, np.concatenate([f[1] for f in self._fake]), np.concatenate([f[2] for f in self._fake]))
+            out.update(("fake_" + k, v) for k, v in res.items())
+        if self._real:
+            rows = torch.cat([r[0] for r in self._real])
+            items = np.concatenate([r[1] for r in self._real])
+            S = self.sentences
+            res = self._rank(rows.repeat_interleave(S, dim=0), np.repeat(items, S), np.tile(np.arange(S), items.shape[0]))
+            out.update(("real_" + k, v) for k, v in res.items())
+        return out
+
+
 class _PngWriter:
     """Writes save_singleimages PNGs on a host thread once the device copy of a batch has landed."""
 
@@ -214,12 +317,15 @@ class _PngWriter:
 
 @torch.no_grad()
 def score_generator(netG, loader, scorer, seed, sentences=None, max_items=None, save_images=None,
-                    stack_images=G_STACK_IMAGES):
+                    stack_images=G_STACK_IMAGES, consistency=None):
     """Drive G (.eval()) over the test loader's (images per branch, embeddings (B, S, D), filenames) batches and feed
     `scorer`: each batch's last-branch real images once, then its fake images sentence by sentence, items in order within
     a sentence (the reference's row order).  z (B, Z_DIM) then eps (B, EMBEDDING_DIM) are drawn per sentence from one
     CPU generator seeded with `seed`, so stacking sentences into one G launch (up to stack_images images) draws the same
     noise.  `save_images`: a directory that receives the reference-named PNGs (single_samples/valid/...).
+    `consistency`: a ConsistencyScorer over the loader's items in loader order (item index = position in the split, its
+    sentences = the embedding columns); it is fed the same real and fake tensors and changes nothing else: the same noise,
+    the same PNGs, the same `scorer` input.
     Returns the number of test items scored."""
     from .miscc.config import cfg
     dev = scorer.device
@@ -236,6 +342,8 @@ def score_generator(netG, loader, scorer, seed, sentences=None, max_items=None, 
             names = list(names)[:B]
             real = imgs[-1][:B].to(dev, non_blocking=True)
             scorer.add_real(ops.images_from_uint8_hwc(real.contiguous()) if real.dtype == torch.uint8 else real.float())
+            if consistency is not None:
+                consistency.add_real(real, np.arange(items, items + B))
             sent = list(range(emb.shape[1])) if sentences is None else list(sentences)
             per = max(1, int(stack_images) // B)
             for s0 in range(0, len(sent), per):
@@ -247,6 +355,8 @@ def score_generator(netG, loader, scorer, seed, sentences=None, max_items=None, 
                 c = torch.cat([emb[:, s] for s in ss]).contiguous()
                 fake, _, _ = netG(torch.cat(zs).to(dev), c, torch.cat(es).to(dev), True)
                 scorer.add_fake(nhwc4_as_nchw(fake[-1]))
+                if consistency is not None:
+                    consistency.add_fake(fake[-1], np.tile(np.arange(items, items + B), len(ss)), np.repeat(ss, B))
                 if writer is not None:
                     writer.put(fake[-1], names, ss)
             items += B
@@ -274,6 +384,11 @@ def parse_args(argv=None):
     p.add_argument("--batch_size", type=int, default=None, help="default: TRAIN.BATCH_SIZE")
     p.add_argument("--workers", type=int, default=None, help="default: WORKERS")
     p.add_argument("--out", default="metrics.json", help="JSON record; fid_stats_fake/real.npz go next to it")
+    p.add_argument("--googlenet", default=None,
+                   help="bvlc_googlenet.caffemodel (local file): adds the speech-image consistency scores (fake_* and "
+                        "real_* recall@k, median rank, R-precision) to the record; the embeddings must be 1024 wide")
+    p.add_argument("--consistency_cosine", action="store_true", default=False,
+                   help="rank by cosine similarity instead of the dot product")
     args = p.parse_args(argv)
     if args.max_items is not None and args.max_items < 1:
         p.error("--max_items must be >= 1")
@@ -310,9 +425,18 @@ def main(argv=None):
     n_sent = dataset.embedding.shape[1]
     scorer = GeneratorScorer(INCEPTION_V3(args.inception), n_items * n_sent, dev)
     netG = load_generator(args.netG, dev)
+    consistency = None
+    if args.googlenet:
+        from .googlenet import GoogLeNetFeatures
+        from .retrieval import labels_from_json
+        labels = labels_from_json(os.path.join(args.data_dir, "test.json"))
+        consistency = ConsistencyScorer(GoogLeNetFeatures(args.googlenet, dev), np.asarray(dataset.embedding)[:n_items],
+                                        labels[:n_items], dev, cosine=args.consistency_cosine)
     score_generator(netG, loader, scorer, args.seed, max_items=args.max_items,
-                    save_images=_image_dir(args.netG) if args.save_images else None)
+                    save_images=_image_dir(args.netG) if args.save_images else None, consistency=consistency)
     res = scorer.result(10, real_stats)
+    if consistency is not None:
+        res.update(consistency.result(), consistency_score="cosine" if args.consistency_cosine else "dot")
     out_dir = os.path.dirname(os.path.abspath(args.out))
     os.makedirs(out_dir, exist_ok=True)
     fake_stats, rstats = res.pop("fake_stats"), res.pop("real_stats")

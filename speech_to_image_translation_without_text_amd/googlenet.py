@@ -449,6 +449,41 @@ class GoogLeNetFeatures:
             del keep
         return out
 
+    def rows(self, u8, per_view=False):
+        """Images that are already on the device: a contiguous uint8 (B, H, W, 3) RGB tensor on self.device -> fp32
+        (B, 1024) on the device, the mean of each image's ten views (s2i_time_mean over T = 10: ten fp32 additions in view
+        order, then one division), which is what `Gallery(views="mean")` stores for a real image up to that rounding.
+        per_view=True: the (B, 10, 1024) views themselves, the values `self(images)` returns for the same pixels.  The
+        images run in chunks of at most MAX_BATCH, as in `self(images)`; no pixel or feature is copied to the host."""
+        if (not torch.is_tensor(u8) or u8.dtype != torch.uint8 or u8.dim() != 4 or u8.shape[3] != 3 or u8.shape[0] < 1
+                or u8.shape[1] < 1 or u8.shape[2] < 1 or not u8.is_contiguous()):
+            raise ValueError("GoogLeNetFeatures.rows takes a contiguous uint8 (B >= 1, H, W, 3) tensor, got %s %s"
+                             % (getattr(u8, "dtype", type(u8)), tuple(getattr(u8, "shape", ()))))
+        if u8.device != self.device:
+            raise _lib.S2IError("GoogLeNetFeatures.rows: the images are on %s, the network on %s: there is no CPU "
+                                "fallback and no implicit copy" % (u8.device, self.device))
+        B, H, W, _ = u8.shape
+        lib = _lib.load()
+        b, g, r = self.mean_bgr
+        with torch.cuda.device(self.device):
+            views = torch.empty(B, VIEWS, FEATURES, device=self.device)
+            n = min(B, MAX_BATCH)
+            offs = torch.arange(n, dtype=torch.int64, device=self.device) * (H * W * 3)
+            hs = torch.full((n,), H, dtype=torch.int32, device=self.device)
+            ws = torch.full((n,), W, dtype=torch.int32, device=self.device)
+            for s in range(0, B, MAX_BATCH):
+                part = u8[s:s + MAX_BATCH]
+                nb = part.shape[0]
+                x = torch.empty(VIEWS * nb, VIEW, VIEW, 4, device=self.device)
+                check(lib.s2i_googlenet_prep(ptr(part), part.numel(), ptr(offs), ptr(hs), ptr(ws), nb, b, g, r, ptr(x),
+                                             stream()), "s2i_googlenet_prep")
+                self.features(x, VIEWS * nb, views[s:s + nb].view(VIEWS * nb, FEATURES))
+            if per_view:
+                return views
+            out = torch.empty(B, FEATURES, device=self.device)
+            check(lib.s2i_time_mean(ptr(views), B, VIEWS, FEATURES, ptr(out), stream()), "s2i_time_mean")
+            return out
+
 
 def flops_per_image():
     return VIEWS * flops_per_view()

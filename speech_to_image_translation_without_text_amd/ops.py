@@ -14,6 +14,7 @@ Each Function stands in for a group of stock torch ops of the reference
   LstmSentence, EncoderLoss     the speech encoder's LSTM head and loss (Audio_to_Image/train_audio_encoder.py)
   TemporalConvBnRelu, InputBatchNorm, MaxPoolW3S2, conv_stack_train   its conv stack in training mode
   score_rows, topk_rows         one gallery chunk's scores and their fold into a running top k (retrieval.Gallery)
+  rank_rows                     the same scores folded into rank counters of one designated row (Gallery.rank)
 
 Activations between these ops are NHWC; parameters stay in the reference's OIHW layout and are
 re-packed to the kernels' layout when their version counter changes.  There is no CPU fallback.
@@ -2023,3 +2024,59 @@ def topk_rows(scores, k, base=0, best=None, out=None):
     check(lib.s2i_topk_rows(ptr(scores.detach()), Q, N, scores.stride(0), base, k, ptr(bs), ptr(br),
                             1 if best is not None else 0, stream()), "s2i_topk_rows")
     return bs, br
+
+
+def _rank_vector(name, t, dtype, n, device):
+    if (not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous()
+            or t.device != device):
+        raise ValueError("rank_rows: %s must be a contiguous %s vector of %d entries on %s"
+                         % (name, str(dtype).replace("torch.", ""), n, device))
+
+
+def rank_rows(scores, own_row, query_label, row_label, base, own_score, gt, eq, mode):
+    """One [Q, N] block of scores (fp32, unit column stride, any row stride >= N; column j is gallery row base + j) folded
+    into the per-query rank state (s2i_rank_rows; include/s2i_hip.h has the definitions).
+
+    mode "gather": own_score[q] = scores[q][own_row[q] - base] for the q whose own row lies in this block; every other
+                   q (own_row[q] = -1 among them) keeps its value.  query_label, row_label, gt and eq may be None.
+    mode "count":  over the columns whose row_label[base + j] != query_label[q]: gt[q] += #(score > own_score[q]),
+                   eq[q] += #(score == own_score[q]).  A NaN score counts in neither; a NaN own score puts every such
+                   column into gt.  own_row may be None.
+
+    own_row, query_label, gt, eq: int32 [Q]; own_score: fp32 [Q]; row_label: int32 over the whole gallery, indexed by
+    global row.  Everything on the scores' device; the counters are accumulated in place (the caller zeroes them).
+    Only comparisons: exact and run-to-run identical.  No autograd."""
+    base = int(base)
+    if mode not in ("gather", "count"):
+        raise ValueError("rank_rows: mode must be 'gather' or 'count', got %r" % (mode,))
+    if not torch.is_tensor(scores) or scores.dim() != 2 or scores.dtype != torch.float32:
+        raise ValueError("rank_rows: scores must be an fp32 [Q, N] tensor")
+    Q, N = scores.shape
+    if Q < 1 or N < 1 or scores.stride(1) != 1 or scores.stride(0) < N:
+        raise ValueError("rank_rows: scores %s with strides %s: need Q, N >= 1, unit column stride and row stride >= N"
+                         % (tuple(scores.shape), tuple(scores.stride())))
+    if base < 0 or base + N > 2 ** 31 - 1:
+        raise ValueError("rank_rows: row ids %d .. %d leave int32" % (base, base + N - 1))
+    if not scores.is_cuda:
+        raise _lib.S2IError("rank_rows runs on the MI355X kernel: there is no CPU fallback (scores on %s)" % scores.device)
+    dev = scores.device
+    _rank_vector("own_score", own_score, torch.float32, Q, dev)
+    n_labels = 0
+    if mode == "gather":
+        _rank_vector("own_row", own_row, torch.int32, Q, dev)
+        query_label = row_label = gt = eq = None
+    else:
+        _rank_vector("query_label", query_label, torch.int32, Q, dev)
+        _rank_vector("gt", gt, torch.int32, Q, dev)
+        _rank_vector("eq", eq, torch.int32, Q, dev)
+        if not torch.is_tensor(row_label) or row_label.dim() != 1:
+            raise ValueError("rank_rows: row_label must be an int32 vector over the gallery's rows")
+        n_labels = row_label.shape[0]
+        _rank_vector("row_label", row_label, torch.int32, n_labels, dev)
+        if base + N > n_labels:
+            raise ValueError("rank_rows: rows %d .. %d pass the %d row labels" % (base, base + N - 1, n_labels))
+        own_row = None
+    lib = _lib_ready()
+    check(lib.s2i_rank_rows(ptr(scores.detach()), Q, N, scores.stride(0), base, ptr(own_row), ptr(query_label),
+                            ptr(row_label), n_labels, ptr(own_score), ptr(gt), ptr(eq),
+                            _lib.RANK_GATHER if mode == "gather" else _lib.RANK_COUNT, stream()), "s2i_rank_rows")

@@ -13,6 +13,11 @@ GPU (`Gallery`, `recall_at_k`).
 `Gallery` keeps image-feature rows in HBM and answers "which rows does this embedding score highest against": the scores
 of one chunk of rows at a time come from the fp32 1x1 matrix kernel and are folded into a running top k by s2i_topk_rows,
 so the [queries, rows] matrix never exists.  `eval_class` stays on the host as it was.
+
+`Gallery.rank` answers the other question a retrieval score asks, "where does THIS row stand for this query": the same
+chunked scores are folded by s2i_rank_rows into the number of rows of other classes that score above (or exactly as) a
+designated own row, and `rank_metrics` turns those counters into recall@k, the median rank and the closed-form
+R-precision (gan_metrics.ConsistencyScorer).
 """
 import argparse
 import json
@@ -134,32 +139,44 @@ class Gallery:
         self.nbytes = sum(c[2].numel() * 4 for c in self.chunks)
         self._scores = None
 
+    def _check_queries(self, queries, what):
+        import torch
+        q = torch.as_tensor(queries)
+        if q.dim() != 2 or q.shape[1] != self.dim or q.shape[0] < 1:
+            raise ValueError("Gallery.%s: queries must be [Q >= 1, %d], got %s" % (what, self.dim, tuple(q.shape)))
+        return q
+
+    def _prepare(self, q):
+        """The queries as the matrix kernel takes them (fp32 on the device, normalised where cosine, padded to cpad,
+        contiguous), and the score scratch of one (QUERY_BLOCK, chunk) launch.  Called on self.device."""
+        import torch
+        q = q.detach().to(device=self.device, dtype=torch.float32)
+        if self.cosine:
+            norm = torch.linalg.vector_norm(q, dim=1, keepdim=True)
+            q = q / torch.where(norm > 0, norm, torch.ones_like(norm))
+        if self.cpad != self.dim:
+            q = torch.nn.functional.pad(q, (0, self.cpad - self.dim))
+        q = q.contiguous()
+        need = min(q.shape[0], QUERY_BLOCK) * min(self.chunk_rows, self.rows)
+        if self._scores is None or self._scores.numel() < need:
+            self._scores = torch.empty(need, dtype=torch.float32, device=self.device)
+        return q
+
     def search(self, queries, k):
         """(scores [Q, k] fp32, items [Q, k] int64, views [Q, k] int64 or None) on the device: for each query row its k
         best gallery rows, best first; equal scores by ascending row.  k is clipped to the number of rows (64 at the most
         after that: the kernel's limit)."""
         import torch
         from . import ops
-        q = torch.as_tensor(queries)
-        if q.dim() != 2 or q.shape[1] != self.dim or q.shape[0] < 1:
-            raise ValueError("Gallery.search: queries must be [Q >= 1, %d], got %s" % (self.dim, tuple(q.shape)))
+        q = self._check_queries(queries, "search")
         k = min(int(k), self.rows)
         if not 1 <= k <= 64:
             raise ValueError("Gallery.search: k must lie in 1..64 after clipping to the %d rows, got %d" % (self.rows, k))
-        q = q.detach().to(device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
-            if self.cosine:
-                norm = torch.linalg.vector_norm(q, dim=1, keepdim=True)
-                q = q / torch.where(norm > 0, norm, torch.ones_like(norm))
-            if self.cpad != self.dim:
-                q = torch.nn.functional.pad(q, (0, self.cpad - self.dim))
-            q = q.contiguous()
+            q = self._prepare(q)
             Q = q.shape[0]
             best = (torch.empty((Q, k), dtype=torch.float32, device=self.device),
                     torch.empty((Q, k), dtype=torch.int32, device=self.device))
-            need = min(Q, QUERY_BLOCK) * min(self.chunk_rows, self.rows)
-            if self._scores is None or self._scores.numel() < need:
-                self._scores = torch.empty(need, dtype=torch.float32, device=self.device)
             for q0 in range(0, Q, QUERY_BLOCK):
                 qb = q[q0:q0 + QUERY_BLOCK]
                 pair = (best[0][q0:q0 + QUERY_BLOCK], best[1][q0:q0 + QUERY_BLOCK])
@@ -173,6 +190,107 @@ class Gallery:
         if self.nviews is None:
             return best[0], row, None
         return best[0], torch.div(row, self.nviews, rounding_mode="floor"), row % self.nviews
+
+    def rank(self, queries, own_rows, query_labels, row_labels):
+        """(gt, eq) int32 [Q] on the device.  Query q designates gallery row own_rows[q] (-1: none) and has class
+        query_labels[q]; row_labels gives the class of every gallery row.  Among the rows of OTHER classes, gt[q] score
+        strictly above the own row and eq[q] exactly as it does (float comparison; s2i_rank_rows has the NaN rules).  Rows
+        of the query's class are never counted, the own row included.  A query without an own row is compared with a
+        score of 0.
+
+        Two passes over the (QUERY_BLOCK, chunk) launches `search` makes: the first gathers each own score out of the
+        chunk that holds it (chunks without an own row of the block are skipped), the second counts.  The own score so
+        comes from the same kind of launch, on the same operands, that scores its neighbours, and nothing of size
+        Q x rows exists."""
+        import torch
+        from . import ops
+        q = self._check_queries(queries, "rank")
+        Q = q.shape[0]
+        own = np.asarray(own_rows.cpu() if torch.is_tensor(own_rows) else own_rows).reshape(-1).astype(np.int64)
+        qlab = np.asarray(query_labels.cpu() if torch.is_tensor(query_labels) else query_labels).reshape(-1)
+        rlab = np.asarray(row_labels.cpu() if torch.is_tensor(row_labels) else row_labels).reshape(-1)
+        if own.shape[0] != Q or qlab.shape[0] != Q or rlab.shape[0] != self.rows:
+            raise ValueError("Gallery.rank: %d own rows and %d query labels for %d queries, %d row labels for %d rows"
+                             % (own.shape[0], qlab.shape[0], Q, rlab.shape[0], self.rows))
+        if own.min() < -1 or own.max() >= self.rows:
+            raise ValueError("Gallery.rank: own rows must lie in -1..%d" % (self.rows - 1))
+        for lab in (qlab, rlab):
+            if lab.dtype.kind not in "iu" or lab.min() < -2 ** 31 or lab.max() > 2 ** 31 - 1:
+                raise ValueError("Gallery.rank: labels must be integers that fit int32")
+        with torch.cuda.device(self.device):
+            q = self._prepare(q)
+            own_d = torch.from_numpy(own.astype(np.int32)).to(self.device)
+            qlab_d = torch.from_numpy(qlab.astype(np.int32)).to(self.device)
+            rlab_d = torch.from_numpy(rlab.astype(np.int32)).to(self.device)
+            own_score = torch.zeros(Q, dtype=torch.float32, device=self.device)
+            gt = torch.zeros(Q, dtype=torch.int32, device=self.device)
+            eq = torch.zeros(Q, dtype=torch.int32, device=self.device)
+            for q0 in range(0, Q, QUERY_BLOCK):
+                q1 = min(Q, q0 + QUERY_BLOCK)
+                qb, ob = q[q0:q1], own[q0:q1]
+                for start, n, packed in self.chunks:
+                    if ((ob >= start) & (ob < start + n)).any():
+                        sc = ops.score_rows(qb, packed, n, self._scores)
+                        ops.rank_rows(sc, own_d[q0:q1], None, None, start, own_score[q0:q1], None, None, "gather")
+                for start, n, packed in self.chunks:
+                    sc = ops.score_rows(qb, packed, n, self._scores)
+                    ops.rank_rows(sc, None, qlab_d[q0:q1], rlab_d, start, own_score[q0:q1], gt[q0:q1], eq[q0:q1], "count")
+        return gt, eq
+
+
+def rank_metrics(gt, eq, n_candidates, m=99, ks=(1, 5, 10)):
+    """The retrieval scores of Gallery.rank's counters, on the host in float64.
+
+    For query i, c = gt[i] + eq[i] wrong candidates stand at or ahead of its own one (a tie counts against the query) among
+    the n = n_candidates[i] gallery rows of other classes.
+
+    recall@k      percent of queries with c < k: the own candidate among the first k of itself and the n others.
+    median_rank   the median of 1 + c.
+    r_precision   100 x the mean of  prod_{t < m'} (n - c - t) / (n - t),  m' = min(m, n), 0 where n - c < m': the exact
+                  probability that the own candidate comes first among itself and m mismatched candidates drawn without
+                  replacement from the n (all m' drawn ones must be among the n - c that score below it), i.e. the
+                  expectation of the sampled R-precision protocol.  Nothing is sampled: no seed.
+    n_queries     queries scored;  n_skipped  queries with n == 0 (nothing to be ranked against), left out of all means.
+    With no query left the scores are NaN."""
+    gt = np.asarray(gt.cpu() if hasattr(gt, "cpu") else gt).reshape(-1).astype(np.int64)
+    eq = np.asarray(eq.cpu() if hasattr(eq, "cpu") else eq).reshape(-1).astype(np.int64)
+    n = np.asarray(n_candidates).reshape(-1).astype(np.int64)
+    m, ks = int(m), [int(k) for k in ks]
+    if not gt.shape == eq.shape == n.shape:
+        raise ValueError("rank_metrics: %d gt, %d eq and %d candidate counts" % (gt.shape[0], eq.shape[0], n.shape[0]))
+    if m < 1 or not ks or min(ks) < 1:
+        raise ValueError("rank_metrics: m and every k must be >= 1, got m %d, ks %s" % (m, ks))
+    c = gt + eq
+    if gt.size and (min(gt.min(), eq.min(), n.min()) < 0 or (c > n).any()):
+        raise ValueError("rank_metrics: counters must satisfy 0 <= gt + eq <= n_candidates")
+    keep = n > 0
+    c, n = c[keep], n[keep]
+    out = {"n_queries": int(keep.sum()), "n_skipped": int((~keep).sum())}
+    if c.size == 0:
+        out.update(("recall@%d" % k, float("nan")) for k in ks)
+        out.update(median_rank=float("nan"), r_precision=float("nan"))
+        return out
+    for k in ks:
+        out["recall@%d" % k] = float((c < k).mean() * 100.0)
+    out["median_rank"] = float(np.median(1.0 + c))
+    mm = np.minimum(m, n)
+    p = np.ones(c.shape[0], dtype=np.float64)
+    nf, cf = n.astype(np.float64), c.astype(np.float64)
+    for t in range(int(mm.max())):
+        live = t < mm
+        p = np.where(live, p * np.maximum(nf - cf - t, 0.0) / np.where(live, nf - t, 1.0), p)
+    out["r_precision"] = float(p.mean() * 100.0)
+    return out
+
+
+def other_class_counts(query_labels, row_labels):
+    """For every query the number of gallery rows whose label differs from its own: rank_metrics' n_candidates."""
+    qlab, rlab = np.asarray(query_labels).reshape(-1), np.asarray(row_labels).reshape(-1)
+    vals, cnt = np.unique(rlab, return_counts=True)
+    pos = np.searchsorted(vals, qlab)
+    pos = np.minimum(pos, len(vals) - 1)
+    same = np.where(vals[pos] == qlab, cnt[pos], 0)
+    return rlab.shape[0] - same
 
 
 def gallery_rows(features, views="mean", cosine=False):
