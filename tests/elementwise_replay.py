@@ -2,11 +2,14 @@
 s2i_optim.hip): their argument lists, the gamma of each
 family and the replay of one record against tests/elementwise_ref.py in fp64.  tests/test_step_elementwise_gpu.py documents
 the operands, the bound and the mutations and runs the replays over the train step; tests/test_eval_launches_gpu.py runs
-them over the eval-mode generator.  run() notes what it measured in the ledger of the suite that called it."""
+them over the eval-mode generator; tests/test_elementwise_edges_gpu.py runs them over the table of tests/elementwise_edges.py
+(shapes off the step's) and the B = 23 step.  run() notes what it measured in the ledger of the suite that called it, and
+hands every output out between guard margins that Check.done() compares (Ops.full, Ops.guard)."""
 import ctypes
 
 import torch
 
+import elementwise_edges as E
 import elementwise_ref as R
 import launch_harness as LH
 from launch_harness import BF16_ROUND, P, call
@@ -63,7 +66,10 @@ GAMMA = {
     "colstats": 3.4e-7,         # 1.7e-7
     "axpby": 1.2e-7,            # 5.9e-8
     "spatial_sum": 2.2e-7,      # 1.1e-7
-    "tap_sums": 3e-8,           # 1.5e-8 (of the image's total |dy|)
+    # of the image's total |dy|.  1.5e-8 on the step's 64 x 64 and 128 x 128 maps, where that total is ~60 x the result;
+    # 1.6e-7 = 2.7 x 2^-24 on the 4 x 4 map of tests/elementwise_edges.py (C = 1028: one lane adds all 16 pixels, then
+    # total - row - column + corner: at most 18 roundings of 2^-24 of the total each)
+    "tap_sums": 3.2e-7,
     "cvec_table": 1e-7,         # 4.9e-8
     "cvec_grads": 6.6e-7,       # 3.3e-7
     "ca_net": 3e-7,             # 1.4e-7
@@ -88,8 +94,11 @@ def tdt(code):
 
 
 class Ops:
-    def __init__(self, gen, dev):
-        self.gen, self.dev = gen, dev
+    """Operands of one replay.  Outputs (full, guard) are views into a buffer with LH.GUARD_BYTES of a fixed bit pattern on
+    both sides; with a Check given, its done() asserts that both margins are still bit-identical."""
+
+    def __init__(self, gen, dev, chk=None):
+        self.gen, self.dev, self.chk = gen, dev, chk
 
     def randn(self, shape, dtype=torch.float32, scale=1.0):
         t = torch.randn(tuple(shape), generator=self.gen, device=self.dev) * scale
@@ -113,8 +122,21 @@ class Ops:
         sh = self.randint(-32, 33, (G, C)).float() / 32
         return torch.stack((mean, invstd, sc, sh), 1).contiguous()
 
+    def _guarded(self, shape, dtype):
+        n = torch.empty((), dtype=dtype).element_size()
+        for d in shape:
+            n *= d
+        buf = torch.full((n + 2 * LH.GUARD_BYTES,), LH.GUARD_BYTE, dtype=torch.uint8, device=self.dev)
+        if self.chk is not None:
+            self.chk.watch(buf, LH.GUARD_BYTES, n)
+        return buf[LH.GUARD_BYTES:LH.GUARD_BYTES + n].view(dtype).view(tuple(shape))
+
     def full(self, shape, dtype=torch.float32, value=float("nan")):
-        return torch.full(tuple(shape), value, dtype=dtype, device=self.dev)
+        return self._guarded(tuple(shape), dtype).fill_(value)
+
+    def guard(self, t):
+        """A copy of t between guard margins, for a buffer the launch updates in place (None stays None)."""
+        return None if t is None else self._guarded(t.shape, t.dtype).copy_(t)
 
 
 def swap_halves(t):
@@ -127,6 +149,14 @@ def drop_last_row(ref, G=1):
     m = ref.clone()
     v = m.reshape(G, -1, *m.shape[1:]) if m.dim() > 1 else m.view(G, -1)
     v[:, -1] = 0
+    return m
+
+
+def _drop_last_segment(v, B, n, S):
+    """v [B * n][...] with the rows of each image's last non-empty segment (E.segments(n, S)) zeroed."""
+    r0, r1 = [seg for seg in E.segments(n, S)[1] if seg[1] > seg[0]][-1]
+    m = v.clone(memory_format=torch.contiguous_format)
+    m.view(B, n, -1)[:, r0:r1] = 0
     return m
 
 
@@ -371,14 +401,15 @@ def replay_colstats(rec, o, chk):
     call("s2i_colstats", P(y), M, C, ldy, P(part), nparts)
     yd = y.double()[:, :C]
     chk.close("colstats", "part", part, R.colstats(yd, nparts), R.colstats(yd.abs(), nparts), 0.0,
-              {"last row missing": R.colstats(drop_last_row(yd), nparts)})
+              {"last row missing": R.colstats(drop_last_row(yd), nparts),
+               "last row chunk left out": R.colstats(_drop_last_segment(yd, 1, M, nparts), nparts)})
 
 
 def replay_axpby(rec, o, chk):
     n, a, b = rec["n"], rec["a"], rec["b"]
     x = o.randn((n,))
     y0 = o.randn((n,)) if b != 0 else o.full((n,))
-    y = y0.clone()
+    y = o.guard(y0)
     call("s2i_axpby", P(y), P(x), n, a, b)
     xd, yd = x.double(), y0.double()
     ref = R.axpby(yd, xd, a, b)
@@ -395,11 +426,13 @@ def replay_spatial_sum(rec, o, chk):
     src = o.randn((B * HW, ld), dt)
     dst = o.full((B, C))
     lib = _lib.load()
-    ws = torch.empty((lib.s2i_spatial_sum_workspace_bytes(B, HW, C) // 4 + 1,), device=o.dev)
+    ws = o.full((lib.s2i_spatial_sum_workspace_bytes(B, HW, C) // 4,))      # exactly what the library asks for
     call("s2i_spatial_sum_dt", rec["dtype"], P(src), ld, B, HW, C, P(dst), P(ws), ws.numel() * 4)
     sd = src.double()
     chk.close("spatial_sum", "dst", dst, R.spatial_sum(sd, B, C), R.spatial_sum(sd.abs(), B, C), 0.0,
-              {"last row of each image missing": R.spatial_sum(drop_last_row(sd, B), B, C)})
+              {"last row of each image missing": R.spatial_sum(drop_last_row(sd, B), B, C),
+               "last segment of each image left out": R.spatial_sum(_drop_last_segment(sd, B, HW, E.spatial_segments(HW)),
+                                                                    B, C)})
 
 
 def replay_tap_sums(rec, o, chk):
@@ -408,13 +441,17 @@ def replay_tap_sums(rec, o, chk):
     dy = o.randn((B, H, W, C), dt)
     out = o.full((B, 9, C))
     lib = _lib.load()
-    ws = torch.empty((lib.s2i_border_sums_workspace_bytes(B, H, W, C) // 4 + 1,), device=o.dev)
+    ws = o.full((lib.s2i_border_sums_workspace_bytes(B, H, W, C) // 4,))    # exactly what the library asks for
     call("s2i_tap_sums_dt", rec["dtype"], P(dy), B, H, W, C, P(out), P(ws), ws.numel() * 4)
     dd = dy.double()
     # inclusion and exclusion from the image total: the error scales with the total of |dy|
     absref = dd.abs().sum((1, 2)).unsqueeze(1).expand(B, 9, C)
-    chk.close("tap_sums", "tapsum", out, R.tap_sums(dd), absref, 0.0,
-              {"top and bottom border classes swapped": R.tap_sums(dd, swap_top_bottom=True)})
+    band = _drop_last_segment(dd.reshape(B * H, W * C), B, H, E.border_segments(H)).view(B, H, W, C)
+    mut = {"top and bottom border classes swapped": R.tap_sums(dd, swap_top_bottom=True),
+           "last row band of each image left out": R.tap_sums(band)}
+    if H != W:
+        mut["H and W exchanged"] = R.tap_sums(dd.reshape(B, W, H, C))      # the same buffer read as W rows of H pixels
+    chk.close("tap_sums", "tapsum", out, R.tap_sums(dd), absref, 0.0, mut)
 
 
 def replay_cvec_bias_table(rec, o, chk):
@@ -422,11 +459,18 @@ def replay_cvec_bias_table(rec, o, chk):
     cvec = o.randn((B, Cc))
     packed = o.randn((9, Ip, Op), scale=0.1)
     table = o.full((B, 9, N))
-    ws = torch.empty((B * 9 * N + 64,), device=o.dev)
+    ws = o.full((B * 9 * N,))                                               # exactly what the entry point requires
     call("s2i_cvec_bias_table", P(cvec), P(packed), B, Cc, Ip, Op, N, P(table), P(ws), ws.numel() * 4)
     cd, pd = cvec.double(), packed.double()
-    chk.close("cvec_table", "table", table, R.cvec_bias_table(cd, pd, Cc, N), R.cvec_bias_table(cd.abs(), pd.abs(), Cc, N),
-              0.0, {"top and bottom border classes swapped": R.cvec_bias_table(cd, pd, Cc, N, swap_top_bottom=True)})
+    ref = R.cvec_bias_table(cd, pd, Cc, N)
+    # the table of a map whose H and W are exchanged: row class and column class change places
+    mut = {"top and bottom border classes swapped": R.cvec_bias_table(cd, pd, Cc, N, swap_top_bottom=True),
+           "H and W exchanged": ref.view(B, 3, 3, N).transpose(1, 2).reshape(B, 9, N)}
+    if Cc % 4:
+        mc = cd.clone()
+        mc[:, Cc - Cc % 4:] = 0
+        mut["last Cc % 4 channels left out"] = R.cvec_bias_table(mc, pd, Cc, N)
+    chk.close("cvec_table", "table", table, ref, R.cvec_bias_table(cd.abs(), pd.abs(), Cc, N), 0.0, mut)
 
 
 def replay_cvec_grads(rec, o, chk):
@@ -436,14 +480,17 @@ def replay_cvec_grads(rec, o, chk):
     tapsum = o.randn((B, 9, N), scale=8.0)
     dc = o.full((B, Cc)) if rec["dc"] else None
     dw0 = o.randn((O, It, 3, 3)) if rec["dw"] else None
-    dw = None if dw0 is None else dw0.clone()
+    dw = o.guard(dw0)
     call("s2i_cvec_grads", P(cvec), P(packed), P(tapsum), B, Cc, Ip, Op, N, O, It, P(dc), P(dw), acc)
     cd, pd, td = cvec.double(), packed.double(), tapsum.double()
     if dc is not None:
         mt = td.clone()
         mt[:, 8] = 0
-        chk.close("cvec_grads", "dc", dc, R.cvec_dc(pd, td, Cc, N), R.cvec_dc(pd.abs(), td.abs(), Cc, N), 0.0,
-                  {"last tap missing": R.cvec_dc(pd, mt, Cc, N)})
+        ref = R.cvec_dc(pd, td, Cc, N)
+        mut = {"last tap missing": R.cvec_dc(pd, mt, Cc, N)}
+        if Cc > 64:
+            mut["channels from 64 on left out"] = torch.cat((ref[:, :64], torch.zeros_like(ref[:, 64:])), 1)
+        chk.close("cvec_grads", "dc", dc, ref, R.cvec_dc(pd.abs(), td.abs(), Cc, N), 0.0, mut)
     if dw is not None:
         base = dw0.double()[:, :Cc] if acc else 0
         ref = base + R.cvec_dw(cd, td, O)
@@ -495,12 +542,14 @@ def replay_reparam_forward(rec, o, chk):
 
 def replay_reparam_backward(rec, o, chk):
     B, E = rec["B"], rec["E"]
-    h, eps, dc = o.randn((B, 2 * E)), o.randn((B, E)), o.randn((B, E))
+    h, eps = o.randn((B, 2 * E)), o.randn((B, E))
+    dc = o.randn((B, E)) if rec["dc"] else None
     dmu = o.randn((B, E)) if rec["dmu"] else None
     dlv = o.randn((B, E)) if rec["dlogvar"] else None
     dh = o.full((B, 2 * E))
     call("s2i_reparam_backward", P(h), P(eps), P(dc), P(dmu), P(dlv), B, E, P(dh))
-    hd, ed, cd = h.double(), eps.double(), dc.double()
+    hd, ed = h.double(), eps.double()
+    cd = torch.zeros_like(ed) if dc is None else dc.double()       # a NULL dc is a zero gradient
     ref = R.reparam_backward(hd, ed, cd)
     ex = torch.exp(0.5 * hd[:, E:])
     absref = torch.cat((cd.abs(), cd.abs() * ed.abs() * 0.5 * ex * (1 + hd[:, E:].abs())), 1)
@@ -525,7 +574,11 @@ def replay_kl_forward(rec, o, chk):
     call("s2i_kl_forward", P(mb), rec["ldmu"], P(lb), rec["ldlv"], B, E, P(kl))
     ref = R.kl_forward(mu, lv)
     absref = 0.5 * torch.mean(1 + lv.abs() + mu * mu + torch.exp(lv) * (1 + lv.abs()))
-    chk.close("ca_net", "kl", kl, ref, absref, 0.0, {"last row missing": R.kl_forward(drop_last_row(mu), lv)})
+    mut = {"last row missing": R.kl_forward(drop_last_row(mu), lv)}
+    if B * E > 256:
+        terms = (1 + lv - mu * mu - torch.exp(lv)).reshape(-1)
+        mut["items from 256 on left out"] = -0.5 * terms[:256].sum() / (B * E)
+    chk.close("ca_net", "kl", kl, ref, absref, 0.0, mut)
 
 
 def replay_kl_backward(rec, o, chk):
@@ -564,7 +617,7 @@ def replay_logit_backward(rec, o, chk):
     dx0 = o.randn((B, 4, 4, C)) if rec["dx"] else None
     dw0 = o.randn((1, C, 4, 4)) if rec["dw"] else None
     db0 = o.randn((1,)) if rec["dbias"] else None
-    pre = lambda t, acc: None if t is None else (t.clone() if acc else torch.full_like(t, float("nan")))
+    pre = lambda t, acc: None if t is None else o.guard(t if acc else torch.full_like(t, float("nan")))
     dx, dw, db = pre(dx0, rec["acc_dx"]), pre(dw0, rec["acc_dw"]), pre(db0, rec["acc_dw"])
     call("s2i_logit_backward", P(x), P(w), P(prob), P(dprob), B, C, P(dx), rec["acc_dx"], P(dw), P(db), rec["acc_dw"])
     xd, wd, pd, gd = x.double(), w.double(), prob.double(), dprob.double()
@@ -585,6 +638,13 @@ def replay_logit_backward(rec, o, chk):
             mut = {"last image missing": base + dl[:-1].sum().view(1)}
         if acc:
             mut["accumulate treated as assign"] = ref
+        if B > 256:
+            if k == 1:
+                m = ref.clone()
+                m[256:] = 0
+            else:
+                m = R.logit_backward(xd[:256], wd, pd[:256], gd[:256])[k]
+            mut["images from 256 on left out"] = base + m
         chk.close("logit", name, got, base + ref, ab + (pre.double().abs() if acc else 0), 0.0, mut)
 
 
@@ -593,6 +653,9 @@ def _probs(o, n):
     p = o.rand((n,), 0.02, 0.98)
     if n >= 4:
         p[1], p[2] = 0.0, 1.0
+    else:                         # what fits: 1 at the end, 0 at the start (n = 1: the 0)
+        p[-1] = 1.0
+        p[0] = 0.0
     return p
 
 
@@ -606,13 +669,15 @@ def replay_bce_forward(rec, o, chk):
     B, t, wgt, acc = rec["B"], rec["target"], rec["weight"], rec["accumulate"]
     prob = _probs(o, B)
     loss0 = o.randn(())
-    loss = loss0.clone() if acc else o.full(())
+    loss = o.guard(loss0) if acc else o.full(())
     call("s2i_bce_forward", P(prob), t, B, wgt, P(loss), acc)
     pd = prob.double()
     base = loss0.double() if acc else 0
     ref = base + R.bce_forward(pd, t, wgt)
     absref = abs(wgt) * _bce_abs(pd, torch.tensor(t, dtype=torch.float64)).mean() + (loss0.double().abs() if acc else 0)
     mut = {"last element missing": base + wgt * R.bce_terms(pd[:-1], t).sum() / B}
+    if B > 256:
+        mut["items from 256 on left out"] = base + wgt * R.bce_terms(pd[:256], t).sum() / B
     chk.close("bce", "loss", loss, ref, absref, 0.0, mut)
 
 
@@ -629,16 +694,19 @@ def _bce_multi_operands(rec, o):
     G, H, B = rec["G"], rec["H"], rec["B"]
     probs = [_probs(o, G * B) for _ in range(H)]
     target = (o.randint(0, 2, (G * H,)).float())
-    target[0], target[-1] = 1.0, 0.0
+    target[-1] = 0.0
+    target[0] = 1.0
     weight = 0.5 + 0.37 * ((5 * torch.arange(G * H, device=o.dev)) % (G * H)).float()     # distinct, shuffled
     arr = (ctypes.c_void_p * H)(*[P(p) for p in probs])
-    wswap = weight.double().clone()
-    wswap[0], wswap[1] = weight[1].double(), weight[0].double()
-    return G, H, B, probs, target, weight, arr, wswap
+    wmut = weight.double().clone()
+    if G * H > 1:
+        wmut[0], wmut[1] = weight[1].double(), weight[0].double()
+        return G, H, B, probs, target, weight, arr, ("two terms' weights swapped", wmut)
+    return G, H, B, probs, target, weight, arr, ("the one term's weight taken as 1", torch.ones_like(wmut))
 
 
 def replay_bce_multi_forward(rec, o, chk):
-    G, H, B, probs, target, weight, arr, wswap = _bce_multi_operands(rec, o)
+    G, H, B, probs, target, weight, arr, (mname, wmut) = _bce_multi_operands(rec, o)
     loss = o.full(())
     call("s2i_bce_multi_forward", arr, P(target), P(weight), G, H, B, P(loss))
     pd = [p.double() for p in probs]
@@ -648,12 +716,17 @@ def replay_bce_multi_forward(rec, o, chk):
     for g in range(G):
         for h in range(H):
             absref = absref + wd[g * H + h] * _bce_abs(pd[h][g * B:(g + 1) * B], td[g * H + h]).mean()
-    chk.close("bce", "multi loss", loss, ref, absref, 0.0,
-              {"two terms' weights swapped": R.bce_multi_forward(pd, td, wswap, G, B)})
+    mut = {mname: R.bce_multi_forward(pd, td, wmut, G, B)}
+    if G * H * B > 256:
+        # the kernel's item e = (g H + h) B + b
+        flat = torch.stack([wd[g * H + h] * R.bce_terms(pd[h][g * B:(g + 1) * B], td[g * H + h])
+                            for g in range(G) for h in range(H)]).reshape(-1)
+        mut["items from 256 on left out"] = flat[:256].sum() / B
+    chk.close("bce", "multi loss", loss, ref, absref, 0.0, mut)
 
 
 def replay_bce_multi_backward(rec, o, chk):
-    G, H, B, probs, target, weight, arr, wswap = _bce_multi_operands(rec, o)
+    G, H, B, probs, target, weight, arr, (mname, wmut) = _bce_multi_operands(rec, o)
     gout = o.randn((1,))
     grads = [o.full((G * B,)) for _ in range(H)]
     parr = (ctypes.c_void_p * H)(*[P(t) for t in grads])
@@ -661,8 +734,8 @@ def replay_bce_multi_backward(rec, o, chk):
     pd = [p.double() for p in probs]
     td, wd = target.double(), weight.double()
     ref = torch.cat(R.bce_multi_backward(pd, td, wd, G, B, float(gout)))
-    mref = torch.cat(R.bce_multi_backward(pd, td, wswap, G, B, float(gout)))
-    chk.close("bce", "multi dprobs", torch.cat(grads), ref, ref.abs(), 0.0, {"two terms' weights swapped": mref})
+    mref = torch.cat(R.bce_multi_backward(pd, td, wmut, G, B, float(gout)))
+    chk.close("bce", "multi dprobs", torch.cat(grads), ref, ref.abs(), 0.0, {mname: mref})
 
 
 def replay_cal_loss(rec, o, chk):
@@ -670,20 +743,33 @@ def replay_cal_loss(rec, o, chk):
     X = o.randn((B, D)).double()
     S = (X @ X.t()).float()
     labels = o.randint(0, max(2, B // 4), (B,)).int()
+    if B == 2:
+        labels = torch.zeros_like(labels)          # the only draw with a same-label pair
+    same = (labels.view(-1, 1) == labels.view(1, -1)) & ~torch.eye(B, dtype=torch.bool, device=o.dev)
+    n = int(same.sum())
+    diff = S.double().mean() - S.double()[same].sum() / max(n, 1)
+    if n and diff <= 0:
+        # a draw that leaves the loss inactive (small D: the diagonal no longer dominates): lower the same-label scores by
+        # c, which raises diff by c (1 - n / B^2), to half the mean |score|
+        c = (0.5 * S.double().abs().mean() - diff) / (1 - n / (B * B))
+        S = (S.double() - c * same).float()
     loss0 = o.randn((1,))
-    loss = loss0.clone() if acc else o.full((1,))
+    loss = o.guard(loss0) if acc else o.full((1,))
     dS = o.full((B, B)) if rec["dscores"] else None
     call("s2i_cal_loss", P(S), P(labels), B, D, P(loss), acc, P(dS))
     Sd = S.double()
     lref, dref = R.cal_loss(Sd, labels, D)
     base = loss0.double() if acc else 0
-    same = (labels.view(-1, 1) == labels.view(1, -1)) & ~torch.eye(B, dtype=torch.bool, device=o.dev)
-    n = int(same.sum())
     labs = (Sd.abs().mean() + Sd.abs()[same].sum() / max(n, 1)) / D
     assert float(lref) > 0, "cal_loss operands leave the loss inactive"
     ml, md = R.cal_loss(Sd, labels, D, count_diagonal=True)
-    chk.close("cal_loss", "loss", loss, base + lref.view(1), labs + (loss0.double().abs() if acc else 0), 0.0,
-              {"diagonal pairs counted": base + ml.view(1)})
+    mut = {"diagonal pairs counted": base + ml.view(1)}
+    if B * B > 256:
+        # the sums over S, the pairs and their count stop at item 256 (the divisor B * B is a launch constant)
+        flat, fsame = Sd.reshape(-1)[:256], same.reshape(-1)[:256]
+        diff = flat.sum() / (B * B) - flat[fsame].sum() / max(int(fsame.sum()), 1)
+        mut["items from 256 on left out"] = base + (diff.clamp_min(0) / D).view(1)
+    chk.close("cal_loss", "loss", loss, base + lref.view(1), labs + (loss0.double().abs() if acc else 0), 0.0, mut)
     if dS is not None:
         chk.close("cal_loss", "dS", dS, dref, torch.full_like(dref, 2 * (1.0 / (B * B) + 1.0 / n) / D), 0.0,
                   {"diagonal pairs counted": md})
@@ -691,8 +777,8 @@ def replay_cal_loss(rec, o, chk):
 
 def replay_scale_dev(rec, o, chk):
     n = rec["n"]
-    x, a = o.randn((n,)), o.randn((1,))
-    x0 = x.clone()
+    x0, a = o.randn((n,)), o.randn((1,))
+    x = o.guard(x0)
     call("s2i_scale_dev", P(x), P(x), n, P(a))          # in place, as ClassAwareLoss.backward runs it
     ref = R.scale_dev(x0.double(), float(a))
     chk.close("scale_dev", "y", x, ref, ref.abs(), 0.0, {"last element missing": drop_last_row(ref)})
@@ -706,7 +792,8 @@ def run_adam(o, chk, n, lr, b1, b2, eps, step, use_dev, gscale):
     lr, b1, b2, eps, gscale = (_f32(v) for v in (lr, b1, b2, eps, gscale))     # what the kernel receives
     p, g = o.randn((n,)), o.randn((n,), scale=1e-2)
     m, v = o.randn((n,), scale=1e-2), o.rand((n,), 0.0, 1e-4)
-    p0, m0, v0 = p.clone(), m.clone(), v.clone()
+    p0, m0, v0 = p, m, v
+    p, m, v = o.guard(p0), o.guard(m0), o.guard(v0)
     t = 3 if use_dev else step
     sd = torch.tensor([t], dtype=torch.int32, device=o.dev) if use_dev else None
     call("s2i_adam_step", P(p), P(g), P(m), P(v), n, lr, b1, b2, eps, 0 if use_dev else step, P(sd), gscale)
@@ -730,8 +817,8 @@ def replay_adam_step(rec, o, chk):
 
 def replay_ema_update(rec, o, chk):
     n, dec = rec["n"], rec["decay"]
-    avg, p = o.randn((n,)), o.randn((n,))
-    a0 = avg.clone()
+    a0, p = o.randn((n,)), o.randn((n,))
+    avg = o.guard(a0)
     call("s2i_ema_update", P(avg), P(p), n, dec)
     ad, pd = a0.double(), p.double()
     chk.close("ema", "avg", avg, R.ema_update(ad, pd, dec), dec * ad.abs() + (1 - dec) * pd.abs(), 0.0,
@@ -751,6 +838,9 @@ def replay_nchw_to_nhwc(rec, o, chk):
     dst = o.full((B, H, W, Cp), dt)
     call("s2i_nchw_to_nhwc_dt", rec["dtype"], P(src), P(dst), B, C, H, W, Cp)
     chk.equal("nhwc (round to nearest even, zero pad channels)", dst, R.nchw_to_nhwc(src, Cp).to(dt))
+    # torch.equal takes -0 for +0: the pad channels as integers
+    pad = dst[..., C:].contiguous().view(torch.int32 if dt == torch.float32 else torch.int16)
+    chk.equal("nhwc pad channels (+0 bit patterns)", pad, torch.zeros_like(pad))
 
 
 def replay_nhwc_to_nchw(rec, o, chk):
@@ -817,6 +907,6 @@ def run(rec, what, ledger, fn=None):
     dev = torch.device("cuda:0")
     chk = LH.Check(what, GAMMA, ledger)
     with torch.no_grad():
-        (fn or REPLAY[rec["fn"]])(rec, Ops(LH.gen_rec(dev, rec), dev), chk)
+        (fn or REPLAY[rec["fn"]])(rec, Ops(LH.gen_rec(dev, rec), dev, chk), chk)
     torch.cuda.empty_cache()
     chk.done()

@@ -19,6 +19,8 @@ from speech_to_image_translation_without_text_amd import _lib
 
 BF16_ROUND = 2.0 ** -8       # round to nearest bf16 (8 significant bits): |rounded - v| <= 2^-8 |v|
 U = 2.0 ** -24               # fp32 unit roundoff
+GUARD_BYTES = 256            # margin on both sides of a guarded output buffer (a multiple of every alignment in use)
+GUARD_BYTE = 0xA5            # its fill: a fixed bit pattern compared as integers (no NaN, and any float added to it shows)
 
 # the train step's workloads, mode name -> (case, bf16 activations): BASELINE configs 2 and 4
 STEP_MODES = {
@@ -211,10 +213,14 @@ def fails(out, mref, absref, rnd, gamma):
 
 class Check:
     """Collects the comparisons of one test against the gamma table of its suite, notes them in the ledger; done() raises
-    with every failure."""
+    with every failure, a write into the margins of a watched buffer among them."""
 
     def __init__(self, what, gammas, ledger):
-        self.what, self.gammas, self.ledger, self.bad = what, gammas, ledger, []
+        self.what, self.gammas, self.ledger, self.bad, self.watched = what, gammas, ledger, [], []
+
+    def watch(self, buf, margin, nbytes):
+        """buf: uint8, GUARD_BYTE throughout when handed out; the bytes [margin, margin + nbytes) belong to the test."""
+        self.watched.append((buf, margin, nbytes))
 
     def close(self, fam, name, out, ref, absref, rnd=0.0, mutants=None):
         out, ref, absref = out.double(), ref.double(), torch.as_tensor(absref, dtype=torch.float64, device=ref.device)
@@ -237,6 +243,11 @@ class Check:
             self.bad.append("%s: not bit-identical (%d elements differ)" % (name, n))
 
     def done(self):
+        for i, (buf, margin, nbytes) in enumerate(self.watched):
+            for side, m in (("before", buf[:margin]), ("past the end of", buf[margin + nbytes:])):
+                hit = int((m != GUARD_BYTE).sum())
+                if hit:
+                    self.bad.append("%d guard bytes %s output %d (%d bytes) were written" % (hit, side, i, nbytes))
         assert not self.bad, "%s: %s" % (self.what, "; ".join(self.bad))
 
 
