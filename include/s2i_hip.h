@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define S2I_ABI_VERSION 6
+#define S2I_ABI_VERSION 7
 
 /* conv geometry kinds */
 #define S2I_CONV_K1      0  /* 1x1 / nn.Linear (model.py:179, 217)                              */
@@ -214,13 +214,16 @@ int s2i_split_packed_weight(const float* packed, int T, int R, int C, int planes
  *     fp32 copy P[t][R][C]: d->wmode = 0 uses P[t][k][n] (forward), 1 uses P[t][n][k] (input gradient), d->flip /
  *     the transposed-conv parity select the source tap; P may point at a row offset inside a tap (channel split).
  * d->Cc must be 0 (a broadcast vector is concatenated by the caller), d->act NONE, N and ldy multiples of 8. */
-int    s2i_conv_bf16_eligible(const s2i_conv_desc* d);
-size_t s2i_conv_bf16_workspace_bytes(const s2i_conv_desc* d);
-int    s2i_conv_bf16_stat_parts(const s2i_conv_desc* d);
-size_t s2i_conv_bf16_weight_elems(const s2i_conv_desc* d);
-/* Identifies the weight arrangement (CK | Npad << 8) the plan of this descriptor consumes: the same layer at another batch
- * size or map size may be planned onto another kernel, so a cache of packed bf16 weights is keyed by it.  -1 on error. */
-int    s2i_conv_bf16_weight_layout(const s2i_conv_desc* d);
+/* What s2i_conv_forward_bf16 launches for this descriptor, and everything a caller sizes by it (host only; one planning pass).
+   out = { kernel id (B16Kernel of csrc/s2i_bf16.h; -1: planned, but the kernel is not instantiated for this tile, i.e. the
+   layer is not eligible and the caller takes s2i_conv_forward_dt), output pixels per tile (128 or 256), output channels per
+   block BN, input channels per LDS stage CK, threads per block, grid x (the block slots of the persistent form where it is
+   taken) / y / z, tile width / rows / images, tiles, K splits, channel chunks per split, channel chunks, partial rows of the
+   statistics (part is [2][rows][N] floats), Npad, elements of the packed bf16 weights, dynamic LDS bytes, workspace bytes
+   (split-K slabs; 0: none), rows of y }.  The arrangement of the packed weights is identified by CK | Npad << 8: the same
+   layer at another batch or map size may be planned onto another kernel, so a cache of packed bf16 weights is keyed by it.
+   Non-zero, with out zeroed and the error text set, where the plan refuses the descriptor. */
+int s2i_conv_bf16_plan_query(const s2i_conv_desc* d, long long out[21]);
 int s2i_pack_conv_weight_bf16(const s2i_conv_desc* d, const float* packed, int R, int C, unsigned short* out,
                               void* stream);
 /* The bf16 copies of a whole network in one launch (after the fused Adam step).  s2i_pack16_item_fill (host only, no

@@ -28,7 +28,7 @@ RESAMPLE_MAX_WINDOW = 13826
 TOPK_MAX = 64
 RANK_GATHER, RANK_COUNT = 0, 1      # s2i_rank_rows modes (S2I_RANK_*)
 DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4
-ABI_VERSION = 6
+ABI_VERSION = 7
 # s2i_wgrad_plan_query: the WgKernel values of csrc/s2i_igemm.h in order, and the twelve outputs
 WGRAD_KERNELS = ("f32-128x128", "f32-128x64", "f32-128x32", "f32-64x64", "f32-256x128", "f32-256x256", "f32-96x64", "f32-96x32",
                  "f32in-128x128", "b16-128x128", "b16-128x64", "b16-128x32", "b16-64x64", "b16-256x128", "b16-256x256",
@@ -43,6 +43,13 @@ FWD_KERNELS = ("f32-128x128", "f32-128x64", "f32-128x32", "f32-96x128", "f32in-1
 FWD_PLAN_FIELDS = ("kernel", "bm", "bn", "threads", "gx", "gy", "gz", "splitk", "cps", "nchunks", "prep_elems", "reduce",
                    "ws_bytes", "M", "K")
 FWD_REDUCE_NONE, FWD_REDUCE_PLAIN, FWD_REDUCE_COLSTATS, FWD_REDUCE_STATS = 0, 1, 2, 3
+# s2i_conv_bf16_plan_query: the B16Kernel values of csrc/s2i_bf16.h in order (kind-BNxCK of the 128-pixel kernel, then the
+# 256-pixel forms) and the twenty-one outputs
+B16_KERNELS = ("b16-k3s1-128x16", "b16-k3s1-64x32", "b16-k3s1-32x64", "b16-k3s1-32x32", "b16-k4s2-128x32", "b16-k4s2-128x16",
+               "b16-k4s2-64x32", "b16-k4s2-32x32", "b16-tconv-128x32", "b16-tconv-64x64", "b16-tconv-32x64", "b16-tconv-32x32",
+               "b16v2-k3s1", "b16v2-tconv", "b16v2-k4s2-pw66", "b16v2-k4s2")
+B16_PLAN_FIELDS = ("kernel", "pixels", "bn", "ck", "threads", "gx", "gy", "gz", "tw", "th", "tb", "tiles", "splitk", "cps",
+                   "nchunks", "parts", "npad", "w_elems", "smem", "ws_bytes", "rows")
 
 c_int, c_float, c_void_p, c_size_t, c_ll = (ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
                                             ctypes.c_size_t, ctypes.c_longlong)
@@ -94,11 +101,7 @@ _SIGNATURES = {
     "s2i_split_packed_weight": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
     "s2i_wgrad_workspace_bytes_split": (c_size_t, [ctypes.POINTER(WgradDesc), c_int]),
     "s2i_conv_wgrad_split": (c_int, [ctypes.POINTER(WgradDesc), c_int, P, P, P, P, P, c_size_t, P]),
-    "s2i_conv_bf16_eligible": (c_int, [ctypes.POINTER(ConvDesc)]),
-    "s2i_conv_bf16_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc)]),
-    "s2i_conv_bf16_stat_parts": (c_int, [ctypes.POINTER(ConvDesc)]),
-    "s2i_conv_bf16_weight_elems": (c_size_t, [ctypes.POINTER(ConvDesc)]),
-    "s2i_conv_bf16_weight_layout": (c_int, [ctypes.POINTER(ConvDesc)]),
+    "s2i_conv_bf16_plan_query": (c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_ll * 21)]),
     "s2i_pack16_item_fill": (c_int, [ctypes.POINTER(ConvDesc), P, c_int, c_int, P, ctypes.POINTER(Pack16Item)]),
     "s2i_pack_conv_weights_bf16_batched": (c_int, [P, c_int, c_int, P]),
     "s2i_pack_conv_weight_bf16": (c_int, [ctypes.POINTER(ConvDesc), P, c_int, c_int, P, P]),
@@ -294,6 +297,18 @@ def conv_plan(d, x_dtype=DT_F32, y_dtype=DT_F32, planes=0, bias=False, cls_bias=
         return None
     plan = dict(zip(FWD_PLAN_FIELDS, out))
     plan["kernel"] = FWD_KERNELS[plan["kernel"]]
+    return plan
+
+
+def conv_bf16_plan(d):
+    """What s2i_conv_forward_bf16 launches for ConvDesc d (s2i_conv_bf16_plan_query, host only): a dict of B16_PLAN_FIELDS
+    with the kernel as its B16_KERNELS name, None for a tile the kernel is not instantiated for (the layer is not eligible);
+    or None where the plan refuses the descriptor (s2i_last_error says why).  The weight layout key is ck | npad << 8."""
+    out = (c_ll * 21)()
+    if load().s2i_conv_bf16_plan_query(ctypes.byref(d), ctypes.byref(out)):
+        return None
+    plan = dict(zip(B16_PLAN_FIELDS, out))
+    plan["kernel"] = B16_KERNELS[plan["kernel"]] if plan["kernel"] >= 0 else None
     return plan
 
 

@@ -2,7 +2,7 @@
 // convolutions whose activations live in HBM as bf16 NHWC, weights as bf16 (fp32 masters stay in the trainer's flat buffers),
 // products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, BatchNorm statistics taken from the fp32 accumulators.
 //   s2i_bf16_conv.hip     the 128-pixel kernel        s2i_bf16_pack.hip   weight re-pack, split-K reduction with bf16 output
-//   s2i_bf16_conv_v2.hip  the 256-pixel kernel        s2i_bf16_plan.hip   plan_bf16, LDS sizing, the entry points (no kernel)
+//   s2i_bf16_conv_v2.hip  the 256-pixel kernel        s2i_bf16_plan.hip   plan_bf16, its query, the entry point (no kernel)
 // Only what two or more units use lives here.  Kernels are never declared here: each __global__ template is defined and
 // instantiated in exactly one unit and reached from the others through the launch_* host functions below.
 //
@@ -142,12 +142,40 @@ __device__ __forceinline__ void transpose_tile_bf16(unsigned char* smem, const f
 }
 
 // ---- host side ---------------------------------------------------------------------------------
+// Every instantiation of the two convolution kernels, each list in the order its unit instantiates them (that order is the
+// layout of the unit's code object).  The B16Kernel values, the names, the planner's match and the two
+// launch switches are generated from these lists and nothing else names an instantiation.
+//   conv_bf16_kernel (128 pixels): kind, BN, CK, TG
+#define S2I_BF16_TILES(X) \
+  X(K3S1, 128, 16, 9) X(K3S1, 64, 32, 9) X(K3S1, 32, 64, 9) X(K3S1, 32, 32, 9) \
+  X(K4S2, 128, 32, 4) X(K4S2, 128, 16, 8) X(K4S2, 64, 32, 8) X(K4S2, 32, 32, 8) \
+  X(TCONV, 128, 32, 4) X(TCONV, 64, 64, 4) X(TCONV, 32, 64, 4) X(TCONV, 32, 32, 4)
+//   conv_bf16_v2_kernel (256 pixels, BN = 128): id, kind, CK, TG, two patch buffers, padded patch width.  The two-buffer forms
+//   first, the stride-2 forms last
+#define S2I_BF16_V2_TILES(X) \
+  X(V2_K3S1, K3S1, 32, 3, true, 0) X(V2_TCONV, TCONV, 64, 2, true, 0) X(V2_K4S2_PW66, K4S2, 32, 4, false, 66) \
+  X(V2_K4S2, K4S2, 32, 4, false, 0)
+
+enum B16Kernel {
+  B16_NO_KERNEL = -1,   // planned, but conv_bf16_kernel is not instantiated for this (kind, BN, CK): the layer is not eligible
+#define S2I_ID(K, bn, ck, tg) B16_##K##_##bn##x##ck,
+  S2I_BF16_TILES(S2I_ID)
+#undef S2I_ID
+#define S2I_ID(id, K, ck, tg, pdb, pwc) B16_##id,
+  S2I_BF16_V2_TILES(S2I_ID)
+#undef S2I_ID
+  B16_KERNEL_COUNT
+};
+
+// What a descriptor launches, all of it: plan_bf16 decides, s2i_conv_bf16_plan_query reports, the launch_* functions obey.
 struct BPlan {
   int v2;   // conv_bf16_v2_kernel: 256-pixel tiles, 512 threads
   int kb, T, NG, TG, Ho, Wo, nphases, BN, CK, Npad;
   int lgTW, lgTH, lgTB, tilesX, tilesY, tilesB, PH, PW, npix;
   int nchunk, splitk, cps, gridM, gridN;
   long long Mrows;
+  B16Kernel kernel;
+  int threads, gx, smem;   // block size; grid x (gridM, or the block slots of the persistent form); dynamic LDS bytes
 };
 
 // more than 64 KB of dynamic LDS needs the attribute once per kernel: `raised` is the instantiation's own flag
@@ -161,16 +189,12 @@ inline int bf16_raise_lds(const void* kernel, int bytes, bool* raised) {
 
 // Unit interfaces.  A launch_* function returns 0 after a launch, 1 with the error text set.  None of them is exported.
 #pragma GCC visibility push(hidden)
-// s2i_bf16_plan.hip.  v2_padded: the 66-pixel-wide stride-2 patch takes the padded-row instantiation; bf16_patch_bytes: one
-// patch buffer in LDS; bf16_smem_bytes: the dynamic LDS of the planned kernel
+// s2i_bf16_plan.hip: the one place that knows which kernel, grid and LDS size a descriptor launches; the kernels' names for
+// error texts ("K3S1_128x16", "V2_K4S2_PW66"; _lib.B16_KERNELS holds the ones tools and tests read)
 int plan_bf16(const s2i_conv_desc* d, BPlan* pl);
-bool v2_padded(const BPlan& pl);
-size_t bf16_patch_bytes(const BPlan& pl);
-size_t bf16_smem_bytes(const BPlan& pl);
-// s2i_bf16_conv.hip: the 128-pixel kernel; bf16_has_kernel: it is instantiated for this tile
-bool bf16_has_kernel(int kb, int bn, int ck);
+extern const char* const b16_kernel_names[B16_KERNEL_COUNT];
+// s2i_bf16_conv.hip: the 128-pixel kernel (!pl.v2); s2i_bf16_conv_v2.hip: the 256-pixel kernel (pl.v2)
 int launch_conv_bf16(const BPlan& pl, const ConvBP& p, dim3 grid, hipStream_t st);
-// s2i_bf16_conv_v2.hip: the 256-pixel kernel (pl.v2); sets grid.x itself (persistent form)
 int launch_conv_bf16_v2(const BPlan& pl, const ConvBP& p, dim3 grid, hipStream_t st);
 // s2i_bf16_pack.hip: sums the pl.splitk slabs of ws into y (bf16) and, with part, the BatchNorm column statistics
 int launch_splitk_reduce_bf16(const s2i_conv_desc* d, const BPlan& pl, unsigned short* y, float* part, const float* ws,

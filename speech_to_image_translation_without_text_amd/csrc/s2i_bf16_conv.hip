@@ -274,7 +274,7 @@ template <int KIND, int BN, int CK, int TG>
 int launch_one(const BPlan& pl, const ConvBP& p, dim3 grid, hipStream_t st) {
   static bool raised = false;
   if (bf16_raise_lds((const void*)conv_bf16_kernel<KIND, BN, CK, TG>, 96 * 1024, &raised)) return 1;
-  hipLaunchKernelGGL((conv_bf16_kernel<KIND, BN, CK, TG>), grid, dim3(256), bf16_smem_bytes(pl), st, p);
+  hipLaunchKernelGGL((conv_bf16_kernel<KIND, BN, CK, TG>), grid, dim3(pl.threads), pl.smem, st, p);
   return 0;
 }
 
@@ -284,28 +284,21 @@ int launch_one(const BPlan& pl, const ConvBP& p, dim3 grid, hipStream_t st) {
 
 }  // namespace
 
-// the instantiations: kind, BN, CK, TG
-#define S2I_BF16_TILES(X) \
-  X(KB_K3S1, 128, 16, 9) X(KB_K3S1, 64, 32, 9) X(KB_K3S1, 32, 64, 9) X(KB_K3S1, 32, 32, 9) \
-  X(KB_K4S2, 128, 32, 4) X(KB_K4S2, 128, 16, 8) X(KB_K4S2, 64, 32, 8) X(KB_K4S2, 32, 32, 8) \
-  X(KB_TCONV, 128, 32, 4) X(KB_TCONV, 64, 64, 4) X(KB_TCONV, 32, 64, 4) X(KB_TCONV, 32, 32, 4)
-
-bool bf16_has_kernel(int kb, int bn, int ck) {
-#define S2I_CASE(K, bn_, ck_, tg_) if (kb == K && bn == bn_ && ck == ck_) return true;
-  S2I_BF16_TILES(S2I_CASE)
-#undef S2I_CASE
-  return false;
-}
-
+// the kernel the plan names (S2I_BF16_TILES of s2i_bf16.h, instantiated in its order), where its taps per stage are the planned ones
 int launch_conv_bf16(const BPlan& pl, const ConvBP& p, dim3 grid, hipStream_t st) {
-  const int kb = pl.kb, bn = pl.BN, ck = pl.CK, tg = pl.TG;
 #ifdef S2I_DIAG   // libs2i_hip_diag.so only (make diag): ablation / in-kernel timeline instantiations of tools/conv16_*.py
   int rc = 0;
   if (diag_launch_conv_bf16(pl, p, grid, st, &rc)) return rc;
 #endif
-#define S2I_CASE(K, bn_, ck_, tg_) \
-  if (kb == K && bn == bn_ && ck == ck_ && tg == tg_) return launch_one<K, bn_, ck_, tg_>(pl, p, grid, st);
-  S2I_BF16_TILES(S2I_CASE)
+  switch (pl.kernel) {
+#define S2I_CASE(K, bn, ck, tg)                                        \
+  case B16_##K##_##bn##x##ck:                                          \
+    if (pl.TG != tg) break;                                            \
+    return launch_one<KB_##K, bn, ck, tg>(pl, p, grid, st);
+    S2I_BF16_TILES(S2I_CASE)
 #undef S2I_CASE
-  S2I_FAIL("conv(bf16): no kernel for kind %d BN=%d CK=%d TG=%d", kb, bn, ck, tg);
+    default: break;
+  }
+  S2I_FAIL("conv(bf16): no kernel for kind %d BN=%d CK=%d TG=%d (the plan names %s)", pl.kb, pl.BN, pl.CK, pl.TG,
+           pl.kernel < 0 ? "none" : b16_kernel_names[pl.kernel]);
 }

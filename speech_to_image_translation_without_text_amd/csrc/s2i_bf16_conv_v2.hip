@@ -413,28 +413,12 @@ __global__ __launch_bounds__(512, 1) void conv_bf16_v2_kernel(ConvBP p) {
   }
 }
 
-// blocks along x for the second-generation kernel: persistent (one block per CU looping over its tiles) where the kernel
-// supports it -- single patch buffer, no split-K, and a patch region large enough for the epilogue's transpose
-int v2_grid_x(const BPlan& pl) {
-  const int pers = s2i_tune(S2I_TUNE_B16_PERSIST, 1);
-  if (!pers || pl.kb != KB_K4S2 || pl.splitk != 1 || bf16_patch_bytes(pl) < bf16_epilogue_bytes(256, 128)) return pl.gridM;
-  int nblk = (pers > 1 ? pers : 256) / (pl.gridN * pl.nphases);   // knob b16_persist > 1: that many block slots (tests)
-  if (nblk < 1) nblk = 1;
-  if (pl.gridM <= nblk) return pl.gridM;
-  // a block walks ceil(gridM / nblk) tiles: persistent only where that rounding costs little (measured: 144 tiles over
-  // 64 slots -- 3 rounds for 2.25 rounds of work -- lost what the prefetch across tiles gained)
-  if (pers == 1 && (pl.gridM % nblk) != 0 && pl.gridM < 6 * nblk) return pl.gridM;
-  return nblk;
-}
-
-template <int KIND, int CK, int TG, bool PDB, int PWC = 0>
+template <int KIND, int CK, int TG, bool PDB, int PWC>
 int launch_v2(const BPlan& pl, const ConvBP& p, dim3 grid, hipStream_t st) {
-  const size_t shb = bf16_smem_bytes(pl);
-  S2I_REQUIRE(shb <= 160 * 1024, "conv(bf16): %zu bytes of LDS", shb);
-  grid.x = v2_grid_x(pl);
+  S2I_REQUIRE(pl.smem <= 160 * 1024, "conv(bf16): %s needs %d bytes of LDS", b16_kernel_names[pl.kernel], pl.smem);
   static bool raised = false;
   if (bf16_raise_lds((const void*)conv_bf16_v2_kernel<KIND, CK, TG, PDB, 0, PWC>, 160 * 1024, &raised)) return 1;
-  hipLaunchKernelGGL((conv_bf16_v2_kernel<KIND, CK, TG, PDB, 0, PWC>), grid, dim3(512), shb, st, p);
+  hipLaunchKernelGGL((conv_bf16_v2_kernel<KIND, CK, TG, PDB, 0, PWC>), grid, dim3(pl.threads), pl.smem, st, p);
   return 0;
 }
 
@@ -444,14 +428,19 @@ int launch_v2(const BPlan& pl, const ConvBP& p, dim3 grid, hipStream_t st) {
 
 }  // namespace
 
+// the kernel the plan names.  S2I_BF16_V2_TILES (s2i_bf16.h) lists the two-buffer forms first: the order of the cases is the
+// order of the instantiations in the code object
 int launch_conv_bf16_v2(const BPlan& pl, const ConvBP& p, dim3 grid, hipStream_t st) {
 #ifdef S2I_DIAG   // libs2i_hip_diag.so only (make diag): the in-kernel timeline instantiations of tools/conv16_timeline.py
   int rc = 0;
   if (diag_launch_conv_bf16_v2(pl, p, grid, st, &rc)) return rc;
 #endif
-  // the two-buffer forms first: the order here is the order of the instantiations in the code object
-  if (pl.kb == KB_K3S1) return launch_v2<KB_K3S1, 32, 3, true>(pl, p, grid, st);
-  if (pl.kb == KB_TCONV) return launch_v2<KB_TCONV, 64, 2, true>(pl, p, grid, st);
-  if (v2_padded(pl)) return launch_v2<KB_K4S2, 32, 4, false, 66>(pl, p, grid, st);
-  return launch_v2<KB_K4S2, 32, 4, false>(pl, p, grid, st);
+  switch (pl.kernel) {
+#define S2I_CASE(id, K, ck, tg, pdb, pwc) \
+  case B16_##id: return launch_v2<KB_##K, ck, tg, pdb, pwc>(pl, p, grid, st);
+    S2I_BF16_V2_TILES(S2I_CASE)
+#undef S2I_CASE
+    default: break;
+  }
+  S2I_FAIL("conv(bf16): kernel %d is not a 256-pixel kernel", (int)pl.kernel);
 }

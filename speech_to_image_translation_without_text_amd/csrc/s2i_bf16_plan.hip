@@ -1,5 +1,6 @@
-// bf16 activation path: the launch plan, LDS sizing and the entry points of the convolution (no kernel: s2i_bf16_conv.hip,
-// s2i_bf16_conv_v2.hip and s2i_bf16_pack.hip hold them; s2i_bf16.h says what the path is).
+// bf16 activation path: the launch plan -- tile, K split, kernel, grid and LDS size, decided here and nowhere else -- its
+// query and the entry point of the convolution (no kernel: s2i_bf16_conv.hip, s2i_bf16_conv_v2.hip and s2i_bf16_pack.hip
+// hold them; s2i_bf16.h says what the path is).
 #include "s2i_bf16.h"
 
 namespace {
@@ -24,7 +25,57 @@ size_t workspace_bytes(const s2i_conv_desc* d, const BPlan& pl) {
   return pl.splitk > 1 ? (size_t)pl.splitk * pl.Mrows * d->N * sizeof(float) : 0;
 }
 
+// the 66-pixel-wide stride-2 patch (32-column tiles) takes the padded-row instantiation
+bool v2_padded(const BPlan& pl) { return pl.v2 && pl.kb == KB_K4S2 && pl.PW == 66 && pl.CK == 32; }
+
+// one patch buffer in LDS
+size_t patch_bytes(const BPlan& pl) {
+  return ((size_t)pl.npix * (pl.CK * 2 + (v2_padded(pl) ? 16 : 0)) + 255) & ~(size_t)255;
+}
+
+// dynamic LDS: [patch | weight stage], or for the 256-pixel kernel [patch (x2) | weight stage x2 | 1 KB sink]; reused by the
+// epilogue
+size_t smem_bytes(const BPlan& pl) {
+  const size_t ab = patch_bytes(pl), stage = (size_t)pl.TG * pl.BN * pl.CK * 2;
+  const size_t main_b = pl.v2 ? (pl.kb == KB_K4S2 ? 1 : 2) * ab + 2 * stage + 1024 : ab + stage;
+  const size_t epi = bf16_epilogue_bytes(pl.v2 ? 256 : 128, pl.BN);
+  return main_b > epi ? main_b : epi;
+}
+
+// blocks along x for the second-generation kernel: persistent (one block per CU looping over its tiles) where the kernel
+// supports it -- single patch buffer, no split-K, and a patch region large enough for the epilogue's transpose
+int v2_grid_x(const BPlan& pl) {
+  const int pers = s2i_tune(S2I_TUNE_B16_PERSIST, 1);
+  if (!pers || pl.kb != KB_K4S2 || pl.splitk != 1 || patch_bytes(pl) < bf16_epilogue_bytes(256, 128)) return pl.gridM;
+  int nblk = (pers > 1 ? pers : 256) / (pl.gridN * pl.nphases);   // knob b16_persist > 1: that many block slots (tests)
+  if (nblk < 1) nblk = 1;
+  if (pl.gridM <= nblk) return pl.gridM;
+  // a block walks ceil(gridM / nblk) tiles: persistent only where that rounding costs little (measured: 144 tiles over
+  // 64 slots -- 3 rounds for 2.25 rounds of work -- lost what the prefetch across tiles gained)
+  if (pers == 1 && (pl.gridM % nblk) != 0 && pl.gridM < 6 * nblk) return pl.gridM;
+  return nblk;
+}
+
+// the instantiation a finished tile plan runs on.  conv_bf16_kernel is matched on (kind, BN, CK): a TG its instantiation does
+// not have is refused by launch_conv_bf16, not here
+B16Kernel pick_kernel(const BPlan& pl) {
+  if (pl.v2) return pl.kb == KB_K3S1 ? B16_V2_K3S1 : pl.kb == KB_TCONV ? B16_V2_TCONV : v2_padded(pl) ? B16_V2_K4S2_PW66 : B16_V2_K4S2;
+#define S2I_CASE(K, bn, ck, tg) if (pl.kb == KB_##K && pl.BN == bn && pl.CK == ck) return B16_##K##_##bn##x##ck;
+  S2I_BF16_TILES(S2I_CASE)
+#undef S2I_CASE
+  return B16_NO_KERNEL;
+}
+
 }  // namespace
+
+const char* const b16_kernel_names[B16_KERNEL_COUNT] = {
+#define S2I_NAME(K, bn, ck, tg) #K "_" #bn "x" #ck,
+    S2I_BF16_TILES(S2I_NAME)
+#undef S2I_NAME
+#define S2I_NAME(id, K, ck, tg, pdb, pwc) #id,
+    S2I_BF16_V2_TILES(S2I_NAME)
+#undef S2I_NAME
+};
 
 int plan_bf16(const s2i_conv_desc* d, BPlan* pl) {
   S2I_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->N > 0, "conv(bf16): non-positive extent");
@@ -127,38 +178,24 @@ int plan_bf16(const s2i_conv_desc* d, BPlan* pl) {
   }
   pl->cps = s2i_cdiv(pl->nchunk, splitk);
   pl->splitk = s2i_cdiv(pl->nchunk, pl->cps);
+  pl->kernel = pick_kernel(*pl);
+  pl->threads = pl->v2 ? 512 : 256;
+  pl->gx = pl->v2 ? v2_grid_x(*pl) : pl->gridM;
+  pl->smem = (int)smem_bytes(*pl);
   return 0;
 }
 
-// the 66-pixel-wide stride-2 patch (32-column tiles) takes the padded-row instantiation
-bool v2_padded(const BPlan& pl) { return pl.v2 && pl.kb == KB_K4S2 && pl.PW == 66 && pl.CK == 32; }
-
-size_t bf16_patch_bytes(const BPlan& pl) {
-  return ((size_t)pl.npix * (pl.CK * 2 + (v2_padded(pl) ? 16 : 0)) + 255) & ~(size_t)255;
+extern "C" int s2i_conv_bf16_plan_query(const s2i_conv_desc* d, long long out[21]) {
+  for (int i = 0; i < 21; ++i) out[i] = 0;
+  BPlan pl;
+  if (plan_bf16(d, &pl)) return 1;
+  const long long v[21] = {pl.kernel, pl.v2 ? 256 : 128, pl.BN, pl.CK, pl.threads, pl.gx, pl.gridN, pl.nphases * pl.splitk,
+                           1 << pl.lgTW, 1 << pl.lgTH, 1 << pl.lgTB, pl.gridM, pl.splitk, pl.cps, pl.nchunk,
+                           stat_parts(pl, d->groups), pl.Npad, (long long)pl.nphases * pl.T * pl.Npad * d->Cx, pl.smem,
+                           (long long)workspace_bytes(d, pl), pl.Mrows};
+  for (int i = 0; i < 21; ++i) out[i] = v[i];
+  return 0;
 }
-
-// [patch | weight stage], or for the 256-pixel kernel [patch (x2) | weight stage x2 | 1 KB sink]; reused by the epilogue
-size_t bf16_smem_bytes(const BPlan& pl) {
-  const size_t ab = bf16_patch_bytes(pl), stage = (size_t)pl.TG * pl.BN * pl.CK * 2;
-  const size_t main_b = pl.v2 ? (pl.kb == KB_K4S2 ? 1 : 2) * ab + 2 * stage + 1024 : ab + stage;
-  const size_t epi = bf16_epilogue_bytes(pl.v2 ? 256 : 128, pl.BN);
-  return main_b > epi ? main_b : epi;
-}
-
-// The planner's queries: `fail` for a descriptor the plan refuses (s2i_last_error says why), else `expr` of the plan pl.
-#define S2I_BF16_QUERY(type, name, fail, expr)      \
-  extern "C" type name(const s2i_conv_desc* d) {    \
-    BPlan pl;                                       \
-    return plan_bf16(d, &pl) ? (fail) : (expr);     \
-  }
-S2I_BF16_QUERY(int, s2i_conv_bf16_eligible, 0, (pl.v2 || bf16_has_kernel(pl.kb, pl.BN, pl.CK)) ? 1 : 0)
-// identifies the arrangement of the bf16 weights the plan of this descriptor consumes (a cache key for callers: the same
-// layer at another batch size may be planned onto another kernel)
-S2I_BF16_QUERY(int, s2i_conv_bf16_weight_layout, -1, pl.CK | (pl.Npad << 8))
-S2I_BF16_QUERY(size_t, s2i_conv_bf16_workspace_bytes, 0, workspace_bytes(d, pl))
-S2I_BF16_QUERY(int, s2i_conv_bf16_stat_parts, -1, stat_parts(pl, d->groups))
-S2I_BF16_QUERY(size_t, s2i_conv_bf16_weight_elems, 0, (size_t)pl.nphases * pl.T * pl.Npad * d->Cx)
-#undef S2I_BF16_QUERY
 
 extern "C" int s2i_conv_forward_bf16(const s2i_conv_desc* d, const unsigned short* x, const unsigned short* w,
                                      const float* cls_bias, unsigned short* y, float* part, void* ws, size_t ws_bytes,
@@ -188,7 +225,7 @@ extern "C" int s2i_conv_forward_bf16(const s2i_conv_desc* d, const unsigned shor
 #else
   p.dbg = 0;
 #endif
-  dim3 grid(pl.gridM, pl.gridN, pl.nphases * pl.splitk);
+  dim3 grid(pl.gx, pl.gridN, pl.nphases * pl.splitk);
   const hipStream_t st = (hipStream_t)stream;
   if (pl.v2 ? launch_conv_bf16_v2(pl, p, grid, st) : launch_conv_bf16(pl, p, grid, st)) return 1;
   S2I_LAUNCH_CHECK("conv_bf16");

@@ -297,25 +297,41 @@ def cast(t, dtype):
     return out
 
 
+_B16_KERNEL, _B16_CK, _B16_PARTS, _B16_NPAD, _B16_W_ELEMS, _B16_WS_BYTES = (
+    _lib.B16_PLAN_FIELDS.index(f) for f in ("kernel", "ck", "parts", "npad", "w_elems", "ws_bytes"))
+
+
+def _bf16_plan(d):
+    """The answers of s2i_conv_bf16_plan_query for descriptor d, read by index (_B16_*: no dict on the launch path), or None
+    where the bf16 kernels do not take the layer: the plan refuses it or names no kernel.  The answer stays on the descriptor
+    (d.b16_plan), so that conv_any and the bf16_weight it calls with d plan once between them."""
+    out = (ctypes.c_longlong * 21)()
+    if _lib_ready().s2i_conv_bf16_plan_query(ctypes.byref(d), ctypes.byref(out)) or out[_B16_KERNEL] < 0:
+        out = None
+    d.b16_plan = out
+    return out
+
+
 def bf16_weight(packed, d, w_offset):
     """bf16 weights of one convolution descriptor in the stage order of s2i_conv_forward_bf16, cached on the packed fp32
     tensor until it is re-packed (the fused Adam bumps `_s2i_gen`)."""
     lib = _lib_ready()
+    plan = getattr(d, 'b16_plan', None) or _bf16_plan(d)
+    if plan is None:
+        raise _lib.S2IError("bf16_weight: the bf16 convolution kernels do not take this layer")
     cache = getattr(packed, '_s2i_b16', None)
     gen = getattr(packed, '_s2i_gen', 0)
     if cache is None or cache[0] != gen:
         cache = (gen, {})
         packed._s2i_b16 = cache
-    key = (d.kind, d.wmode, d.flip, d.Cx, d.N, int(w_offset), lib.s2i_conv_bf16_weight_layout(ctypes.byref(d)))
+    key = (d.kind, d.wmode, d.flip, d.Cx, d.N, int(w_offset), plan[_B16_CK] | plan[_B16_NPAD] << 8)
     ent = cache[1].get(key)
     if ent is None:
         old = getattr(packed, '_s2i_b16_bufs', None)
         if old is None:
             old = packed._s2i_b16_bufs = {}
         ent = old.get(key)               # reuse the allocation across generations
-        n = lib.s2i_conv_bf16_weight_elems(ctypes.byref(d))
-        if n == 0:
-            check(1, "s2i_conv_bf16_weight_elems")
+        n = plan[_B16_W_ELEMS]
         if ent is None or ent.numel() != n:
             ent = torch.empty(n, dtype=torch.bfloat16, device=packed.device)
             old[key] = ent
@@ -344,8 +360,10 @@ def conv_any(kind, x, packed, N, *, wmode=0, flip=0, bias=None, act=ACT_NONE, st
     d = ConvDesc(kind, B, H, W, Cx, 0, N, wmode, flip, wR, ldw, act, 1 if stats else 0, N, groups,
                  1 if cls_bias is not None else 0, 0, 0, 0)
     y = torch.empty((B, Ho, Wo, N), dtype=out_dtype, device=x.device)
-    fast = (x.dtype == torch.bfloat16 and out_dtype == torch.bfloat16 and bias is None and act == ACT_NONE
-            and N % 8 == 0 and lib.s2i_conv_bf16_eligible(ctypes.byref(d)))
+    # the one planning pass of a bf16 launch: eligibility, partial rows, weight layout and workspace are its answers
+    plan = (_bf16_plan(d) if x.dtype == torch.bfloat16 and out_dtype == torch.bfloat16 and bias is None and act == ACT_NONE
+            and N % 8 == 0 else None)
+    fast = plan is not None
     if EXEC_LOG is not None:
         T = _TAPS[kind]
         _log_exec("conv%s k%d %s[%d,%d,%d,%d]->%d" % ("16" if fast else "", kind, "T" if wmode else "", B, H, W, Cx, N),
@@ -354,12 +372,10 @@ def conv_any(kind, x, packed, N, *, wmode=0, flip=0, bias=None, act=ACT_NONE, st
     part, nparts = None, 0
     if fast:
         if stats:
-            nparts = lib.s2i_conv_bf16_stat_parts(ctypes.byref(d))
-            if nparts <= 0:
-                check(1, "s2i_conv_bf16_stat_parts")
+            nparts = plan[_B16_PARTS]
             part = torch.empty((2, nparts, N), dtype=torch.float32, device=x.device)
         wb = bf16_weight(packed, d, w_offset)
-        ws = _ws.get(lib.s2i_conv_bf16_workspace_bytes(ctypes.byref(d)), x.device)
+        ws = _ws.get(plan[_B16_WS_BYTES], x.device)
         check(lib.s2i_conv_forward_bf16(ctypes.byref(d), ptr(x), ptr(wb), ptr(cls_bias), ptr(y), ptr(part), ptr(ws),
                                         ws.numel() * 4, stream()), "s2i_conv_forward_bf16")
         return y, part, nparts

@@ -233,12 +233,8 @@ def record_id(i, rec):
 
 
 # ---- what a record's plan reaches, from the planners' host queries ---------------------------------------------------
-# The library loads and plans without a device: s2i_conv_plan_query and s2i_wgrad_plan_query name the kernel, tile and split
-# of a launch.  What the bf16 unit's queries cannot tell is restated from its planner and marked so.
-def _cdiv(a, b):
-    return -(-a // b)
-
-
+# The library loads and plans without a device: s2i_conv_plan_query, s2i_conv_bf16_plan_query and s2i_wgrad_plan_query name
+# the kernel, tile, grid and split of a launch, and nothing of the planners is restated here.
 def _geom(kind, H, W):
     return ops._geom(kind, H, W) if kind != ops.TCONV_K4S2 else (H, W)     # the planners count rows per phase
 
@@ -281,7 +277,7 @@ def conv_plan(rec):
     reach = set()
     with _lib.tuning(**rec.get("tune", {})):
         if rec["fast"]:
-            return _bf16_plan(rec, lib, M, nph, Ho, Wo)
+            return _bf16_plan(rec, M, nph)
         d = conv_desc(rec)
         told = _lib.conv_plan(d, int(rec["x"][1] == "bf16"), int(rec["out_dtype"] == "bf16"), 0, rec["bias"], rec["cls_bias"])
         assert told is not None, lib.s2i_last_error()
@@ -310,52 +306,24 @@ def conv_plan(rec):
     return dict(M=M, nphases=nph, K=K, nchunks=nchunks, splitk=sk, cps=cps, bm=bm, BN=BN, reach=reach)
 
 
-def _bf16_plan(rec, lib, M, nph, Ho, Wo):
-    import ctypes
-    B, N, kind = rec["x"][0][0], rec["N"], rec["kind"]
-    d = conv_desc(rec)
-    assert lib.s2i_conv_bf16_eligible(ctypes.byref(d)) == 1, lib.s2i_last_error()
-    ws = lib.s2i_conv_bf16_workspace_bytes(ctypes.byref(d))
-    sk = max(ws // (M * nph * N * 4), 1)
-    parts = lib.s2i_conv_bf16_stat_parts(ctypes.byref(conv_desc(rec, stats=1, nosplit=1)))
-    assert parts > 0 and parts % nph == 0, parts
-    grid_m = parts // nph
-    ck = lib.s2i_conv_bf16_weight_layout(ctypes.byref(d)) & 0xff
-    # pixels per tile: the tile is as wide as the map (up to 32), then rows, then images (tile_geom of s2i_bf16_plan.hip); the tile count tells
-    # 128 from 256 pixels, and where both give the same count the channel chunk does (16 / 32 against 32 / 64)
-    cand = {}
-    for bm in (128, 256):
-        tw = min(Wo, 32)
-        th = min(bm // tw, Ho)
-        tb = bm // (tw * th)
-        if (Wo // tw) * (Ho // th) * _cdiv(B, tb) == grid_m:
-            cand[bm] = tb
-    assert cand, (grid_m, rec)
-    if len(cand) == 2:
-        big = ck == (64 if kind == ops.TCONV_K4S2 else 32) and kind != ops.CONV_K4S2
-        cand = {256: cand[256]} if big else {128: cand[128]}
-    (bm, tb), = cand.items()
+def _bf16_plan(rec, M, nph):
+    """Pixels and images per tile, tiles, K splits and the grid are what s2i_conv_bf16_plan_query says."""
+    from speech_to_image_translation_without_text_amd import _lib
+    told = _lib.conv_bf16_plan(conv_desc(rec))
+    assert told is not None and told["kernel"] is not None, (told, _lib.load().s2i_last_error())
+    assert told["rows"] == M * nph, told
+    B, bm, tb, gx, tiles = rec["x"][0][0], told["pixels"], told["tb"], told["gx"], told["tiles"]
     reach = set()
     if B % tb:
         reach.add("b16-ragged-%d" % bm)
-    # restated from v2_grid_x (s2i_bf16_conv_v2.hip): the persistent form is the stride-2 256-pixel kernel, unsplit, on b16_persist block slots
-    persist = rec.get("tune", {}).get("b16_persist", 1)
-    if bm == 256 and kind == ops.CONV_K4S2 and sk == 1 and persist > 1:
-        nblk = max(persist // _cdiv(N, 128), 1)
-        if grid_m > nblk and grid_m % nblk:
-            reach.add("b16-persist-uneven")
-    return dict(M=M, nphases=nph, splitk=sk, bm=bm, tb=tb, gridM=grid_m, reach=reach)
-
-
-# K rows x N columns per block of plan_wgrad's tile numbers as restated below (the fp32 kernels' WgKernel shapes; 6 / 7: bf16)
-_WG_TILES = {0: (128, 128), 1: (128, 64), 2: (128, 32), 3: (64, 64), 4: (96, 64), 5: (96, 32), 6: (256, 128), 7: (256, 256),
-             8: (256, 128), 9: (256, 256)}
+    if gx < tiles and tiles % gx:         # persistent form: gx block slots walk the tiles, some one tile more than others
+        reach.add("b16-persist-uneven")
+    return dict(M=M, nphases=nph, splitk=told["splitk"], bm=bm, tb=tb, gridM=tiles, reach=reach)
 
 
 def wgrad_plan(rec):
-    """dict(M, K, N, tile, rows3, splitk, reach).  The workspace query gives the split count; the tile shape is restated
-    from plan_wgrad: tiles 0 - 5 follow from K and N alone, 8 / 9 (fp32) and 6 / 7 (bf16) are forced through the knobs wgrad_bm /
-    wgrad16_bm where 256 divides K (and N), and the row-segment kernel takes 3x3 layers of 32 / 64 channels on maps at least 32 wide."""
+    """dict(M, K, N, tile, rows3, splitk, reach) from what s2i_wgrad_plan_query says: the tile is its (bm, bn), the row-segment
+    and bf16 families are in the kernel's name, the pixel / stage tail is M % stage."""
     import ctypes
     from speech_to_image_translation_without_text_amd import _lib
     lib = _lib.load()
@@ -370,39 +338,23 @@ def wgrad_plan(rec):
         ws = lib.s2i_wgrad_workspace_bytes_dt(ctypes.byref(d), int(a16), int(g16))
         if not (a16 or g16):
             assert ws == lib.s2i_wgrad_workspace_bytes(ctypes.byref(d))
-    assert ws > 0 and ws % (K * N * 4) == 0, (ws, K, N, lib.s2i_last_error())
-    sk = ws // (K * N * 4)
-    fp32 = not (a16 or g16)
-    tile = 0 if N > 64 else (1 if N > 32 else 2)
-    if K <= 64 and 32 < N <= 64:
-        tile = 3
-    if fp32 and K % 96 == 0 and N <= 64 and _cdiv(K, 128) * 128 * 5 > K * 6:
-        tile = 4 if N > 32 else 5
-    force = tune.get("wgrad_bm", 0)
-    if fp32 and tile == 0 and K % 256 == 0 and force in (256, 512):
-        tile = 9 if (force == 512 and N % 256 == 0) else 8
-    elif fp32 and tile == 0 and K % 256 == 0:
-        assert force == 128, "a weight gradient that may take the 256-row tiles needs wgrad_bm set: %r" % (rec,)
-    force16 = tune.get("wgrad16_bm", 0)
-    if a16 and g16 and tile == 0 and K % 256 == 0 and force16 in (256, 512):
-        tile = 7 if (force16 == 512 and N % 256 == 0) else 6
-    rows3 = (fp32 and rec["kind"] == ops.CONV_K3S1 and rec["cvec"] == 0 and Ca in (32, 64) and W >= 32 and N % 32 == 0
-             and N <= 128)
-    with _lib.tuning(**tune):
         told = _lib.wgrad_plan(d, int(a16), int(g16))
-    assert told["ws_slabs"] == sk and (told["K"], told["M"]) == (K, M), told
-    if not rows3 and not (a16 and g16) and not (g16 and Ca == 4):
-        assert (told["bm"], told["bn"]) == _WG_TILES[tile], (told, tile)      # the restated tile is the planned one
+    assert ws > 0 and ws == told["ws_slabs"] * K * N * 4 and (told["K"], told["M"]) == (K, M), (ws, told, lib.s2i_last_error())
+    # the record itself: where the cost model may pick any of the 128- / 256-row fp32 tiles, the record pins one
+    if told["kernel"] in ("f32-128x128", "f32-256x128", "f32-256x256") and K % 256 == 0:
+        assert tune.get("wgrad_bm"), "a weight gradient that may take the 256-row tiles needs wgrad_bm set: %r" % (rec,)
+    family = told["kernel"].split("-")[0]
+    tile, rows3 = (told["bm"], told["bn"]), family == "rows3"
     reach = set()
-    if a16 and g16 or (g16 and Ca == 4):
-        if M % 64:
+    if family in ("b16", "b16d1"):
+        if M % told["stage"]:
             reach.add("b16-wg-stagetail")
     elif rows3:
         if B & (B - 1):
             reach.add("wg-rows3-odd-batch")
-    elif M % 32:
-        reach.add("wg-pixtail-%dx%d" % _WG_TILES[tile])
-    return dict(M=M, K=K, N=N, tile=tile, rows3=rows3, splitk=sk, reach=reach)
+    elif M % told["stage"]:
+        reach.add("wg-pixtail-%dx%d" % tile)
+    return dict(M=M, K=K, N=N, tile=tile, rows3=rows3, splitk=told["ws_slabs"], reach=reach)
 
 
 def plan(rec):

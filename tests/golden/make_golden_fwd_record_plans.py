@@ -5,7 +5,7 @@ Until s2i_conv_plan_query existed no host query named the kernel a forward convo
 which kernel, tile and K split each record of tests/conv_edges.py and tests/image_layer_edges.py reaches was a Python
 restatement of the dispatch in those two helper modules (conv_plan in each).  This script froze their answers before the
 restatements were deleted: it was run ONCE, in a checkout of that commit with its library built, and wrote for every
-fp32-path forward record (fn conv_raw / conv_any, not the bf16 unit's `fast` records, which _bf16_plan keeps describing)
+fp32-path forward record (fn conv_raw / conv_any, not the bf16 unit's `fast` records, which s2i_conv_bf16_plan_query describes)
 
   conv_edges          i, id, M, nphases, K, nchunks, splitk, cps, bm (null where the parent could not tell 96 from 128
                       rows), BN, reach (sorted)

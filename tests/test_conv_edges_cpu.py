@@ -1,9 +1,8 @@
 """The edge table (tests/conv_edges.py) reaches what it claims, and the train step's census does not.
 
 The planners are host code and the library loads without a device, so every record's plan is asked of them here: the
-fp32 forward's tile, K split and chunk counts of s2i_conv_plan_query, the weight gradient's of s2i_wgrad_plan_query; the
-bf16 unit has no such query yet, so conv_edges._bf16_plan derives pixels and images per tile from its statistics rows /
-weight layout and restates the persistent form of the 256-pixel kernel, and says so.  No GPU."""
+fp32 forward's tile, K split and chunk counts of s2i_conv_plan_query, the weight gradient's of s2i_wgrad_plan_query, the
+bf16 unit's pixels and images per tile, tiles and (persistent) grid of s2i_conv_bf16_plan_query.  No GPU."""
 import json
 import os
 import sys

@@ -338,14 +338,14 @@ def test_new_symbols_declared_and_bound():
     for name in NEW_SYMBOLS:
         assert re.search(r"\b%s\(" % name, header), name
         assert name in _lib._SIGNATURES, name
-    assert _lib.ABI_VERSION == 6
+    assert _lib.ABI_VERSION == 7
 
 
 def test_new_symbols_exported_and_refuse_bad_arguments():
     from speech_to_image_translation_without_text_amd import _lib
     lib = _lib.load()
     assert not [n for n in NEW_SYMBOLS if not hasattr(lib, n)]
-    assert lib.s2i_version() == 6
+    assert lib.s2i_version() == 7
     # host-side planning and argument checks, no device needed
     assert lib.s2i_conv1d_wgrad_workspace_bytes(64, 2048, 64, 64, 3, 1, 1) >= 64 * 64 * 3 * 4 * 256     # 131 072 rows: split
     assert lib.s2i_conv1d_wgrad_workspace_bytes(64, 64, 512, 1024, 5, 2, 2) == 4 * 1024 * 5 * 512 * 4     # 2 048 rows: 4 slabs

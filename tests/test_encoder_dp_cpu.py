@@ -233,7 +233,7 @@ def test_symbol_is_declared_bound_exported_and_refuses_bad_arguments():
     assert "s2i_adam_l2_step" in _lib.EXPORTED_SYMBOLS and callable(ops.adam_l2_step)
     assert len(_lib._SIGNATURES["s2i_adam_l2_step"][1]) == 14
     lib = _lib.load()
-    assert lib.s2i_version() == _lib.ABI_VERSION == 6
+    assert lib.s2i_version() == _lib.ABI_VERSION == 7
     one = 16                                                 # any non-null address: the checks run before a launch
     args = lambda p=one, g=one, m=one, v=one, n=4, step=1, sd=None: (p, g, m, v, n, 1e-3, 0.9, 0.999, 1e-8, 1e-5, step, sd,
                                                                      1.0, None)

@@ -142,7 +142,7 @@ def test_symbols_are_declared_and_bound():
     assert "s2i_specaug" in _lib.EXPORTED_SYMBOLS and "s2i_specaug_workspace_bytes" in _lib.EXPORTED_SYMBOLS
     assert "s2i_specaug.hip" in open(os.path.join(os.path.dirname(_lib.LIB_PATH), "csrc", "Makefile")).read()
     lib = _lib.load()
-    assert lib.s2i_version() == 6
+    assert lib.s2i_version() == 7
     assert lib.s2i_specaug_workspace_bytes(0) == 0 and lib.s2i_specaug_workspace_bytes(3) >= 3 * 4
 
 

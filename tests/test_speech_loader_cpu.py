@@ -150,6 +150,6 @@ def test_symbol_is_declared_and_bound():
         "void* stream"]
     assert "s2i_logmel_gather" in _lib.EXPORTED_SYMBOLS
     lib = _lib.load()
-    assert lib.s2i_version() == 6
+    assert lib.s2i_version() == 7
     # refused before anything touches a device
     assert lib.s2i_logmel_gather(None, None, None, 1, 1, None, None) != 0 and b"null" in lib.s2i_last_error()

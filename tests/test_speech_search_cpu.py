@@ -19,10 +19,10 @@ def test_symbol_is_declared_exported_and_bound():
     header = open(os.path.join(ROOT, "include", "s2i_hip.h")).read()
     assert re.search(r"\bint s2i_topk_rows\(const float\* scores, int Q, int N, int lds, int base, int k, "
                      r"float\* best_score, int\* best_row,\s+int merge, void\* stream\);", header)
-    assert "#define S2I_ABI_VERSION 6" in header
+    assert "#define S2I_ABI_VERSION 7" in header
     lib = _lib.load()
     assert hasattr(lib, "s2i_topk_rows") and "s2i_topk_rows" in _lib.EXPORTED_SYMBOLS
-    assert lib.s2i_version() == _lib.ABI_VERSION == 6
+    assert lib.s2i_version() == _lib.ABI_VERSION == 7
     assert _lib.TOPK_MAX == 64
     makefile = open(os.path.join(ROOT, "speech_to_image_translation_without_text_amd", "csrc", "Makefile")).read()
     assert "s2i_topk.hip" in makefile
