@@ -6,7 +6,7 @@
 // Only what two or more units use lives here.  Kernels are never declared here: each __global__ template is defined and
 // instantiated in exactly one unit and reached from the others through the launch_* host functions below.
 //
-// What is different from the fp32 / split kernels of s2i_conv_fwd.hip (which gather an im2col chunk per 32-deep K step
+// What is different from the fp32 / split kernels of s2i_conv_fwd.h (which gather an im2col chunk per 32-deep K step
 // from global memory, i.e. pull every input pixel through L2 once per tap):
 //   * the block stages a 2-D input PATCH with its halo in LDS once per channel chunk -- the pixels of TB images x
 //     (TH-1)*s+KH rows x (TW-1)*s+KW columns -- and every tap reads its MFMA A-fragments from that patch at a

@@ -1,6 +1,6 @@
 // Forward launch of the implicit-GEMM convolutions: conv_forward_impl fills the parameter block of the plan (plan_fwd,
-// s2i_conv_plan.hip) and launches it; the s2i_conv_forward* entry points.  The kernels live in s2i_conv_fwd.hip and
-// s2i_conv_thin.hip and are reached through the launch_* functions of s2i_igemm.h.
+// s2i_conv_plan.hip) and launches it; the s2i_conv_forward* entry points.  The kernels live in the s2i_conv_fwd*.hip
+// units and s2i_conv_thin.hip and are reached through the launch_* functions of s2i_igemm.h.
 #include "s2i_igemm.h"
 
 static int conv_forward_impl(const s2i_conv_desc* d, const float* x, const float* cvec, const float* w,

@@ -1,8 +1,9 @@
 // Pieces shared by the implicit-GEMM convolution units (internal, next to s2i_tile.h): the kernel parameter block and gather
 // helpers of the StackGAN-v2 convolutions, the fp32 matrix loop, the bounds-checked loads, the bf16 split, the two plans
 // and the host functions that cross a unit boundary.  Only what two or more units use lives here; a helper of one family
-// stays in that family's file.  Kernels are never declared here: each __global__ template is defined and instantiated in
-// exactly one unit and reached from the others through the launch_* host functions below.
+// stays in that family's file.  Kernels are never declared here: each __global__ template is defined in one unit, or in
+// one private header where several units instantiate it (s2i_conv_fwd.h), every instantiation is compiled in exactly one
+// unit, and the other units reach it through the launch_* host functions below.
 //
 // One gather formulation covers every convolution on the StackGAN-v2 path
 // (reference StackGAN_v2/model.py:125-140, 144-169, 287-298, 358-398):
@@ -284,7 +285,7 @@ struct WgPlan {
 // bytes of the workspace every s2i_wgrad_workspace_bytes* query reports and the launcher asks for
 static inline size_t wg_workspace_bytes(const WgPlan& pl, int N) { return (size_t)pl.ws_slabs * pl.K * N * sizeof(float); }
 
-// Unit interfaces.  A launch_* function returns 0 after a launch, 1 with the error text set.  None of them is exported.
+// Unit interfaces.  An int launch_* function returns 0 after a launch, 1 with the error text set.  None of them is exported.
 #pragma GCC visibility push(hidden)
 // s2i_conv_plan.hip: both return 0, or 1 with the error text set.  fwd_mode names the operands of an entry point's
 // arguments; plan_fwd decides the launch, or refuses a layer that no kernel takes in this mode.
@@ -293,6 +294,13 @@ int plan_fwd(const s2i_conv_desc* d, const FwdMode& mode, FwdPlan* pl);
 // s2i_conv_fwd.hip: the matrix families (the byte windows of p come from conv_forward_impl), small_n_conv_kernel and the
 // reduction of a split
 int launch_igemm_fwd(const FwdPlan& pl, const IgemmP& p, hipStream_t st);
+// s2i_conv_fwd_<BM>x<BN>.hip, s2i_conv_fwd_split.hip: the instantiations of one fp32 tile shape each, and of the split-bf16
+// tiles.  Only launch_igemm_fwd calls them; they launch and return nothing, the launch check is its.
+void launch_fwd_128x128(const FwdPlan& pl, const IgemmP& p, dim3 grid, hipStream_t st);
+void launch_fwd_128x64(const FwdPlan& pl, const IgemmP& p, dim3 grid, hipStream_t st);
+void launch_fwd_128x32(const FwdPlan& pl, const IgemmP& p, dim3 grid, hipStream_t st);
+void launch_fwd_96x128(const FwdPlan& pl, const IgemmP& p, dim3 grid, hipStream_t st);
+void launch_fwd_split(const FwdPlan& pl, const IgemmP& p, dim3 grid, hipStream_t st);
 int launch_small_n_conv(const FwdPlan& pl, const IgemmP& p, hipStream_t st);
 int launch_splitk_reduce(const s2i_conv_desc* d, const FwdPlan& pl, const float* bias, float* y, float* part, void* ws,
                          int y16, void* stream);

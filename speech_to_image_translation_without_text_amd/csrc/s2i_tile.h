@@ -1,4 +1,4 @@
-// Tile pieces shared by the matrix kernels of the convolution units (s2i_conv_fwd.hip, s2i_wgrad.hip, s2i_conv2d.hip) and
+// Tile pieces shared by the matrix kernels of the convolution units (s2i_conv_fwd.h, s2i_wgrad.hip, s2i_conv2d.hip) and
 // of the bf16 units (s2i_bf16_conv.hip, s2i_bf16_conv_v2.hip) (internal).  Every kernel there keeps its result as f32x16 acc[TM][TN]: a wave owns TM x TN MFMA tiles of
 // 32 x 32, wave (wm, wn) of the block's WAVES_M x WAVES_N.
 // The helpers take plain arguments, no kernel parameter struct, and the caller supplies what differs between kernels (how a
