@@ -842,6 +842,42 @@ int s2i_topk_rows(const float* scores, int Q, int N, int lds, int base, int k, f
 int s2i_rank_rows(const float* scores, int Q, int N, int lds, int base, const int* own_row, const int* query_label,
                   const int* row_label, int n_labels, float* own_score, int* gt, int* eq, int mode, void* stream);
 
+/* ---- kernel inception distance and k-nearest-neighbour manifolds, chunk by chunk --------------------------------------
+ * KID (the unbiased MMD^2 with the cubic polynomial kernel) and precision / recall / density / coverage compare every
+ * row of one set of Inception pool3 rows with every row of another (gan_metrics.kid, gan_metrics.prdc).  Like
+ * s2i_topk_rows and s2i_rank_rows the three folds below take one [Q, N] block of scores at a time, exactly as
+ * ops.score_rows writes it (fp32, row stride lds >= N floats, column j = row base + j of the other set), so the
+ * [rows, rows] matrix never exists.  Common to the three: Q >= 1, 1 <= N <= 2^30, base >= 0, base + N <= INT_MAX; any
+ * row stride, base and pointer are taken (16-byte loads where the addresses allow, single loads before and after); one
+ * block per query; no atomics, no workspace, no allocation, no synchronisation, no environment reads; bad arguments
+ * return non-zero before any launch. */
+/* sum[q] += sum over j of k(q, j),  k = t * t * t,  t = (double)scores[q][j] * inv_d + 1.0, every operation rounded on
+ * its own in fp64 (no contraction).  When own_base >= 0 the column j with base + j == own_base + q is left out: the
+ * off-diagonal sum of a set against itself (query q is row own_base + q of that set); own_base = -1 leaves nothing out.
+ * The sum runs in a fixed order (lane accumulators, a wave butterfly, the waves in order through LDS), so the same
+ * inputs and geometry give the same bits from run to run; against another order it differs by at most
+ * N 2^-52 sum_j |k|.  sum is fp64 [Q], accumulated in place across chunks; the caller zeroes it. */
+int s2i_polykernel_rows(const float* scores, int Q, int N, int lds, int base, int own_base, double inv_d, double* sum,
+                        void* stream);
+/* Rewrites the block in place to the negated squared distance,
+ *   scores[q][j] = -fmaxf(0.f, (q_norm2[q] + row_norm2[base + j]) - 2.f * scores[q][j]),
+ * in fp32, evaluated as written (2 s is exact, so contracting the subtraction into an FMA changes nothing: an fp32
+ * restatement on the host reproduces the bits).  A NaN stays a NaN.  The own row (base + j == own_base + q, own_base >= 0;
+ * -1: none) becomes -inf.  Negated, so that s2i_topk_rows, which takes the largest, finds the nearest rows as it is.
+ * q_norm2 is fp32 [Q]; row_norm2 is fp32 over the whole other set (n_rows entries, indexed by global row:
+ * base + N <= n_rows). */
+int s2i_sqdist_rows(float* scores, int Q, int N, int lds, int base, int own_base, const float* q_norm2,
+                    const float* row_norm2, int n_rows, void* stream);
+/* Compare-only fold of a block s2i_sqdist_rows has rewritten (nd = negated squared distances):
+ *   count[q] += #{j : nd[q][j] >= row_bound[base + j]}   (int32: the balls of the other set that hold query q),
+ *   best[q] = max(best[q], max over j of nd[q][j])        (fp32: minus the squared distance to the nearest row).
+ * row_bound[r] is -radius_r^2, column k - 1 of the top k of the other set against itself, used as it comes; it is fp32
+ * over the whole other set (n_rows entries: base + N <= n_rows).  A NaN entry counts nowhere and never becomes best; a NaN
+ * bound counts nothing.  The caller zeroes count and sets best to -inf; either of the two may be null, not both.
+ * Integer counters and comparisons only: exact, whatever the division of a row among lanes, waves or chunks. */
+int s2i_ball_rows(const float* nd, int Q, int N, int lds, int base, const float* row_bound, int n_rows, int* count,
+                  float* best, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

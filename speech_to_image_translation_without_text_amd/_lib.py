@@ -214,6 +214,9 @@ _SIGNATURES = {
     "s2i_moments_accumulate": (c_int, [P, c_int, c_int, c_ll, P, P, P]),
     "s2i_topk_rows": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P]),
     "s2i_rank_rows": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, P]),
+    "s2i_polykernel_rows": (c_int, [P, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, P, P]),
+    "s2i_sqdist_rows": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P]),
+    "s2i_ball_rows": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, P, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

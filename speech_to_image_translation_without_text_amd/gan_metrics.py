@@ -4,7 +4,7 @@ trainer.py:88-159, whose evaluate() computes them only in dead code after its ea
     python -m speech_to_image_translation_without_text_amd.gan_metrics --cfg cfg/birds_3stages.yml \\
         --netG output/Model/netG_600.pth --inception inception_v3_google-1a9a5a14.pth --data_dir data/birds \\
         [--real_stats stats.npz] [--save_images] [--seed S] [--max_items K] [--out metrics.json]
-        [--googlenet bvlc_googlenet.caffemodel [--consistency_cosine]]
+        [--googlenet bvlc_googlenet.caffemodel [--consistency_cosine]] [--kid] [--prdc] [--nearest_k K]
 
 G runs in .eval() over every embedding column of every test item, its last-stage images go through the native
 Inception-v3 (inception.py), and the pool3 rows of each pass are folded into fp64 moments on the device
@@ -18,9 +18,16 @@ quantised as its PNG would be, goes through BVLC GoogLeNet on the device (google
 ten-view pool5 row is ranked against the speech embeddings of the whole split (retrieval.Gallery.rank, s2i_rank_rows):
 recall@1/5/10, the median rank and the closed-form R-precision under `fake_*` keys, with the same scores of the real
 images under `real_*` keys as the ceiling the speech encoder allows.
+
+With --kid, --prdc or --nearest_k the pool3 rows are kept on the device after all (`FeatureRows`) and the record gains
+`kid` (the unbiased cubic-kernel MMD^2 over the full samples) and `precision`, `recall`, `density`, `coverage` (k-nearest-
+neighbour manifolds): `kid` and `prdc` below fold the chunked scores of the fp32 matrix kernel with s2i_polykernel_rows,
+s2i_sqdist_rows + s2i_topk_rows and s2i_ball_rows, so no rows x rows matrix exists.  The real
+set has one row per item and the fake set one per sentence.
 """
 import argparse
 import json
+import math
 import os
 import queue
 import random
@@ -119,12 +126,213 @@ def nhwc4_as_nchw(img):
     return img[..., :3].permute(0, 3, 1, 2)
 
 
+class FeatureRows:
+    """The D-wide fp32 rows of a stream themselves, on `device` in arrival order: what KID and the nearest-neighbour
+    manifolds need and FeatureMoments drops.  The buffer holds `capacity` rows and doubles when more arrive (one device
+    copy per doubling).  n rows so far; rows() is the [n, D] view of them."""
+
+    def __init__(self, D, device, capacity=1024):
+        self.D = int(D)
+        self.device = torch.device(device)
+        self._buf = torch.empty(max(1, int(capacity)), self.D, dtype=torch.float32, device=self.device)
+        self.n = 0
+
+    def __len__(self):
+        return self.n
+
+    def append(self, rows):
+        """Copy (N, D) fp32 device rows (any row stride) behind the kept ones: device to device, no sync."""
+        if rows.dim() != 2 or rows.shape[1] != self.D or rows.dtype != torch.float32 or rows.device != self.device:
+            raise ValueError("rows must be (N, %d) fp32 on %s, got %s %s on %s"
+                             % (self.D, self.device, tuple(rows.shape), rows.dtype, rows.device))
+        n = rows.shape[0]
+        if self.n + n > self._buf.shape[0]:
+            grown = torch.empty(max(2 * self._buf.shape[0], self.n + n), self.D, dtype=torch.float32, device=self.device)
+            grown[:self.n].copy_(self._buf[:self.n])
+            self._buf = grown
+        self._buf[self.n:self.n + n].copy_(rows)
+        self.n += n
+
+    def rows(self):
+        return self._buf[:self.n]
+
+
+def _device_rows(name, rows):
+    """A FeatureRows or an fp32 [n, D] device tensor as that tensor."""
+    rows = rows.rows() if isinstance(rows, FeatureRows) else rows
+    if not torch.is_tensor(rows) or rows.dim() != 2 or rows.dtype != torch.float32:
+        raise ValueError("%s: rows must be a FeatureRows or an fp32 [n, D] tensor" % name)
+    if not rows.is_cuda:
+        raise _lib.S2IError("%s runs on the MI355X kernels: there is no CPU fallback (rows on %s)" % (name, rows.device))
+    return rows.detach()
+
+
+def _pair_blocks(queries, chunks, query_block, scratch):
+    """(q0, q1, start, scores [q1 - q0, n]) for every (query block, chunk) pair: one launch of the fp32 matrix kernel each,
+    all into the one scratch block."""
+    for q0 in range(0, queries.shape[0], query_block):
+        q1 = min(queries.shape[0], q0 + query_block)
+        for start, n, packed in chunks:
+            yield q0, q1, start, ops.score_rows(queries[q0:q1], packed, n, scratch)
+
+
+def _pair_args(name, a, b, chunk_rows, query_block):
+    from . import retrieval
+    a, b = _device_rows(name, a), _device_rows(name, b)
+    if a.shape[1] != b.shape[1] or a.device != b.device:
+        raise ValueError("%s: the two sets must share width and device, got %s on %s and %s on %s"
+                         % (name, tuple(a.shape), a.device, tuple(b.shape), b.device))
+    chunk_rows = int(chunk_rows or retrieval.GALLERY_CHUNK_ROWS)
+    query_block = int(query_block or retrieval.QUERY_BLOCK)
+    if chunk_rows < 1 or query_block < 1:
+        raise ValueError("%s: chunk_rows and query_block must be >= 1" % name)
+    return a, b, chunk_rows, query_block
+
+
+def _pair_scratch(a, b, chunk_rows, query_block):
+    need = min(max(a.shape[0], b.shape[0]), query_block) * min(max(a.shape[0], b.shape[0]), chunk_rows)
+    return torch.empty(need, dtype=torch.float32, device=a.device)
+
+
+def _kernel_sums(queries, chunks, own, inv_d, query_block, scratch):
+    """fp64 [Q] on the device: for every query row the sum of the cubic kernel against every row of `chunks`; own=True:
+    the chunks hold the queries themselves, and a row's kernel with itself is left out."""
+    sums = torch.zeros(queries.shape[0], dtype=torch.float64, device=queries.device)
+    for q0, q1, start, sc in _pair_blocks(queries, chunks, query_block, scratch):
+        ops.polykernel_rows(sc, inv_d, sums[q0:q1], base=start, own_base=q0 if own else None)
+    return sums
+
+
+def _norm2(rows, block):
+    """fp32 [n]: the squared norm of every row, formed in fp64 on the device, `block` rows at a time."""
+    out = torch.empty(rows.shape[0], dtype=torch.float32, device=rows.device)
+    for s in range(0, rows.shape[0], block):
+        out[s:s + block] = rows[s:s + block].double().square_().sum(dim=1)
+    return out
+
+
+def _radii(queries, chunks, norms, k, query_block, scratch):
+    """fp32 [n]: -r^2 of every row of a set, the k-th largest negated squared distance to another row of it (the chunks
+    hold the queries themselves)."""
+    Q, dev = queries.shape[0], queries.device
+    best = (torch.empty((Q, k), dtype=torch.float32, device=dev), torch.empty((Q, k), dtype=torch.int32, device=dev))
+    for q0, q1, start, sc in _pair_blocks(queries, chunks, query_block, scratch):
+        ops.sqdist_rows(sc, norms[q0:q1], norms, base=start, own_base=q0)
+        pair = (best[0][q0:q1], best[1][q0:q1])
+        if start == 0:
+            ops.topk_rows(sc, k, base=start, out=pair)
+        else:
+            ops.topk_rows(sc, k, base=start, best=pair)
+    return best[0][:, k - 1].contiguous()
+
+
+def _balls(queries, q_norms, chunks, norms, bound, query_block, scratch):
+    """(count int32 [Q], best fp32 [Q]): how many balls of the other set (-r^2 in `bound`) hold each query, and minus its
+    squared distance to the nearest row of that set."""
+    Q, dev = queries.shape[0], queries.device
+    count = torch.zeros(Q, dtype=torch.int32, device=dev)
+    best = torch.full((Q,), float("-inf"), dtype=torch.float32, device=dev)
+    for q0, q1, start, sc in _pair_blocks(queries, chunks, query_block, scratch):
+        ops.sqdist_rows(sc, q_norms[q0:q1], norms, base=start)
+        ops.ball_rows(sc, bound, base=start, count=count[q0:q1], best=best[q0:q1])
+    return count, best
+
+
+def kid(x_rows, y_rows, chunk_rows=None, query_block=None):
+    """The kernel inception distance (Binkowski et al. 2018) of two sets of feature rows as a float64: the unbiased
+    estimator of MMD^2 with the kernel k(a, b) = (a . b / D + 1)^3,
+
+        Sxx / (m (m - 1)) + Syy / (n (n - 1)) - 2 Sxy / (m n),
+
+    Sxx and Syy the sums of k over the ordered pairs of DIFFERENT rows of one set, Sxy over all pairs across the sets.
+    x_rows [m, D] and y_rows [n, D]: FeatureRows or fp32 device tensors, m, n >= 2.
+
+    This is the estimator over the full samples: no subsets are drawn, so there is no seed.  It has the same expectation
+    as the usual protocol that averages the estimator over random subsets, with lower variance (every pair is used);
+    that protocol's standard deviation over subsets is not produced.
+
+    Every (query_block, chunk_rows) block of scores comes from one launch of the fp32 matrix kernel and is folded by
+    s2i_polykernel_rows into per-query fp64 sums, which are copied to the host (m or n doubles per pass) and added there
+    in float64; no [m, n] matrix exists.  There is no CPU fallback."""
+    from . import retrieval
+    x, y, chunk_rows, query_block = _pair_args("kid", x_rows, y_rows, chunk_rows, query_block)
+    m, n, D = x.shape[0], y.shape[0], x.shape[1]
+    if m < 2 or n < 2:
+        raise ValueError("kid: each set needs at least 2 rows, have %d and %d" % (m, n))
+    inv_d = 1.0 / D
+    with torch.cuda.device(x.device):
+        xq, xc = retrieval.pack_device_rows(x, chunk_rows)
+        yq, yc = retrieval.pack_device_rows(y, chunk_rows)
+        scratch = _pair_scratch(x, y, chunk_rows, query_block)
+        sxx, syy, sxy = (math.fsum(_kernel_sums(q, c, own, inv_d, query_block, scratch).cpu().tolist())
+                         for q, c, own in ((xq, xc, True), (yq, yc, True), (xq, yc, False)))
+    return sxx / (m * (m - 1.0)) + syy / (n * (n - 1.0)) - 2.0 * sxy / (float(m) * n)     # Python floats: float64
+
+
+def prdc(real_rows, fake_rows, nearest_k=5, chunk_rows=None, query_block=None):
+    """Precision and recall (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020) of fake feature rows
+    against real ones, from k-nearest-neighbour balls: r_i is the distance from row i to its nearest_k-th nearest OTHER
+    row of its own set.  With N real and M fake rows,
+
+        precision  the share of fake rows that lie in the ball of at least one real row,
+        density    the number of real balls that hold a fake row, summed over the fake rows, over nearest_k M,
+        recall     the share of real rows that lie in the ball of at least one fake row,
+        coverage   the share of real rows whose nearest fake row lies inside their own ball,
+
+    a row on the surface of a ball counting as inside.  One nearest_k serves all four, as in the `prdc` reference
+    implementation (default 5; 3 is Kynkaanniemi's setting); 1 <= nearest_k <= 64 and each set holds more rows than that.
+    real_rows [N, D] and fake_rows [M, D]: FeatureRows or fp32 device tensors.
+
+    Four passes over (query_block, chunk_rows) blocks of scores from the fp32 matrix kernel, each block rewritten in
+    place to negated squared distances (s2i_sqdist_rows, |a|^2 + |b|^2 - 2 a.b in fp32, the squared norms formed in fp64
+    on the device and stored as fp32): real against real and fake against fake are folded by s2i_topk_rows into the k
+    nearest other rows (the radii), fake against real and real against fake by s2i_ball_rows into counts and the nearest
+    distance.  Nothing of size N x M exists beyond one block.
+
+    Returns the four values as floats with `nearest_k`, and the per-query device tensors they come from:
+    real_bound [N], fake_bound [M] fp32 (-r_i^2), fake_count [M] int32 and fake_best [M] fp32 (the real balls that hold
+    each fake row; minus its squared distance to the nearest real row), real_count [N] and real_best [N] (the same for
+    each real row among the fake ones).  There is no CPU fallback."""
+    from . import retrieval
+    real, fake, chunk_rows, query_block = _pair_args("prdc", real_rows, fake_rows, chunk_rows, query_block)
+    k = int(nearest_k)
+    if not 1 <= k <= _lib.TOPK_MAX:
+        raise ValueError("prdc: nearest_k must lie in 1..%d, got %d" % (_lib.TOPK_MAX, k))
+    N, M = real.shape[0], fake.shape[0]
+    if N <= k or M <= k:
+        raise ValueError("prdc: each set must hold more than nearest_k = %d rows, have %d real and %d fake" % (k, N, M))
+    dev = real.device
+    with torch.cuda.device(dev):
+        rq, rc = retrieval.pack_device_rows(real, chunk_rows)
+        fq, fc = retrieval.pack_device_rows(fake, chunk_rows)
+        scratch = _pair_scratch(real, fake, chunk_rows, query_block)
+
+        rn, fn = _norm2(real, query_block), _norm2(fake, query_block)
+        real_bound = _radii(rq, rc, rn, k, query_block, scratch)
+        fake_bound = _radii(fq, fc, fn, k, query_block, scratch)
+        fake_count, fake_best = _balls(fq, fn, rc, rn, real_bound, query_block, scratch)
+        real_count, real_best = _balls(rq, rn, fc, fn, fake_bound, query_block, scratch)
+        hit_f = int((fake_count > 0).sum().item())
+        tot_f = int(fake_count.sum(dtype=torch.int64).item())
+        hit_r = int((real_count > 0).sum().item())
+        cov_r = int((real_best >= real_bound).sum().item())
+    return dict(precision=hit_f / float(M), recall=hit_r / float(N), density=tot_f / (float(k) * M), coverage=cov_r / float(N),
+                nearest_k=k, real_bound=real_bound, fake_bound=fake_bound, fake_count=fake_count, fake_best=fake_best,
+                real_count=real_count, real_best=real_best)
+
+
+_kid, _prdc = kid, prdc      # GeneratorScorer.result has flags of these names
+PRDC_KEYS = ("precision", "recall", "density", "coverage", "nearest_k")
+
+
 class GeneratorScorer:
     """IS / NLPP over the fake softmax rows (kept on the device in arrival order, in a buffer preallocated for n_fake_max
     rows that grows if more arrive) and FID between the streamed fake and real pool3 moments.  `inception` is a
-    model.INCEPTION_V3 with weights or an inception.InceptionNet."""
+    model.INCEPTION_V3 with weights or an inception.InceptionNet.  keep_rows=True also keeps every pool3 row on the
+    device (two FeatureRows, 8 KB a row), which `result(kid=True)` and `result(prdc=True)` need; it changes nothing
+    else."""
 
-    def __init__(self, inception, n_fake_max, device=None):
+    def __init__(self, inception, n_fake_max, device=None, keep_rows=False):
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.net = inception.net(self.device) if hasattr(inception, "net") else inception
         self.soft = torch.empty(max(1, int(n_fake_max)), CLASSES, device=self.device)
@@ -132,6 +340,8 @@ class GeneratorScorer:
         self.fake = FeatureMoments(POOL3, self.device)
         self.real = FeatureMoments(POOL3, self.device)
         self._pool3 = self._soft_real = None
+        self.fake_rows = FeatureRows(POOL3, self.device, n_fake_max) if keep_rows else None
+        self.real_rows = FeatureRows(POOL3, self.device) if keep_rows else None
 
     def _scratch(self, n):
         if self._pool3 is None or self._pool3.shape[0] < n:
@@ -154,6 +364,8 @@ class GeneratorScorer:
         pool3 = self._scratch(n)
         self.net.run(imgs, self.soft[self.n_fake:self.n_fake + n], pool3)
         self.fake.update(pool3)
+        if self.fake_rows is not None:
+            self.fake_rows.append(pool3)
         self.n_fake += n
 
     def add_real(self, images):
@@ -161,21 +373,38 @@ class GeneratorScorer:
         pool3 = self._scratch(n)
         self.net.run(imgs, self._soft_real[:n], pool3)
         self.real.update(pool3)
+        if self.real_rows is not None:
+            self.real_rows.append(pool3)
 
     def fake_predictions(self):
         return self.soft[:self.n_fake].cpu().double().numpy()
 
-    def result(self, num_splits=10, real_stats=None):
+    def result(self, num_splits=10, real_stats=None, kid=False, prdc=False, nearest_k=5):
         """{is_mean, is_std, nlpp_mean, nlpp_std, fid, n_fake, n_real} plus the fitted 'fake_stats' / 'real_stats'
-        (mu, sigma, n).  real_stats, if given, replaces the streamed real moments."""
+        (mu, sigma, n).  real_stats, if given, replaces the streamed real moments.  kid=True adds `kid` (the module's
+        kid of the kept fake rows against the kept real rows), prdc=True adds `precision`, `recall`, `density`,
+        `coverage` and `nearest_k`; both need keep_rows=True and real rows that were scored here.  The real set has one
+        row per item and the fake set one per sentence: recall and coverage see that many fakes per real image."""
+        if kid or prdc:
+            if self.fake_rows is None:
+                raise ValueError("GeneratorScorer: kid and prdc need the pool3 rows: construct with keep_rows=True")
+            if len(self.real_rows) == 0:
+                raise ValueError("GeneratorScorer: kid and prdc need the real rows, and no real image was scored "
+                                 "(precomputed real_stats hold moments, not rows)")
         pred = self.fake_predictions()
         is_mean, is_std = compute_inception_score(pred, num_splits)
         nlpp_mean, nlpp_std = negative_log_posterior_probability(pred, num_splits)
         fake = self.fake.mean_cov()
         real = real_stats if real_stats is not None else self.real.mean_cov()
         fid = frechet_distance(fake[0], fake[1], real[0], real[1])
-        return dict(is_mean=float(is_mean), is_std=float(is_std), nlpp_mean=float(nlpp_mean), nlpp_std=float(nlpp_std),
-                    fid=fid, n_fake=int(fake[2]), n_real=int(real[2]), fake_stats=fake, real_stats=real)
+        out = dict(is_mean=float(is_mean), is_std=float(is_std), nlpp_mean=float(nlpp_mean), nlpp_std=float(nlpp_std),
+                   fid=fid, n_fake=int(fake[2]), n_real=int(real[2]), fake_stats=fake, real_stats=real)
+        if kid:
+            out["kid"] = _kid(self.fake_rows, self.real_rows)
+        if prdc:
+            res = _prdc(self.real_rows, self.fake_rows, nearest_k)
+            out.update((key, res[key]) for key in PRDC_KEYS)
+        return out
 
 
 class ConsistencyScorer:
@@ -389,10 +618,27 @@ def parse_args(argv=None):
                         "real_* recall@k, median rank, R-precision) to the record; the embeddings must be 1024 wide")
     p.add_argument("--consistency_cosine", action="store_true", default=False,
                    help="rank by cosine similarity instead of the dot product")
+    p.add_argument("--kid", action="store_true", default=False,
+                   help="add `kid`: the unbiased cubic-kernel MMD^2 of the fake against the real pool3 rows (full samples)")
+    p.add_argument("--prdc", action="store_true", default=False,
+                   help="add `precision`, `recall`, `density`, `coverage`: k-nearest-neighbour manifolds of the pool3 rows")
+    p.add_argument("--nearest_k", type=int, default=None, metavar="K",
+                   help="the k of --prdc, 1..64 (default 5; 3 is Kynkaanniemi's setting); implies --prdc")
     args = p.parse_args(argv)
     if args.max_items is not None and args.max_items < 1:
         p.error("--max_items must be >= 1")
     args.real_stats_mode = None if not args.real_stats else ("read" if os.path.isfile(args.real_stats) else "write")
+    if args.nearest_k is not None:
+        if not 1 <= args.nearest_k <= _lib.TOPK_MAX:
+            p.error("--nearest_k must lie in 1..%d" % _lib.TOPK_MAX)
+        args.prdc = True
+    else:
+        args.nearest_k = 5
+    args.keep_rows = args.kid or args.prdc
+    if args.keep_rows and args.real_stats_mode == "read":
+        p.error("--kid, --prdc and --nearest_k compare pool3 rows, and with --real_stats %s, which exists, the real "
+                "images are not scored, so there are no real rows: drop --real_stats or name a file to be written"
+                % args.real_stats)
     return args
 
 
@@ -423,7 +669,7 @@ def main(argv=None):
                              workers=cfg.WORKERS if args.workers is None else args.workers)
     n_items = len(dataset) if args.max_items is None else min(len(dataset), args.max_items)
     n_sent = dataset.embedding.shape[1]
-    scorer = GeneratorScorer(INCEPTION_V3(args.inception), n_items * n_sent, dev)
+    scorer = GeneratorScorer(INCEPTION_V3(args.inception), n_items * n_sent, dev, keep_rows=args.keep_rows)
     netG = load_generator(args.netG, dev)
     consistency = None
     if args.googlenet:
@@ -434,7 +680,7 @@ def main(argv=None):
                                         labels[:n_items], dev, cosine=args.consistency_cosine)
     score_generator(netG, loader, scorer, args.seed, max_items=args.max_items,
                     save_images=_image_dir(args.netG) if args.save_images else None, consistency=consistency)
-    res = scorer.result(10, real_stats)
+    res = scorer.result(10, real_stats, kid=args.kid, prdc=args.prdc, nearest_k=args.nearest_k)
     if consistency is not None:
         res.update(consistency.result(), consistency_score="cosine" if args.consistency_cosine else "dot")
     out_dir = os.path.dirname(os.path.abspath(args.out))
@@ -449,9 +695,14 @@ def main(argv=None):
     with open(args.out, "w") as f:
         json.dump(rec, f)
         f.write("\n")
-    print("IS %.4f +- %.4f, NLPP %.4f +- %.4f, FID %.4f (%d fake, %d real)"
-          % (res["is_mean"], res["is_std"], res["nlpp_mean"], res["nlpp_std"], res["fid"], res["n_fake"],
-             res["n_real"]))
+    line = ("IS %.4f +- %.4f, NLPP %.4f +- %.4f, FID %.4f (%d fake, %d real)"
+            % (res["is_mean"], res["is_std"], res["nlpp_mean"], res["nlpp_std"], res["fid"], res["n_fake"], res["n_real"]))
+    if args.kid:
+        line += ", KID %.6f" % res["kid"]
+    if args.prdc:
+        line += (", precision %.4f, recall %.4f, density %.4f, coverage %.4f (k %d)"
+                 % (res["precision"], res["recall"], res["density"], res["coverage"], res["nearest_k"]))
+    print(line)
     return rec
 
 

@@ -20,6 +20,7 @@ Activations between these ops are NHWC; parameters stay in the reference's OIHW 
 re-packed to the kernels' layout when their version counter changes.  There is no CPU fallback.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -2096,3 +2097,94 @@ def rank_rows(scores, own_row, query_label, row_label, base, own_score, gt, eq, 
     check(lib.s2i_rank_rows(ptr(scores.detach()), Q, N, scores.stride(0), base, ptr(own_row), ptr(query_label),
                             ptr(row_label), n_labels, ptr(own_score), ptr(gt), ptr(eq),
                             _lib.RANK_GATHER if mode == "gather" else _lib.RANK_COUNT, stream()), "s2i_rank_rows")
+
+
+# ---- kernel distance and nearest-neighbour manifolds (s2i_manifold.hip) ---------------------------------------------------
+def _block(name, scores, base):
+    """(Q, N, device) of one [Q, N] block of scores, checked as topk_rows and rank_rows check theirs."""
+    if not torch.is_tensor(scores) or scores.dim() != 2 or scores.dtype != torch.float32:
+        raise ValueError("%s: scores must be an fp32 [Q, N] tensor" % name)
+    Q, N = scores.shape
+    if Q < 1 or N < 1 or scores.stride(1) != 1 or scores.stride(0) < N:
+        raise ValueError("%s: scores %s with strides %s: need Q, N >= 1, unit column stride and row stride >= N"
+                         % (name, tuple(scores.shape), tuple(scores.stride())))
+    if base < 0 or base + N > 2 ** 31 - 1:
+        raise ValueError("%s: row ids %d .. %d leave int32" % (name, base, base + N - 1))
+    if not scores.is_cuda:
+        raise _lib.S2IError("%s runs on the MI355X kernel: there is no CPU fallback (scores on %s)" % (name, scores.device))
+    return Q, N, scores.device
+
+
+def _block_vector(name, what, t, dtype, n, device):
+    if (not torch.is_tensor(t) or t.dtype != dtype or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous()
+            or t.device != device):
+        raise ValueError("%s: %s must be a contiguous %s vector of %d entries on %s"
+                         % (name, what, str(dtype).replace("torch.", ""), n, device))
+
+
+def _own_base(name, own_base):
+    own_base = -1 if own_base is None else int(own_base)
+    if own_base < -1 or own_base > 2 ** 31 - 1:
+        raise ValueError("%s: own_base must be None / -1 or a row id, got %d" % (name, own_base))
+    return own_base
+
+
+def polykernel_rows(scores, inv_d, sums, base=0, own_base=None):
+    """sums[q] += sum_j (scores[q][j] * inv_d + 1)^3 over one [Q, N] block of scores (fp32, unit column stride, any row
+    stride >= N; column j is row base + j of the other set), evaluated and added in fp64 in a fixed order
+    (s2i_polykernel_rows).  own_base: query q is row own_base + q of the other set and that column is left out (the
+    off-diagonal sum of a set against itself); None leaves nothing out.  sums: fp64 [Q] on the scores' device,
+    accumulated in place (the caller zeroes it).  No autograd."""
+    base, inv_d = int(base), float(inv_d)
+    own_base = _own_base("polykernel_rows", own_base)
+    if not math.isfinite(inv_d):
+        raise ValueError("polykernel_rows: inv_d must be finite, got %r" % (inv_d,))
+    Q, N, dev = _block("polykernel_rows", scores, base)
+    _block_vector("polykernel_rows", "sums", sums, torch.float64, Q, dev)
+    check(_lib_ready().s2i_polykernel_rows(ptr(scores.detach()), Q, N, scores.stride(0), base, own_base, inv_d, ptr(sums),
+                                           stream()), "s2i_polykernel_rows")
+    return sums
+
+
+def sqdist_rows(scores, q_norm2, row_norm2, base=0, own_base=None):
+    """Rewrites one [Q, N] block of scores IN PLACE to minus the squared distance, -max(0, (q_norm2[q] + row_norm2[base + j])
+    - 2 scores[q][j]) in fp32 as written (s2i_sqdist_rows); a NaN stays one; the own row (base + j == own_base + q) becomes
+    -inf, so topk_rows on the result gives the nearest OTHER rows.  q_norm2: fp32 [Q]; row_norm2: fp32 over the whole
+    other set, indexed by global row.  Returns scores.  No autograd."""
+    base = int(base)
+    Q, N, dev = _block("sqdist_rows", scores, base)
+    own_base = _own_base("sqdist_rows", own_base)
+    _block_vector("sqdist_rows", "q_norm2", q_norm2, torch.float32, Q, dev)
+    if not torch.is_tensor(row_norm2) or row_norm2.dim() != 1:
+        raise ValueError("sqdist_rows: row_norm2 must be an fp32 vector over the other set's rows")
+    n_rows = row_norm2.shape[0]
+    _block_vector("sqdist_rows", "row_norm2", row_norm2, torch.float32, n_rows, dev)
+    if base + N > n_rows:
+        raise ValueError("sqdist_rows: rows %d .. %d pass the %d row norms" % (base, base + N - 1, n_rows))
+    check(_lib_ready().s2i_sqdist_rows(ptr(scores.detach()), Q, N, scores.stride(0), base, own_base, ptr(q_norm2),
+                                       ptr(row_norm2), n_rows, stream()), "s2i_sqdist_rows")
+    return scores
+
+
+def ball_rows(nd, row_bound, base=0, count=None, best=None):
+    """One [Q, N] block of negated squared distances (sqdist_rows) folded into count[q] += #{j : nd[q][j] >=
+    row_bound[base + j]} (int32 [Q]) and best[q] = max(best[q], max_j nd[q][j]) (fp32 [Q]); either may be None
+    (s2i_ball_rows).  row_bound: fp32 over the whole other set, -radius^2 of every row's ball.  NaN entries and NaN bounds
+    count nothing.  The caller zeroes count and fills best with -inf.  Only comparisons: exact.  No autograd."""
+    base = int(base)
+    Q, N, dev = _block("ball_rows", nd, base)
+    if count is None and best is None:
+        raise ValueError("ball_rows: give count, best or both")
+    if count is not None:
+        _block_vector("ball_rows", "count", count, torch.int32, Q, dev)
+    if best is not None:
+        _block_vector("ball_rows", "best", best, torch.float32, Q, dev)
+    if not torch.is_tensor(row_bound) or row_bound.dim() != 1:
+        raise ValueError("ball_rows: row_bound must be an fp32 vector over the other set's rows")
+    n_rows = row_bound.shape[0]
+    _block_vector("ball_rows", "row_bound", row_bound, torch.float32, n_rows, dev)
+    if base + N > n_rows:
+        raise ValueError("ball_rows: rows %d .. %d pass the %d row bounds" % (base, base + N - 1, n_rows))
+    check(_lib_ready().s2i_ball_rows(ptr(nd.detach()), Q, N, nd.stride(0), base, ptr(row_bound), n_rows, ptr(count),
+                                     ptr(best), stream()), "s2i_ball_rows")
+    return count, best

@@ -238,6 +238,36 @@ class Gallery:
         return gt, eq
 
 
+def pack_device_rows(rows, chunk_rows=GALLERY_CHUNK_ROWS):
+    """(padded, chunks): fp32 rows [R, C] that are ALREADY on the device, as the matrix kernel takes them on either side.
+    `padded` is the rows as queries ([R, cpad] contiguous, C rounded up to a multiple of 4 with zeros; `rows` itself where
+    nothing had to change), `chunks` the list of (start, n, packed) that Gallery keeps, every chunk packed on the device
+    (ops.pack_weight, PACK_PLAIN).  No host round trip.  There is no CPU fallback."""
+    import torch
+    from . import _lib, ops
+    if not torch.is_tensor(rows) or rows.dim() != 2 or rows.dtype != torch.float32 or rows.shape[0] < 1 or rows.shape[1] < 1:
+        raise ValueError("pack_device_rows: rows must be an fp32 [R >= 1, C >= 1] tensor")
+    if not rows.is_cuda:
+        raise _lib.S2IError("rows are packed for and scored by the MI355X kernels: there is no CPU fallback (rows on %s)"
+                            % rows.device)
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < 1:
+        raise ValueError("pack_device_rows: chunk_rows must be >= 1")
+    R, C = rows.shape
+    cpad = (C + 3) & ~3
+    if chunk_rows * cpad * 4 >= 0x7ff00000:
+        raise ValueError("pack_device_rows: a chunk of %d rows of %d floats exceeds the matrix kernel's 2 GiB operand window"
+                         % (chunk_rows, cpad))
+    with torch.cuda.device(rows.device):
+        padded = rows.detach()
+        if cpad != C:
+            padded = torch.nn.functional.pad(padded, (0, cpad - C))
+        padded = padded.contiguous()
+        chunks = [(s, min(chunk_rows, R - s), ops.pack_weight(padded[s:s + chunk_rows], ops.PACK_PLAIN))
+                  for s in range(0, R, chunk_rows)]
+    return padded, chunks
+
+
 def rank_metrics(gt, eq, n_candidates, m=99, ks=(1, 5, 10)):
     """The retrieval scores of Gallery.rank's counters, on the host in float64.
 
