@@ -156,7 +156,8 @@ def refresh_packed(params):
     if not entries:
         return
     lib = _lib_ready()
-    key = tuple((p.data_ptr(), mode, out.data_ptr()) for p, mode, out in entries)
+    # the shape belongs to the key: the allocator hands the addresses of a dead network to the next one
+    key = tuple((p.data_ptr(), p.shape, mode, out.data_ptr()) for p, mode, out in entries)
     tab = _pack_tables.get(key)
     if tab is None:
         items = (_lib.PackItem * len(entries))()
@@ -201,7 +202,7 @@ def _refresh_bf16(packed_list):
     if not recs:
         return
     lib = _lib_ready()
-    tkey = tuple((packed.data_ptr(), key, ent.data_ptr()) for packed, key, _, _, ent in recs)
+    tkey = tuple((packed.data_ptr(), packed.shape, key, ent.data_ptr()) for packed, key, _, _, ent in recs)
     tab = _pack16_tables.get(tkey)
     if tab is None:
         items = (_lib.Pack16Item * len(recs))()

@@ -83,6 +83,8 @@ GAMMA = {
 
 
 def is_matrix(name):
+    """Entry points the non-matrix replay sets aside.  The s2i_pack* launches among them are held, bit for bit, by
+    tests/test_weight_pack_gpu.py."""
     return (name.startswith("s2i_conv_") or name.startswith("s2i_pack") or name == "s2i_split_packed_weight"
             or "workspace_bytes" in name or name.endswith("_eligible") or "_stat_parts" in name or "_weight_" in name
             or name in ("s2i_check_device", "s2i_last_error"))
