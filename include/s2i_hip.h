@@ -447,6 +447,45 @@ int s2i_specaug(const float* x, const int* valid, int B, int T, float* y, int fr
                 int time_width, float time_ratio, unsigned long long seed, unsigned long long step, void* ws,
                 size_t ws_bytes, void* stream);
 
+/* ---- additive white noise and babble on a batch of waveforms, in place (csrc/s2i_waveaug.hip) ----------------------------
+   x: the flat fp32 batch that s2i_pcm_resample wrote, 16-byte aligned; clip b is x[offsets[b] .. offsets[b] + n), offsets
+   DEVICE int64 [B] in floats, n = lens[b] (DEVICE int32 [B], clamped to [0, max_len]).  max_len is the host's bound on the
+   lens, in [1, 2^31 - 5]: a sample number i stays under 2^31 - 4.  pool: the fp32 samples an interferer is read from,
+   16-byte aligned, never written and disjoint from x; NULL turns babble off for every clip.  table: DEVICE, 32 bytes per
+   clip, 16-byte aligned:
+     float g_white; float g_babble; long long src; int n_j; int start; unsigned uid; int pad;
+   g_white = 10^(-snr / 10) and g_babble = 10^(-snr / 10) / Q_j (Q_j the interferer's mean square), computed in float64 by
+   the host and rounded to fp32 once; 0 switches the term off.  The interferer is pool[src .. src + n_j), n_j >= 1, read
+   cyclically from `start` in [0, n_j); uid is the clip's id in the noise counter.
+   power:  P_b = S_b / (float)n (a correctly rounded division), S_b the fp32 sum of the n squares x_i x_i (each square
+           rounded, then added) in a fixed order without atomics.  The clip is cut into runs of 8192 samples = 2048
+           four-sample pieces, counted from its first sample; thread j of a run's 256 adds pieces j, j + 256, ..., j + 1792
+           in that order, sample c of a piece into lane c of a four-lane accumulator that starts at 0 (a sample at or past
+           n adds nothing); the lanes fold (a0 + a1) + (a2 + a3); a wave's 64 lanes by an xor butterfly (offsets 32 .. 1);
+           the four waves ((w0 + w1) + w2) + w3.  The ceil(n / 8192) run sums are added by 64 lanes, lane l taking runs l,
+           l + 64, ... in that order from 0, then the same butterfly.  The zero tail s2i_pcm_resample writes is part of the
+           n samples.  The same clip gives the same bits in any batch, at any offset and for any max_len.
+   white:  a_w = sqrtf(P_b g_white) (the product rounded, the root correctly rounded).  Sample i takes the Philox4x32-10
+           block (the rounds of s2i_specaug) with key (seed mod 2^32, (seed div 2^32) ^ 0x57415645) and counter
+           (step mod 2^32, step div 2^32, uid, 2 + i div 2): words (r0, r1) for an even i, (r2, r3) for an odd one.  h = the
+           sum of the four 16-bit halves of the two words, in [0, 262140]; e_i = ((float)h - 131070.0f) c with
+           c = 0x1.bb67aep-16f, 1 / sqrt((2^32 - 1) / 3) rounded to fp32: the sum of four uniform 16-bit integers, centred
+           and scaled to unit variance (Irwin-Hall; |e_i| <= 3.4641).  The key differs from s2i_specaug's in word 1 for
+           every seed, so the two never share a block; counters 0 and 1 of a uid are the host's draws.
+   babble: a_b = sqrtf(P_b g_babble);  v_i = pool[src + (start + i) mod n_j].
+   result: y_i = (x_i + a_w e_i) + a_b v_i, every product and every sum rounded to fp32 on its own, in that order (a term
+           that is off is not added).  P_b == 0, or both gains 0, leaves the clip unwritten; samples outside the clips are
+           never written.
+   Two launches on `stream` with no host round trip: the run sums into the caller's workspace of
+   s2i_wave_mix_workspace_bytes(B, max_len) = 4 B ceil(max_len / 8192) bytes, then the mix, four pieces per thread, in
+   16-byte accesses where the clip starts on a 16-byte boundary and sample by sample elsewhere (the same sums either way).
+   Bad arguments (a null x, offsets, lens, table or workspace, B < 1, max_len outside its range, a misaligned buffer, a
+   workspace too small) return non-zero before any launch; s2i_wave_mix_workspace_bytes returns 0 for them. */
+size_t s2i_wave_mix_workspace_bytes(int B, int max_len);
+int s2i_wave_mix(float* x, const long long* offsets, const int* lens, int B, int max_len, const float* pool,
+                 const void* table, unsigned long long seed, unsigned long long step, void* ws, size_t ws_bytes,
+                 void* stream);
+
 /* ---- CA_NET reparameterisation + KL (model.py:182-200, trainer.py:54-58) -------------------- */
 /* h = GLU output [B][2E] = [mu | logvar];  c = eps*exp(0.5*logvar) + mu */
 int s2i_reparam_forward(const float* h, const float* eps, int B, int E, float* c, void* stream);

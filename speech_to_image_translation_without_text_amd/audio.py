@@ -448,16 +448,26 @@ def prepare_batch(sigs, T, dev):
     """device buffers of one ragged batch of non-empty fp32 device signals: the flat samples, int64 offsets, int32
     lengths, the tile table (one (b, first frame) entry per 64 frames) and the kernels' workspace"""
     lens = np.array([s.numel() for s in sigs], dtype=np.int64)
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    return prepare_flat(torch.cat(sigs), offsets, lens, T, dev)
+
+
+def prepare_flat(flat, offsets, lens, T, dev):
+    """prepare_batch's buffers over clips that already lie in one flat fp32 device tensor: clip b is
+    flat[offsets[b] : offsets[b] + lens[b]], lens[b] >= 1 (host arrays; the clips need not be back to back)"""
+    lens = np.asarray(lens, dtype=np.int64)
+    offsets = np.asarray(offsets, dtype=np.int64)
     if lens.max() >= 2 ** 31 - 2 * N_FFT:
         raise ValueError("log_mel: a clip of %d samples is too long" % lens.max())
-    B = len(sigs)
+    if len(offsets) != len(lens) or lens.min() < 1 or offsets.min() < 0 or int((offsets + lens).max()) > flat.numel():
+        raise ValueError("log_mel: a clip is empty or lies outside the flat buffer of %d samples" % flat.numel())
+    B = len(lens)
     nf = 1 + lens // HOP
     ntile = (nf + LOGMEL_TILE_FRAMES - 1) // LOGMEL_TILE_FRAMES
     tiles = np.empty((int(ntile.sum()), 2), dtype=np.int32)
     tiles[:, 0] = np.repeat(np.arange(B), ntile)
     tiles[:, 1] = (np.arange(len(tiles)) - np.repeat(np.cumsum(ntile) - ntile, ntile)) * LOGMEL_TILE_FRAMES
-    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-    return dict(x=torch.cat(sigs), lens=lens, T=T, ntiles=len(tiles), offsets_d=torch.from_numpy(offsets).to(dev),
+    return dict(x=flat, lens=lens, T=T, ntiles=len(tiles), offsets_d=torch.from_numpy(offsets).to(dev),
                 lens_d=torch.from_numpy(lens.astype(np.int32)).to(dev), tiles_d=torch.from_numpy(tiles).to(dev),
                 mean=torch.empty(B, dtype=torch.float32, device=dev),
                 maxbits=torch.empty(B, dtype=torch.int32, device=dev),

@@ -15,6 +15,12 @@ shortest item's data and length by the second-shortest's when it has fewer than 
 cap_lens = n_frames // 64 and restores the order.  The encoder treats every item on its own, so here the chunk rule is
 applied to the lengths first (`chunk_sources`) and any number of files runs as one GPU batch: log-mel (audio.log_mel,
 NHWC) straight into CNNRNN.forward_nhwc.
+
+--waveaug 'speed=1.1,white=1@20:20' --waveaug_seed S writes the embeddings of perturbed audio instead (ops.waveaug_policy,
+wave_loader.perturb): every file at a drawn speed and under white noise at a drawn signal-to-noise ratio, the draws a
+function of (S, 0, the file's running number in its split) alone, so a run repeats bit for bit.  The `retrieval` CLI over
+such files measures how accuracy, AP@50 and recall@k fall with noise or tempo.  babble= needs a pool of training
+utterances and is refused here.  Without the flag nothing changes.
 """
 import argparse
 import json
@@ -77,17 +83,28 @@ def read_wavs(paths, workers=MAX_READERS, resample=False):
         return list(pool.map(audio.read_wav, paths))
 
 
-def encode_waveforms(model, waves, batch_size=240, chunk=CHUNK):
+def encode_waveforms(model, waves, batch_size=240, chunk=CHUNK, aug=None):
     """Sentence embeddings (N, D) float32 and n_frames (N,) int64 of the waveforms, equal to the reference's
-    chunk-of-10 processing for any batch_size."""
-    frames = np.array([audio.n_frames(len(w)) for w in waves], dtype=np.int64)
+    chunk-of-10 processing for any batch_size.  `aug` (a wave_loader.WaveAug; None: off) perturbs each waveform first,
+    waveform k drawing with step 0 and uid k: the perturbed lengths, which the chunk rule needs before anything runs,
+    come from the host-side plan, and the perturbed audio of one batch at a time is on the device."""
+    if aug is not None:
+        from . import ops
+        from .wave_loader import perturb
+        plan = ops.waveaug_plan(aug.policy, aug.seed, 0, np.arange(len(waves)), [len(w) for w in waves])
+        frames = np.array([audio.n_frames(n) for n in plan["out_len"]], dtype=np.int64)
+    else:
+        frames = np.array([audio.n_frames(len(w)) for w in waves], dtype=np.int64)
     src = chunk_sources(frames, chunk)
     dev = next(model.parameters()).device
     feats = None
     for s in range(0, len(waves), batch_size):
         items = np.arange(s, min(s + batch_size, len(waves)))
         need = np.unique(src[items])
-        logspec, nf = audio.log_mel([waves[i] for i in need], layout="nhwc", device=dev)
+        clips = [waves[i] for i in need]
+        if aug is not None:
+            clips = perturb(clips, aug, dev, step=0, uids=need)
+        logspec, nf = audio.log_mel(clips, layout="nhwc", device=dev)
         pos = np.searchsorted(need, src[items])
         cap = nf[pos] // MIN_FRAMES
         order = np.argsort(-cap, kind="stable")                  # the encoder takes cap_lens sorted descending
@@ -109,11 +126,12 @@ def split_files(data_dir, split, dataset):
     return [os.path.join(meta["audio_base_path"], name) for d in meta["data"] for name in d[key]]
 
 
-def extract_split(model, data_dir, split, dataset, audio_switch, batch_size=240, resample=False):
+def extract_split(model, data_dir, split, dataset, audio_switch, batch_size=240, resample=False, aug=None):
+    """`aug` (a wave_loader.WaveAug; None: off) perturbs every file first, inside the encode loop."""
     files = split_files(data_dir, split, dataset)
     if not files or len(files) % CHUNK:
         raise ValueError("%s split has %d files: need a positive multiple of %d" % (split, len(files), CHUNK))
-    feats, frames = encode_waveforms(model, read_wavs(files, resample=resample), batch_size)
+    feats, frames = encode_waveforms(model, read_wavs(files, resample=resample), batch_size, aug=aug)
     out_dir = os.path.join(data_dir, split)
     datasets.save_embedding_pickle(feats.reshape(-1, CHUNK, feats.shape[1]),
                                    os.path.join(out_dir, "audio_features_%s.pickle" % audio_switch))
@@ -136,18 +154,39 @@ def get_parser():
     p.add_argument("--resample", action="store_true", default=False,
                    help="accept WAVs of any rate (4-192 kHz), PCM 8/16/24/32-bit or float 32/64-bit, 1-8 channels: "
                         "decoded, mixed down and resampled to 16 kHz on the GPU (audio.to_16k)")
+    p.add_argument("--waveaug", type=str, default="",
+                   help="write the embeddings of perturbed audio, e.g. 'speed=1.1,white=1@20:20' (ops.waveaug_policy; "
+                        "babble= is refused: it needs a pool of training utterances); default '': off")
+    p.add_argument("--waveaug_seed", type=int, default=0, help="seed of --waveaug's draws")
     return p
+
+
+def make_aug(spec, seed):
+    """The WaveAug of --waveaug (None for ''), refused with the reason where the spec is bad or asks for babble."""
+    from . import ops
+    try:
+        if ops.waveaug_policy(spec) is None:
+            return None
+    except ValueError as e:
+        raise SystemExit("--waveaug: %s" % e)
+    from .wave_loader import WaveAug
+    aug = WaveAug(spec, seed)
+    if aug.policy["babble"] is not None:
+        raise SystemExit("--waveaug: babble= draws its interferers from a pool of training utterances, which an extraction "
+                         "does not have: use speed= and white= here")
+    return aug
 
 
 def main(argv=None):
     args = get_parser().parse_args(argv)
     if args.batch_size < 1:
         raise SystemExit("--batch_size must be >= 1")
+    aug = make_aug(args.waveaug, args.waveaug_seed)
     data_dir = args.data_dir or os.path.join(".", "data", args.dataset)
     dev = torch.device("cuda", torch.cuda.current_device())
     model = load_encoder(args.model, args.bidirectional, args.rnn_layers, dev)
     for split in args.splits.split(","):
-        feats, _ = extract_split(model, data_dir, split, args.dataset, args.audio_switch, args.batch_size, args.resample)
+        feats, _ = extract_split(model, data_dir, split, args.dataset, args.audio_switch, args.batch_size, args.resample, aug)
         print("%s: %d utterances -> %s" % (split, len(feats), os.path.join(data_dir, split)))
 
 

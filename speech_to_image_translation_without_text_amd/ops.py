@@ -1986,6 +1986,263 @@ def specaug(mel, valid, policy, seed, step, out=None):
     return out
 
 
+# ---- speed and noise augmentation of waveforms --------------------------------------------------------------------------
+WAVEAUG_KEY_XOR = 0x57415645        # into key word 1: no (key, counter) block is SpecAugment's
+WAVEAUG_MAX_SPEEDS = 8
+WAVEAUG_MIN_FRAMES = 64             # a perturbed clip under this many frames runs at speed 1.0
+WAVE_MIX_MAX_LEN = 2 ** 31 - 5
+WAVE_MIX_RUN = 8192
+# the device table of s2i_wave_mix, 32 bytes per clip (include/s2i_hip.h)
+WAVE_MIX_ENTRY = [("g_white", "<f4"), ("g_babble", "<f4"), ("src", "<i8"), ("n_j", "<i4"), ("start", "<i4"),
+                  ("uid", "<u4"), ("pad", "<i4")]
+
+
+def _waveaug_noise(token, value):
+    prob, sep, span = value.partition("@")
+    lo, sep2, hi = span.partition(":")
+    try:
+        if not sep or not sep2:
+            raise ValueError
+        prob, lo, hi = float(prob), float(lo), float(hi)
+    except ValueError:
+        raise ValueError("bad augmentation %r: expected P@LO:HI, a probability and an SNR range in dB" % token) from None
+    if not 0.0 < prob <= 1.0:       # a NaN fails both
+        raise ValueError("bad augmentation %r: the probability must lie in (0, 1]" % token)
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+        raise ValueError("bad augmentation %r: the SNR range needs finite LO <= HI" % token)
+    return prob, lo, hi
+
+
+def _waveaug_speeds(token, value):
+    from . import audio
+    parts = value.split("/")
+    if not 1 <= len(parts) <= WAVEAUG_MAX_SPEEDS:
+        raise ValueError("bad augmentation %r: 1 to %d speed factors" % (token, WAVEAUG_MAX_SPEEDS))
+    rates = []
+    for part in parts:
+        try:
+            s = float(part)
+        except ValueError:
+            raise ValueError("bad augmentation %r: %r is not a number" % (token, part)) from None
+        if not 0.5 <= s <= 2.0:
+            raise ValueError("bad augmentation %r: a speed factor must lie in [0.5, 2.0]" % token)
+        rate = round(audio.SAMPLE_RATE * s)
+        if abs(audio.SAMPLE_RATE * s - rate) > 1e-6:
+            raise ValueError("bad augmentation %r: %d x %s is not a whole sample rate" % (token, audio.SAMPLE_RATE, part))
+        try:
+            audio.resample_plan(rate)
+        except ValueError as e:
+            raise ValueError("bad augmentation %r: %s" % (token, e)) from None
+        rates.append(int(rate))
+    return tuple(rates)
+
+
+def waveaug_policy(spec):
+    """'speed=0.9/1.0/1.1,white=0.3@5:25,babble=0.2@0:15' (any order, any subset; '' = off -> None) -> a dict
+    {"rates": the sample rates 16000 s a clip is read at, one per speed factor (None without speed=),
+     "white": (P, LO, HI) or None, "babble": (P, LO, HI) or None}.
+    speed= takes 1 to 8 factors in [0.5, 2.0], each of which makes 16000 s a whole rate `audio.resample_plan` accepts; an
+    utterance draws one uniformly.  white= and babble= add noise or another utterance with probability P in (0, 1] at a
+    signal-to-noise ratio drawn uniformly from [LO, HI] dB.  There is no gain key on purpose: power_to_db(ref=max) and
+    the mean subtraction of the log-mel front end make the features invariant to a clip's gain."""
+    values = {"speed": None, "white": None, "babble": None}
+    seen = set()
+    for token in str(spec).split(","):
+        token = token.strip()
+        if not token:
+            continue
+        key, sep, value = token.partition("=")
+        key = key.strip()
+        if not sep or key not in values:
+            raise ValueError("unknown augmentation %r: expected a comma-separated subset of speed=S/S/..., white=P@LO:HI, "
+                             "babble=P@LO:HI" % token)
+        if key in seen:
+            raise ValueError("augmentation %r given twice" % token)
+        seen.add(key)
+        values[key] = _waveaug_speeds(token, value.strip()) if key == "speed" else _waveaug_noise(token, value.strip())
+    if not seen:
+        return None
+    return {"rates": values["speed"], "white": values["white"], "babble": values["babble"]}
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al. 2011; the rounds of include/s2i_hip.h) over numpy arrays of counters and one key:
+    a uint32 array [4, ...] of output words.  Host only; nothing is launched."""
+    import numpy as np
+    m32 = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(v, dtype=np.uint64) & m32 for v in np.broadcast_arrays(c0, c1, c2, c3)]
+    k0, k1 = int(k0) & 0xFFFFFFFF, int(k1) & 0xFFFFFFFF
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> s32) ^ c[1] ^ np.uint64(k0), p1 & m32, (p0 >> s32) ^ c[3] ^ np.uint64(k1), p0 & m32]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return np.stack(c).astype(np.uint32)
+
+
+def waveaug_uniforms(seed, step, uids, group):
+    """float32 [4, n]: u = (r >> 8) 2^-24 of the four words of block `group` of every uid, on key
+    (seed mod 2^32, (seed div 2^32) ^ WAVEAUG_KEY_XOR) and counter (step mod 2^32, step div 2^32, uid, group)."""
+    import numpy as np
+    seed, step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+    uids = np.asarray(uids, dtype=np.uint64).reshape(-1)
+    r = philox4x32_10(step & 0xFFFFFFFF, step >> 32, uids, group, seed & 0xFFFFFFFF, (seed >> 32) ^ WAVEAUG_KEY_XOR)
+    return (r >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
+def _waveaug_index(u, n):
+    """min(int(u (float)n), n - 1): one fp32 product, truncated (SpecAugment's rule), elementwise"""
+    import numpy as np
+    n = np.asarray(n, dtype=np.int64)
+    return np.minimum((u.astype(np.float32) * n.astype(np.float32)).astype(np.int64), n - 1)
+
+
+def waveaug_plan(policy, seed, step, uids, lens, pool_lens=None, pool_q=None, target_length=None):
+    """The per-utterance draws of a batch, a pure function of (seed, step, uid), made on the host.
+
+    `lens`: each clip's 16 kHz samples; `pool_lens` and `pool_q`: the length and the float64 mean square of every stored
+    utterance an interferer may be (needed for babble=).  Block 0 of a uid gives u_speed, u_white (apply if < P),
+    u_white_snr, u_babble (apply if < P); block 1 gives u_babble_snr, u_src and u_start; snr = LO + u (HI - LO) in
+    float64.  The speed index, the interferer j and the start inside it are min(int(u (float)n), n - 1).  A clip whose
+    perturbed length would have under 64 frames runs at 16000 Hz (speed 1.0), whether or not 1.0 is listed.
+
+    Returns a dict of arrays: rate (int64, the rate the clip is read at), out_len (int64), white_snr / babble_snr
+    (float64, NaN where off), g_white / g_babble (float32, 0 where off: 10^(-snr / 10), for babble divided by Q_j; 0 also
+    where Q_j == 0), src and start (int64), uid (uint32)."""
+    import numpy as np
+    from . import audio
+    uids = np.asarray(uids, dtype=np.int64).reshape(-1)
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    if len(uids) != len(lens) or len(uids) < 1 or uids.min() < 0 or uids.max() >= 2 ** 32:
+        raise ValueError("waveaug_plan: need one 32-bit uid per clip, got %d uids for %d clips" % (len(uids), len(lens)))
+    B = len(uids)
+    u0 = waveaug_uniforms(seed, step, uids, 0)
+    u1 = waveaug_uniforms(seed, step, uids, 1)
+    rate = np.full(B, audio.SAMPLE_RATE, dtype=np.int64)
+    if policy["rates"] is not None:
+        rates = np.array(policy["rates"], dtype=np.int64)
+        rate = rates[_waveaug_index(u0[0], np.full(B, len(rates)))]
+    out_len = np.array([audio.resampled_length(n, r) for n, r in zip(lens, rate)], dtype=np.int64)
+    nf = (audio.n_frames if target_length is None else lambda n: audio.n_frames(n, target_length))
+    for b in range(B):
+        if rate[b] != audio.SAMPLE_RATE and nf(out_len[b]) < WAVEAUG_MIN_FRAMES:
+            rate[b], out_len[b] = audio.SAMPLE_RATE, lens[b]
+    plan = dict(rate=rate, out_len=out_len, uid=uids.astype(np.uint32), white_snr=np.full(B, np.nan),
+                babble_snr=np.full(B, np.nan), g_white=np.zeros(B, np.float32), g_babble=np.zeros(B, np.float32),
+                src=np.zeros(B, np.int64), start=np.zeros(B, np.int64))
+    if policy["white"] is not None:
+        p, lo, hi = policy["white"]
+        on = u0[1].astype(np.float64) < p
+        snr = lo + u0[2].astype(np.float64) * (hi - lo)
+        plan["white_snr"] = np.where(on, snr, np.nan)
+        plan["g_white"] = np.where(on, 10.0 ** (-snr / 10.0), 0.0).astype(np.float32)
+    if policy["babble"] is not None:
+        if pool_lens is None or pool_q is None or len(pool_lens) < 1:
+            raise ValueError("waveaug_plan: babble needs a pool of stored utterances to draw interferers from")
+        pool_lens = np.asarray(pool_lens, dtype=np.int64)
+        pool_q = np.asarray(pool_q, dtype=np.float64)
+        if len(pool_lens) >= 2 ** 24 or pool_lens.min() < 1:
+            raise ValueError("waveaug_plan: a pool holds 1 to 2^24 - 1 utterances of at least one sample")
+        p, lo, hi = policy["babble"]
+        on = u0[3].astype(np.float64) < p
+        snr = lo + u1[0].astype(np.float64) * (hi - lo)
+        src = _waveaug_index(u1[1], np.full(B, len(pool_lens)))
+        q = pool_q[src]
+        on_q = on & (q > 0.0)
+        plan["babble_snr"] = np.where(on, snr, np.nan)
+        plan["g_babble"] = np.where(on_q, 10.0 ** (-snr / 10.0) / np.where(q > 0.0, q, 1.0), 0.0).astype(np.float32)
+        plan["src"] = src
+        plan["start"] = _waveaug_index(u1[2], pool_lens[src])
+    return plan
+
+
+def wave_mix_table(plan, pool_offsets=None, pool_lens=None):
+    """The 32-byte-per-clip table of s2i_wave_mix (WAVE_MIX_ENTRY) out of a waveaug_plan: `pool_offsets` and `pool_lens`
+    give each stored utterance's first sample (in floats from the pool's start) and its length."""
+    import numpy as np
+    B = len(plan["uid"])
+    t = np.zeros(B, dtype=WAVE_MIX_ENTRY)
+    t["g_white"], t["g_babble"], t["uid"] = plan["g_white"], plan["g_babble"], plan["uid"]
+    t["n_j"] = 1
+    if pool_offsets is not None:
+        src = plan["src"]
+        t["src"], t["n_j"], t["start"] = np.asarray(pool_offsets)[src], np.asarray(pool_lens)[src], plan["start"]
+    elif np.any(plan["g_babble"] != 0):
+        raise ValueError("wave_mix_table: babble needs the pool's offsets and lengths")
+    return t
+
+
+def wave_mix_prepare(x, offsets, lens, table, pool=None):
+    """The checked and uploaded arguments of one s2i_wave_mix call (include/s2i_hip.h has the definitions), for
+    `wave_mix_launch`: clip b is x[offsets[b] : offsets[b] + lens[b]] of the flat fp32 device tensor `x`; `table` is a
+    numpy array of WAVE_MIX_ENTRY rows (wave_mix_table), `pool` the flat fp32 device tensor the interferers are read from
+    (None: no babble).  offsets, lens and table are HOST arrays: they are checked against x and pool here -- the kernel
+    trusts them -- and go up in one copy.  Nothing is launched."""
+    import numpy as np
+    _lib_ready()
+    if not x.is_cuda:
+        raise _lib.S2IError("wave_mix runs on the MI355X kernel: x is on %s" % x.device)
+    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_contiguous():
+        raise ValueError("wave_mix: x must be a flat contiguous fp32 tensor, got %s %s" % (x.dtype, tuple(x.shape)))
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    lens = np.ascontiguousarray(lens, dtype=np.int64).reshape(-1)
+    table = np.ascontiguousarray(table, dtype=WAVE_MIX_ENTRY).reshape(-1)
+    B = len(offsets)
+    if B < 1 or len(lens) != B or len(table) != B:
+        raise ValueError("wave_mix: offsets, lens and table must have one length >= 1, got %d, %d, %d"
+                         % (B, len(lens), len(table)))
+    if lens.min() < 0 or lens.max() > WAVE_MIX_MAX_LEN or offsets.min() < 0 or int((offsets + lens).max()) > x.numel():
+        raise ValueError("wave_mix: a clip lies outside x (%d floats) or is longer than %d" % (x.numel(), WAVE_MIX_MAX_LEN))
+    order = np.argsort(offsets, kind="stable")
+    if np.any(offsets[order][1:] < (offsets + lens)[order][:-1]):
+        raise ValueError("wave_mix: clips overlap")
+    if not (np.all(np.isfinite(table["g_white"])) and np.all(np.isfinite(table["g_babble"]))
+            and table["g_white"].min() >= 0 and table["g_babble"].min() >= 0):
+        raise ValueError("wave_mix: gains must be finite and >= 0")
+    bab = table["g_babble"] != 0
+    if bab.any():
+        if pool is None:
+            raise ValueError("wave_mix: babble needs a pool")
+        if (pool.dtype != torch.float32 or pool.dim() != 1 or not pool.is_contiguous() or pool.device != x.device
+                or pool.data_ptr() == x.data_ptr()):
+            raise ValueError("wave_mix: pool must be a flat contiguous fp32 tensor on %s, apart from x" % x.device)
+        t = table[bab]
+        if (t["n_j"].min() < 1 or t["src"].min() < 0 or int((t["src"] + t["n_j"]).max()) > pool.numel()
+                or t["start"].min() < 0 or np.any(t["start"] >= t["n_j"])):
+            raise ValueError("wave_mix: an interferer lies outside the pool (%d floats) or its start outside it"
+                             % pool.numel())
+    max_len = max(int(lens.max()), 1)
+    # one upload: offsets | table | lens, each part on a 16-byte boundary
+    at_table = (8 * B + 15) // 16 * 16
+    at_lens = at_table + 32 * B
+    image = np.zeros(at_lens + 4 * B, dtype=np.uint8)
+    image[:8 * B] = offsets.view(np.uint8)
+    image[at_table:at_lens] = table.view(np.uint8)
+    image[at_lens:] = lens.astype(np.int32).view(np.uint8)
+    image_d = torch.from_numpy(image).to(x.device)
+    base = image_d.data_ptr()
+    return dict(x=x, image=image_d, offsets=base, lens=base + at_lens, table=base + at_table, B=B, max_len=max_len,
+                pool=pool if bab.any() else None)
+
+
+def wave_mix_launch(args, seed, step):
+    """s2i_wave_mix on the current stream over `wave_mix_prepare`'s arguments: the two launches and nothing else."""
+    lib = _lib.load()
+    x = args["x"]
+    ws = _ws.get(lib.s2i_wave_mix_workspace_bytes(args["B"], args["max_len"]), x.device)
+    mask64 = (1 << 64) - 1
+    check(lib.s2i_wave_mix(ptr(x), args["offsets"], args["lens"], args["B"], args["max_len"], ptr(args["pool"]), args["table"],
+                           int(seed) & mask64, int(step) & mask64, ptr(ws), ws.numel() * 4, stream()), "s2i_wave_mix")
+    return x
+
+
+def wave_mix(x, offsets, lens, table, seed, step, pool=None):
+    """White noise and babble on a ragged batch of waveforms, in place: `wave_mix_prepare` (checks, one upload) then
+    `wave_mix_launch` (two launches).  y_i = (x_i + a_w e_i) + a_b v_i with the noise a function of (seed, step, uid, i)
+    alone.  No autograd, no CPU fallback.  Returns x."""
+    return wave_mix_launch(wave_mix_prepare(x, offsets, lens, table, pool), seed, step)
+
+
 # ---- nearest-row search -------------------------------------------------------------------------------------------------
 def score_rows(x, packed, n, out):
     """out[:Q * n] viewed [Q, n] = x [Q, Cp] times the first n rows of a gallery chunk packed with

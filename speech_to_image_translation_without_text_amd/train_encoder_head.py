@@ -45,6 +45,16 @@ counter-based generator keyed by --seed (plus the rank under --distributed) and 
 they take nothing from `random`, so the batches drawn are the same with and without the option, and a --state_every state
 continues the mask sequence exactly.  A plain --resume epoch_N.pth restarts the counter at 0.  Evaluation and the
 checkpoints never see a mask.  Default '': off.
+--waveaug 'speed=0.9/1.0/1.1,white=0.3@5:25,babble=0.2@0:15' perturbs every training utterance as a waveform, in front of
+the log-mel front end (wave_loader.py, ops.waveaug_policy): a speed factor drawn from the list, white noise and another
+training utterance (babble) each with its probability at a signal-to-noise ratio drawn from LO:HI dB.  It keeps the
+training split's 16 kHz samples in device memory (wave_loader.ResidentWaveSet; --waveaug_max_bytes refuses a pool above
+it) whether or not --resident is given; the test split stays as it is and is never perturbed.  The draws come from a
+counter-based generator keyed by --waveaug_seed (default --seed; the rank is added to either under --distributed) and counted by the
+trainer's step counter, with the batch position as the utterance's id: they take nothing from `random`, and a
+--state_every state continues the sequence exactly.  A plain --resume epoch_N.pth restarts the counter at 0.  With
+--specaug the waveform is perturbed first and the masks go over its log-mel.  Default '': off, and then nothing of it is
+imported, drawn, launched or allocated.
 """
 import argparse
 import json
@@ -188,6 +198,15 @@ def get_parser(description="fine-tune the speech encoder's LSTM head (conv stack
                    help="SpecAugment of every training batch on the GPU, e.g. 'freq=2x8,time=2x40,ratio=0.2': count x maximum "
                         "width of the frequency and time masks, `ratio` the largest share of an utterance one time mask "
                         "may take (ops.specaug_policy); default '': off")
+    p.add_argument("--waveaug", type=str, default="",
+                   help="speed and noise augmentation of every training utterance's waveform on the GPU, e.g. "
+                        "'speed=0.9/1.0/1.1,white=0.3@5:25,babble=0.2@0:15' (ops.waveaug_policy); keeps the training "
+                        "split's samples in device memory; default '': off")
+    p.add_argument("--waveaug_seed", type=int, default=None,
+                   help="seed of --waveaug's draws (default: --seed); under --distributed the rank is added to it, whether "
+                        "it was given or defaulted, so that the ranks draw independently")
+    p.add_argument("--waveaug_max_bytes", type=int, default=None,
+                   help="refuse a waveform pool above this many bytes (default: no limit)")
     return p
 
 
@@ -200,6 +219,10 @@ def check_args(args):
         ops.specaug_policy(getattr(args, "specaug", ""))
     except ValueError as e:
         raise SystemExit("--specaug: %s" % e)
+    try:
+        ops.waveaug_policy(getattr(args, "waveaug", ""))
+    except ValueError as e:
+        raise SystemExit("--waveaug: %s" % e)
 
 
 def trainer_kwargs(args):
@@ -224,6 +247,23 @@ def make_resident(split, name, dev, workers, say=print, resample=False):
     say("resident %s: %d utterances, %d rows, %d bytes, %.2f s" % (name, len(resident.row_offsets), resident.pool.shape[0],
                                                                   resident.nbytes, time.perf_counter() - t0))
     return resident
+
+
+def make_wave_resident(split, dev, args, rank, say=print):
+    """(the training split behind a wave_loader.ResidentWaveSet, with one line about the pool; the WaveAug of --waveaug).
+    The seed is --waveaug_seed, or --seed where it is not given; under --distributed the rank is added to either."""
+    from .wave_loader import ResidentWaveSet, WaveAug
+    seed = (args.waveaug_seed if args.waveaug_seed is not None else (args.seed or 0)) + (rank if args.distributed else 0)
+    aug = WaveAug(args.waveaug, seed)
+    t0 = time.perf_counter()
+    try:
+        resident = ResidentWaveSet(split, dev, workers=args.resident_workers, resample=args.resample,
+                                   max_bytes=args.waveaug_max_bytes)
+    except ValueError as e:
+        raise SystemExit("--waveaug: %s" % e)
+    torch.cuda.synchronize(dev)
+    say("resident train waveforms: %s, %.2f s" % (resident.message, time.perf_counter() - t0))
+    return resident, aug
 
 
 def init_device(args):
@@ -309,8 +349,16 @@ def run(trainer, args, dev):
     # the test split is rank 0's alone: the other ranks never evaluate, and with --resident would fill a pool they never read
     names = ("train", "test") if rank == 0 else ("train",)
     splits = [SplitData(data_dir, name, args.dataset, resample=args.resample) for name in names]
+    waveaug = ops.waveaug_policy(getattr(args, "waveaug", "")) is not None
+    feed = {}           # what train.batches takes beyond SplitData's arguments
+    if waveaug:         # the training split as waveforms; the other one as --resident says
+        wave_train, aug = make_wave_resident(splits[0], dev, args, rank, say)
+        feed = dict(aug=aug, step=lambda: trainer.steps)
     if args.resident:
-        splits = [make_resident(s, name, dev, args.resident_workers, say, args.resample) for s, name in zip(splits, names)]
+        splits = [s if waveaug and name == "train" else make_resident(s, name, dev, args.resident_workers, say, args.resample)
+                  for s, name in zip(splits, names)]
+    if waveaug:
+        splits[0] = wave_train
     train, test = splits[0], (splits[1] if rank == 0 else None)
     if rank == 0:
         os.makedirs(args.output_dir, exist_ok=True)
@@ -345,7 +393,7 @@ def run(trainer, args, dev):
             order = list(range(len(train)))
             random.Random((args.seed or 0) + epoch).shuffle(order)       # alike on every rank
             order = shard_order(order, rank, world)
-        for mel, cap_lens, image, label in train.batches(args.batch_size, dev, shuffle=True, order=order):
+        for mel, cap_lens, image, label in train.batches(args.batch_size, dev, shuffle=True, order=order, **feed):
             loss = trainer.step(mel, cap_lens, image, label)
             part = torch.stack([loss["loss"], loss["accu"]]) * len(cap_lens)       # stays on the device until the epoch ends
             total = part if total is None else total + part
