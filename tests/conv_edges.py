@@ -1,5 +1,6 @@
 """Hand-written convolution launches at the edges of the tile kernels: partly filled row tiles, column and K tails, short
-last K splits, pixel-chunk tails of the weight gradients, ragged image tiles of the bf16 kernels.
+last K splits, pixel-chunk tails of the weight gradients, ragged image tiles of the bf16 kernels, and every branch of the
+bf16 planner that no production shape takes (_bf16_branches).
 
 The train step's census (tests/step_launches.json) holds production shapes only: batches of 24 / 48 (72 / 144 stacked)
 on power-of-two maps, where every GEMM is a whole number of row tiles and pixel chunks.  The records below use the
@@ -11,6 +12,7 @@ census schema, so conv_replay.replay_conv / replay_wgrad run them unchanged, and
              the record in fp64
   tile_rows  the value of ops.TILE_ROWS the replay runs under (0 = the planner's choice)
   tune       planner knobs (_lib.tuning) the replay runs under
+  direct     (bf16 branch rows) the record is also launched through s2i_conv_forward_bf16 itself, into guarded buffers
 
 The constructors fill in the packed-weight shape, wR, ldw, w_offset and fast the way ops.ConvBnAct / ConvAct and
 ops._dgrad / _wgrad launch the layer."""
@@ -37,6 +39,13 @@ REACH = (
     "b16-ragged-256",     # the same on the 256-pixel kernel
     "b16-persist-uneven",  # persistent 256-pixel kernel: the blocks walk different numbers of tiles
     "b16-wg-stagetail",   # bf16 weight gradient: the pixel range ends on a short 64-pixel stage
+    "b16-coltail",        # bf16 convolution: N is no multiple of the kernel's column block (Npad > N)
+    "b16-v2-split",       # 256-pixel kernel with a K split: raw slabs, then splitk_reduce_bf16_kernel
+    "b16-short-last-split",  # bf16 K split whose last split has fewer channel chunks than the others
+    "b16-tb>1",           # a pixel tile of more than one image
+    "b16-cls-multi-image",   # class-bias table on a tile of more than one image
+    "b16-groups-multi-image",  # grouped BatchNorm statistics on tiles of more than one image
+    "b16-wg-split-overwrite",  # bf16 weight gradient: summed from more than one slab into a destination it overwrites
 )
 
 
@@ -72,15 +81,16 @@ def fwd(layer, B, H, Cx, N, why, reach, *, Cc=0, cls=0, stats=True, groups=1, bf
     return _extra(rec, why, reach, tile_rows, tune)
 
 
-def dgrad(layer, B, H, Cx, O, why, reach, *, bf16=False, tile_rows=0, tune=None):
-    """Input gradient of a layer Cx -> O channels on an H x H input (ops._dgrad): dy [B, Ho, Ho, Op] -> [B, H, H, Cx]."""
+def dgrad(layer, B, H, Cx, O, why, reach, *, bf16=False, fast=None, tile_rows=0, tune=None):
+    """Input gradient of a layer Cx -> O channels on an H x H input (ops._dgrad): dy [B, Ho, Ho, Op] -> [B, H, H, Cx].
+    fast=False with bf16: a layer the bf16 plan names no kernel for (NO_KERNEL below)."""
     kind, flip = ops._DGRAD[layer]
     packed = _packed(layer, O, Cx)
     Ho = {"k1": H, "k3s1": H, "k4s2": H // 2, "up": 2 * H}[layer]
     rec = dict(fn="conv_any" if bf16 else "conv_raw", kind=kind, wmode=1, flip=flip, x=[[B, Ho, Ho, packed[2]], _dt(bf16)],
                w=dict(packed=packed, oihw=[O, Cx, KH[layer], KH[layer]], mode=ops.PACK_UPFOLD if layer == "up" else
                       ops.PACK_PLAIN), N=Cx, out_dtype=_dt(bf16), stats=False, groups=1, w_offset=0, cvec=0, cls_bias=False,
-               bias=0, act=0, fast=bf16)
+               bias=0, act=0, fast=bf16 if fast is None else fast)
     if not bf16:
         rec.update(wR=packed[1], ldw=packed[2])
     return _extra(rec, why, reach, tile_rows, tune)
@@ -186,24 +196,24 @@ def _table():
     t.append(wgrad("k4s2", 5, 8, 64, 128, "M = 80, 256 x 128 tile, accumulated into a slice", ["wg-pixtail-256x128"],
                    accumulate=True, i_off=8, tune=dict(wgrad_bm=256)))
     # ---- bf16 --------------------------------------------------------------------------------------------------------
-    t.append(fwd("k3s1", 5, 4, 256, 512, "4x4 maps: a 128-pixel tile spans 8 images, the batch has 5", ["b16-ragged-128"],
+    t.append(fwd("k3s1", 5, 4, 256, 512, "4x4 maps: a 128-pixel tile spans 8 images, the batch has 5", ["b16-ragged-128", "b16-tb>1"],
                  bf16=True))
-    t.append(fwd("k4s2", 9, 16, 64, 128, "8x8 outputs: 2 images per tile, 9 images", ["b16-ragged-128"], bf16=True))
-    t.append(fwd("up", 9, 4, 256, 256, "transposed conv on 4x4 maps: 8 images per tile, 9 images", ["b16-ragged-128"],
+    t.append(fwd("k4s2", 9, 16, 64, 128, "8x8 outputs: 2 images per tile, 9 images", ["b16-ragged-128", "b16-tb>1"], bf16=True))
+    t.append(fwd("up", 9, 4, 256, 256, "transposed conv on 4x4 maps: 8 images per tile, 9 images", ["b16-ragged-128", "b16-tb>1"],
                  bf16=True))
-    t.append(dgrad("k3s1", 5, 4, 256, 512, "input gradient on 4x4 maps, 5 of 8 images", ["b16-ragged-128"], bf16=True))
+    t.append(dgrad("k3s1", 5, 4, 256, 512, "input gradient on 4x4 maps, 5 of 8 images", ["b16-ragged-128", "b16-tb>1"], bf16=True))
     t.append(dgrad("k4s2", 9, 8, 128, 64, "stride-2 input gradient (transposed conv of dy on 4x4 maps), 9 images",
-                   ["b16-ragged-128"], bf16=True))
+                   ["b16-ragged-128", "b16-tb>1"], bf16=True))
     t.append(dgrad("up", 9, 4, 256, 256, "up-block input gradient: stride-2 gather of dy [9, 8, 8, 256]: 4x4 outputs, 8 images "
-                   "per tile", ["b16-ragged-128"], bf16=True))
+                   "per tile", ["b16-ragged-128", "b16-tb>1"], bf16=True))
     v2 = dict(b16_v2=2, b16_persist=4)
-    t.append(fwd("k3s1", 5, 8, 96, 256, "256-pixel kernel on 8x8 maps: 4 images per tile, 5 images", ["b16-ragged-256"],
+    t.append(fwd("k3s1", 5, 8, 96, 256, "256-pixel kernel on 8x8 maps: 4 images per tile, 5 images", ["b16-ragged-256", "b16-tb>1"],
                  bf16=True, tune=v2))
     t.append(fwd("k4s2", 5, 32, 96, 256, "persistent 256-pixel kernel: 5 one-image tiles over 2 block slots",
                  ["b16-persist-uneven"], bf16=True, tune=v2))
     t.append(fwd("up", 5, 8, 192, 256, "256-pixel transposed conv on 8x8 maps: 4 images per tile, 5 images",
-                 ["b16-ragged-256"], bf16=True, tune=v2))
-    t.append(dgrad("k3s1", 5, 8, 256, 96, "256-pixel kernel, input gradient, 5 images on 8x8 maps", ["b16-ragged-256"],
+                 ["b16-ragged-256", "b16-tb>1"], bf16=True, tune=v2))
+    t.append(dgrad("k3s1", 5, 8, 256, 96, "256-pixel kernel, input gradient, 5 images on 8x8 maps", ["b16-ragged-256", "b16-tb>1"],
                    bf16=True, tune=v2))
     for bm in (128, 256, 512):
         t.append(wgrad("k3s1", 5, 4, 256, 256, "bf16 x bf16, M = 80: a 64-pixel stage and a 16-pixel one",
@@ -215,7 +225,109 @@ def _table():
     t.append(wgrad("up", 5, 4, 64, 128, "bf16 x bf16 up-block (swap, fold), M = 80", ["b16-wg-stagetail"], a16=True, g16=True))
     t.append(wgrad("k4s2", 5, 8, 4, 64, "the first discriminator conv in bf16 mode: fp32 NHWC4 image x bf16 gradient, M = 80",
                    ["b16-wg-stagetail"], g16=True))
+    t += _bf16_branches(v2)
     return t
+
+
+def _bf16_branches(v2):
+    """The branches of plan_bf16 that no production shape takes, each at the smallest shape that still takes it: column
+    blocks wider than N on every kernel, the 256-pixel kernels with a K split, the class-bias table and grouped statistics
+    on tiles of several images, the kernels and directions no census record runs, the smallest weight-gradient tile.
+    direct=True: tests/test_conv_edges_gpu.py also calls s2i_conv_forward_bf16 itself with ldy = N + 8 into guarded buffers."""
+    t = []
+
+    def f(*a, direct=False, **k):
+        t.append(dict(fwd(*a, bf16=True, **k), direct=direct))
+
+    def g(*a, direct=False, **k):
+        t.append(dict(dgrad(*a, bf16=True, **k), direct=direct))
+
+    def w(*a, **k):
+        t.append(wgrad(*a, a16=True, g16=True, **k))
+
+    tb, rag, ct = "b16-tb>1", "b16-ragged-128", "b16-coltail"
+    # ---- kernels and directions the census never runs ----------------------------------------------------------------
+    f("up", 2, 8, 64, 32, "tconv-32x64 (never run): 32 columns, 2 images in the one tile of each phase", [tb])
+    f("up", 3, 16, 64, 32, "tconv-32x64: one image per tile, 6 tiles per phase", [])
+    f("k3s1", 2, 16, 64, 32, "k3s1-32x64 forward (the census has its input gradient only)", [])
+    f("k4s2", 3, 16, 32, 64, "k4s2-64x32 forward", [rag, tb])
+    f("k4s2", 3, 16, 32, 32, "k4s2-32x32 forward", [rag, tb])
+    g("k4s2", 3, 16, 32, 32, "tconv-32x32 as the stride-2 input gradient (the census has its forward only)", [rag, tb])
+    g("k4s2", 3, 16, 32, 64, "tconv-32x64 as the stride-2 input gradient", [rag, tb])
+    g("up", 3, 16, 128, 128, "256-pixel k4s2 as the up-block input gradient, K split in two", ["b16-v2-split"], tune=v2)
+    g("up", 1, 32, 128, 32, "256-pixel k4s2 with the 66-pixel patch as the up-block input gradient: 32-column tiles of dy "
+      "[1, 64, 64, 32]", [], tune=v2)
+    g("up", 1, 32, 72, 32, "the same with 72 of 128 columns", [ct], tune=v2)
+    # ---- column tail, 128-pixel kernels ------------------------------------------------------------------------------
+    for N in (72, 136, 200):
+        f("k3s1", 3, 8, 64, N, "k3s1-128x16 with N = %d: the last column block holds %d of 128" % (N, N % 128), [ct, rag, tb])
+    f("k3s1", 3, 8, 64, 40, "k3s1-64x32 with 40 of 64 columns", [ct, rag, tb], direct=True)
+    f("k3s1", 3, 8, 64, 24, "k3s1-32x64 with 24 of 32 columns", [ct, rag, tb])
+    f("k3s1", 3, 4, 256, 72, "k3s1-128x16, 8 K splits, N = 72: the reduction with 18 column quads", [ct, rag, tb], direct=True)
+    f("k4s2", 3, 16, 64, 72, "k4s2-128x32 with 72 of 128 columns", [ct, rag, tb], direct=True)
+    f("k4s2", 3, 16, 64, 40, "k4s2-64x32 with 40 of 64 columns", [ct, rag, tb])
+    f("up", 3, 8, 64, 72, "tconv-128x32 with 72 of 128 columns", [ct, rag, tb])
+    f("up", 3, 8, 64, 40, "tconv-64x64 with 40 of 64 columns", [ct, rag, tb])
+    f("up", 3, 8, 64, 24, "tconv-32x64 with 24 of 32 columns", [ct, rag, tb], direct=True)
+    f("k3s1", 3, 8, 32, 24, "k3s1-32x32 (32 input channels) with 24 of 32 columns", [ct, rag, tb])
+    f("k4s2", 3, 16, 32, 24, "k4s2-32x32 with 24 of 32 columns", [ct, rag, tb])
+    f("up", 3, 8, 32, 24, "tconv-32x32 with 24 of 32 columns", [ct, rag, tb])
+    f("k4s2", 9, 8, 64, 72, "k4s2-128x16 (8 maps of 4x4 outputs per tile) with 72 of 128 columns, 9 images", [ct, rag, tb])
+    g("k3s1", 3, 8, 72, 64, "flipped 3x3 input gradient into 72 channels", [ct, rag, tb])
+    g("k3s1", 3, 4, 72, 256, "flipped 3x3 input gradient into 72 channels, 8 K splits", [ct, rag, tb], direct=True)
+    # ---- column tail, 256-pixel kernels ------------------------------------------------------------------------------
+    f("k3s1", 5, 8, 96, 200, "v2-k3s1, 4 images per tile, 5 images, N = 200", [ct, "b16-ragged-256", tb], tune=v2, direct=True)
+    f("k4s2", 3, 32, 64, 200, "v2-k4s2, persistent: 3 tiles over 2 block slots, N = 200", [ct, "b16-persist-uneven"], tune=v2)
+    f("k4s2", 2, 64, 32, 136, "v2-k4s2-pw66, N = 136", [ct], tune=v2, direct=True)
+    f("up", 3, 8, 64, 200, "v2-tconv, N = 200", [ct, "b16-ragged-256", tb], tune=v2, direct=True)
+    # ---- 256-pixel kernels with a K split ----------------------------------------------------------------------------
+    f("k3s1", 4, 8, 256, 128, "v2-k3s1, 4 K splits", ["b16-v2-split", tb], tune=v2)
+    f("k3s1", 5, 8, 224, 128, "v2-k3s1, 7 chunks in splits of 3 + 3 + 1, 5 images on tiles of 4",
+      ["b16-v2-split", "b16-short-last-split", "b16-ragged-256", tb], tune=v2)
+    f("up", 4, 8, 256, 128, "v2-tconv, 2 K splits in each phase", ["b16-v2-split", tb], tune=v2)
+    f("up", 5, 8, 320, 128, "v2-tconv, 5 chunks in splits of 3 + 2", ["b16-v2-split", "b16-short-last-split", "b16-ragged-256",
+                                                                      tb], tune=v2)
+    f("k4s2", 1, 32, 128, 128, "v2-k4s2, 2 K splits (split, so not persistent)", ["b16-v2-split"], tune=v2)
+    f("k4s2", 3, 32, 160, 136, "v2-k4s2, 5 chunks in splits of 3 + 2, N = 136", ["b16-v2-split", "b16-short-last-split", ct],
+      tune=v2, direct=True)
+    f("k4s2", 1, 64, 160, 128, "v2-k4s2-pw66, 5 chunks in splits of 3 + 2", ["b16-v2-split", "b16-short-last-split"], tune=v2)
+    # ---- class bias on tiles of several images (cls = 128 folded weight rows, as the census has them) -----------------
+    cm = "b16-cls-multi-image"
+    f("k3s1", 5, 4, 64, 64, "class bias, k3s1-64x32: 8 images per tile, 5 images", [cm, rag, tb], cls=128)
+    f("k3s1", 5, 8, 64, 128, "class bias, k3s1-128x16: 2 images per tile, 5 images", [cm, rag, tb], cls=128)
+    f("k3s1", 5, 4, 256, 128, "class bias, 16 chunks on one tile: unsplit only because the class bias forbids the split",
+      [cm, rag, tb], cls=128)
+    f("k3s1", 5, 8, 96, 256, "class bias, v2-k3s1: 4 images per tile, 5 images", [cm, "b16-ragged-256", tb], cls=128, tune=v2)
+    # ---- grouped statistics on tiles of several images ---------------------------------------------------------------
+    gm = "b16-groups-multi-image"
+    f("k3s1", 8, 8, 128, 128, "2 groups of 4 images, 2 images per tile", [gm, tb], groups=2)
+    f("k3s1", 6, 8, 128, 128, "3 groups of 2 images, 2 images per tile", [gm, tb], groups=3)
+    f("k3s1", 8, 8, 96, 256, "v2-k3s1: 2 groups of 4 images, 4 images per tile", [gm, tb], groups=2, tune=v2)
+    f("k4s2", 6, 32, 64, 128, "v2-k4s2, persistent: 6 one-image tiles of 3 groups over 4 block slots", ["b16-persist-uneven"],
+      groups=3, tune=v2)
+    f("k3s1", 6, 8, 256, 72, "3 groups of 2 images, 8 K splits, N = 72: the reduction's rows per group", [gm, tb, ct], groups=3, direct=True)
+    f("k3s1", 8, 8, 256, 128, "v2-k3s1: 2 groups of 4 images, 4 K splits", [gm, tb, "b16-v2-split"], groups=2, tune=v2)
+    # ---- bf16 weight gradient ----------------------------------------------------------------------------------------
+    w("k1", 3, 4, 64, 64, "b16-64x64 (never run), M = 48: less than one stage", ["b16-wg-stagetail"])
+    w("k1", 3, 8, 32, 40, "b16-64x64 with 40 of 64 columns", [])
+    w("k1", 1, 16, 32, 40, "b16-64x64, 2 slabs summed into a prefilled gradient it overwrites", ["b16-wg-split-overwrite"], out=True)
+    w("k3s1", 1, 16, 32, 32, "b16-128x32, 2 slabs summed into input channels [32, 64) of a wider tensor",
+      ["b16-wg-split-overwrite"], i_off=32)
+    return t
+
+
+# planned by plan_bf16, which names no kernel for it (B16_NO_KERNEL): ops.conv_any takes the any-dtype fp32 kernel, bf16 in
+# and out (fast=False), and the result holds the bound of the bf16 kernels
+NO_KERNEL = [
+    dgrad("k4s2", 3, 16, 64, 32, "transposed conv with BN 64 and 32-channel chunks", ["rowtail-128x64", "rowtail-4phase"],
+          bf16=True, fast=False),
+]
+
+# refused by plan_bf16 before any launch: (record, text of the error)
+REFUSED = [
+    (fwd("k3s1", 8, 4, 128, 128, "2 groups of 4 images on 4x4 maps: the 128-pixel tile holds 8 images", [], groups=2, bf16=True),
+     "a tile of 8 images straddles the 2 BatchNorm groups of batch 8"),
+]
 
 
 RECORDS = _table()
@@ -313,12 +425,28 @@ def _bf16_plan(rec, M, nph):
     assert told is not None and told["kernel"] is not None, (told, _lib.load().s2i_last_error())
     assert told["rows"] == M * nph, told
     B, bm, tb, gx, tiles = rec["x"][0][0], told["pixels"], told["tb"], told["gx"], told["tiles"]
+    sk, cps, nchunks = told["splitk"], told["cps"], told["nchunks"]
     reach = set()
     if B % tb:
         reach.add("b16-ragged-%d" % bm)
     if gx < tiles and tiles % gx:         # persistent form: gx block slots walk the tiles, some one tile more than others
         reach.add("b16-persist-uneven")
-    return dict(M=M, nphases=nph, splitk=told["splitk"], bm=bm, tb=tb, gridM=tiles, reach=reach)
+    if rec["N"] % told["bn"]:
+        assert told["npad"] > rec["N"], told
+        reach.add("b16-coltail")
+    if bm == 256 and sk > 1:
+        reach.add("b16-v2-split")
+    if sk > 1 and nchunks % cps:
+        reach.add("b16-short-last-split")
+    if tb > 1:
+        reach.add("b16-tb>1")
+        # declared on the record, checked against the plan's images per tile
+        if rec["cls_bias"]:
+            reach.add("b16-cls-multi-image")
+        if rec["stats"] and rec["groups"] > 1:
+            reach.add("b16-groups-multi-image")
+    return dict(M=M, nphases=nph, splitk=sk, cps=cps, nchunks=nchunks, bm=bm, BN=told["bn"], CK=told["ck"], tb=tb, gridM=tiles,
+                gx=gx, kernel=told["kernel"], npad=told["npad"], parts=told["parts"], ws_bytes=told["ws_bytes"], reach=reach)
 
 
 def wgrad_plan(rec):
@@ -349,12 +477,14 @@ def wgrad_plan(rec):
     if family in ("b16", "b16d1"):
         if M % told["stage"]:
             reach.add("b16-wg-stagetail")
+        if told["ws_slabs"] > 1 and not rec["accumulate"]:
+            reach.add("b16-wg-split-overwrite")
     elif rows3:
         if B & (B - 1):
             reach.add("wg-rows3-odd-batch")
     elif M % told["stage"]:
         reach.add("wg-pixtail-%dx%d" % tile)
-    return dict(M=M, K=K, N=N, tile=tile, rows3=rows3, splitk=told["ws_slabs"], reach=reach)
+    return dict(M=M, K=K, N=N, tile=tile, rows3=rows3, splitk=told["ws_slabs"], kernel=told["kernel"], reach=reach)
 
 
 def plan(rec):
