@@ -486,6 +486,46 @@ int s2i_wave_mix(float* x, const long long* offsets, const int* lens, int B, int
                  const void* table, unsigned long long seed, unsigned long long step, void* ws, size_t ws_bytes,
                  void* stream);
 
+/* ---- room reverberation of a batch of waveforms (csrc/s2i_reverb.hip) -------------------------------------------------------
+   Each clip is convolved with a room impulse response (RIR) of its own: a unit direct path and an exponentially decaying
+   noise tail.  table: DEVICE, 16 bytes per clip, 16-byte aligned:
+     float alpha; float slope; int taps; unsigned uid;
+   taps == 0 switches the clip off; else taps is a multiple of 32 in [32, max_taps].  slope = -log2(1000) / (T60 16000), the
+   log2 of the envelope per tap (the tail is 60 dB down after T60 seconds), and alpha = sqrt(10^(-DRR / 10) / E) with
+   E = sum_{k = 1}^{taps - 1} 2^(2 k slope), both computed in float64 by the host and rounded to fp32 once; uid is the clip's
+   id in the counter.
+
+   s2i_reverb_rir writes h[B][max_taps] (fp32, 16-byte aligned), max_taps a multiple of 32 in [32, 16000].  Row b:
+     h[0] = 1;   h[k] = (alpha e_k) env_k for 1 <= k < taps;   h[k] = 0 for taps <= k < max_taps
+   (a row with taps == 0 is all zeros and never read).  env_k = exp2f((float)k slope): the product rounded to fp32, then
+   exp2f.  e_k is s2i_wave_mix's unit-variance value ((float)s - 131070.0f) 0x1.bb67aep-16f, s the sum of the four 16-bit
+   halves of two words of the Philox4x32-10 block with key (seed mod 2^32, (seed div 2^32) ^ 0x52455642) and counter
+   (step mod 2^32, step div 2^32, uid, 1 + k div 2): words (r0, r1) for an even k, (r2, r3) for an odd one.  The key differs
+   in word 1 from s2i_specaug's and from s2i_wave_mix's for every seed, so no block is shared with either; counter 0 of a
+   uid is the host's draws.  The two products are rounded to fp32 one after the other, alpha e_k first (no fused
+   multiply-add).  One launch, one thread per tap.
+
+   s2i_reverb writes y, a second flat fp32 buffer laid out as x: clip b is x[offsets[b] .. offsets[b] + n) and
+   y[offsets[b] .. offsets[b] + n), offsets DEVICE int64 [B] in floats, n = lens[b] (DEVICE int32 [B], clamped to
+   [0, max_len]); max_len is the host's bound on the lens, in [1, 2^31 - 8225].  x, y and h are 16-byte aligned and y is
+   disjoint from x and h.  For a clip with taps > 0
+     y_i = sum_{k = 0}^{taps - 1} h[k] x_{i - k},   i in [0, n),   x_i = 0 for i < 0:
+   the clip keeps its length and the tail past it is cut; nothing is renormalised (the log-mel front end is invariant to a
+   clip's gain).  A clip with taps == 0 is copied bit for bit.  Floats outside the clips are never written.
+   order:  the sum is a block-Toeplitz product on v_mfma_f32_32x32x2_f32, an exact fmaf chain.  Write i = 32 a + b with
+           b in [0, 32).  Output i has ONE fp32 accumulator that starts at +0 and takes
+             acc = fmaf(h[32 j + b - m], x[32 (a - j) + m], acc)     (h = 0 outside [0, taps), x = 0 outside [0, n))
+           for j = 0, 1, ..., min(taps / 32, a) in that order and, inside a j, for m = 0, 1, ..., 31 in that order.  Blocks
+           j > a multiply samples before the clip and are skipped.  The order depends on i, taps and n alone: the same clip
+           with the same h gives the same bits alone or in any batch, at any offset and for any max_len, on every run.
+   One launch over (clip, tile of 8192 outputs), no workspace, no atomics, no host round trip.
+   Bad arguments (a null pointer, B < 1, max_len or max_taps outside its range, a misaligned buffer, y == x or y == h)
+   return non-zero before any launch. */
+int s2i_reverb_rir(const void* table, int B, int max_taps, float* h, unsigned long long seed, unsigned long long step,
+                   void* stream);
+int s2i_reverb(const float* x, const long long* offsets, const int* lens, int B, int max_len, const void* table,
+               const float* h, int max_taps, float* y, void* stream);
+
 /* ---- CA_NET reparameterisation + KL (model.py:182-200, trainer.py:54-58) -------------------- */
 /* h = GLU output [B][2E] = [mu | logvar];  c = eps*exp(0.5*logvar) + mu */
 int s2i_reparam_forward(const float* h, const float* eps, int B, int E, float* c, void* stream);

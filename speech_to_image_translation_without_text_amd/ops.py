@@ -1995,6 +1995,11 @@ WAVE_MIX_RUN = 8192
 # the device table of s2i_wave_mix, 32 bytes per clip (include/s2i_hip.h)
 WAVE_MIX_ENTRY = [("g_white", "<f4"), ("g_babble", "<f4"), ("src", "<i8"), ("n_j", "<i4"), ("start", "<i4"),
                   ("uid", "<u4"), ("pad", "<i4")]
+REVERB_KEY_XOR = 0x52455642         # into key word 1: no (key, counter) block is SpecAugment's or the other waveform draws'
+REVERB_MAX_TAPS = 16000
+REVERB_MAX_LEN = 2 ** 31 - 8225
+# the device table of s2i_reverb_rir and s2i_reverb, 16 bytes per clip (include/s2i_hip.h)
+REVERB_ENTRY = [("alpha", "<f4"), ("slope", "<f4"), ("taps", "<i4"), ("uid", "<u4")]
 
 
 def _waveaug_noise(token, value):
@@ -2011,6 +2016,28 @@ def _waveaug_noise(token, value):
     if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
         raise ValueError("bad augmentation %r: the SNR range needs finite LO <= HI" % token)
     return prob, lo, hi
+
+
+def _waveaug_reverb(token, value):
+    parts = value.split("@")
+    try:
+        if len(parts) != 3:
+            raise ValueError
+        prob = float(parts[0])
+        (lo, sep, hi), (dlo, sep2, dhi) = parts[1].partition(":"), parts[2].partition(":")
+        if not sep or not sep2:
+            raise ValueError
+        lo, hi, dlo, dhi = float(lo), float(hi), float(dlo), float(dhi)
+    except ValueError:
+        raise ValueError("bad augmentation %r: expected P@LO:HI@DLO:DHI, a probability, a T60 range in seconds and a range "
+                         "of the direct-to-reverberant ratio in dB" % token) from None
+    if not 0.0 < prob <= 1.0:       # a NaN fails both
+        raise ValueError("bad augmentation %r: the probability must lie in (0, 1]" % token)
+    if not 0.05 <= lo <= hi <= 1.0:
+        raise ValueError("bad augmentation %r: the T60 range needs 0.05 <= LO <= HI <= 1.0 seconds" % token)
+    if not -20.0 <= dlo <= dhi <= 60.0:
+        raise ValueError("bad augmentation %r: the direct-to-reverberant range needs -20 <= DLO <= DHI <= 60 dB" % token)
+    return prob, lo, hi, dlo, dhi
 
 
 def _waveaug_speeds(token, value):
@@ -2038,14 +2065,20 @@ def _waveaug_speeds(token, value):
 
 
 def waveaug_policy(spec):
-    """'speed=0.9/1.0/1.1,white=0.3@5:25,babble=0.2@0:15' (any order, any subset; '' = off -> None) -> a dict
+    """'speed=0.9/1.0/1.1,reverb=0.3@0.2:0.6@0:15,white=0.3@5:25,babble=0.2@0:15' (any order, any subset; '' = off ->
+    None) -> a dict
     {"rates": the sample rates 16000 s a clip is read at, one per speed factor (None without speed=),
-     "white": (P, LO, HI) or None, "babble": (P, LO, HI) or None}.
+     "white": (P, LO, HI) or None, "babble": (P, LO, HI) or None}
+    and, only where reverb= was given, "reverb": (P, LO, HI, DLO, DHI) (read it with .get).
     speed= takes 1 to 8 factors in [0.5, 2.0], each of which makes 16000 s a whole rate `audio.resample_plan` accepts; an
-    utterance draws one uniformly.  white= and babble= add noise or another utterance with probability P in (0, 1] at a
-    signal-to-noise ratio drawn uniformly from [LO, HI] dB.  There is no gain key on purpose: power_to_db(ref=max) and
-    the mean subtraction of the log-mel front end make the features invariant to a clip's gain."""
-    values = {"speed": None, "white": None, "babble": None}
+    utterance draws one uniformly.  reverb=P@LO:HI@DLO:DHI convolves a clip, with probability P in (0, 1], with a room
+    impulse response drawn on the device: T60 uniform in [LO, HI] seconds (0.05 <= LO <= HI <= 1.0) and the
+    direct-to-reverberant ratio uniform in [DLO, DHI] dB (within [-20, 60]); it is applied after the speed and before the
+    noise, whose power is then the reverberated clip's.  white= and babble= add noise or another utterance with
+    probability P in (0, 1] at a signal-to-noise ratio drawn uniformly from [LO, HI] dB.  There is no gain key on purpose:
+    power_to_db(ref=max) and the mean subtraction of the log-mel front end make the features invariant to a clip's
+    gain."""
+    values = {"speed": None, "white": None, "babble": None, "reverb": None}
     seen = set()
     for token in str(spec).split(","):
         token = token.strip()
@@ -2055,14 +2088,18 @@ def waveaug_policy(spec):
         key = key.strip()
         if not sep or key not in values:
             raise ValueError("unknown augmentation %r: expected a comma-separated subset of speed=S/S/..., white=P@LO:HI, "
-                             "babble=P@LO:HI" % token)
+                             "babble=P@LO:HI, reverb=P@LO:HI@DLO:DHI" % token)
         if key in seen:
             raise ValueError("augmentation %r given twice" % token)
         seen.add(key)
-        values[key] = _waveaug_speeds(token, value.strip()) if key == "speed" else _waveaug_noise(token, value.strip())
+        parse = {"speed": _waveaug_speeds, "reverb": _waveaug_reverb}.get(key, _waveaug_noise)
+        values[key] = parse(token, value.strip())
     if not seen:
         return None
-    return {"rates": values["speed"], "white": values["white"], "babble": values["babble"]}
+    policy = {"rates": values["speed"], "white": values["white"], "babble": values["babble"]}
+    if values["reverb"] is not None:
+        policy["reverb"] = values["reverb"]
+    return policy
 
 
 def philox4x32_10(c0, c1, c2, c3, k0, k1):
@@ -2108,7 +2145,14 @@ def waveaug_plan(policy, seed, step, uids, lens, pool_lens=None, pool_q=None, ta
 
     Returns a dict of arrays: rate (int64, the rate the clip is read at), out_len (int64), white_snr / babble_snr
     (float64, NaN where off), g_white / g_babble (float32, 0 where off: 10^(-snr / 10), for babble divided by Q_j; 0 also
-    where Q_j == 0), src and start (int64), uid (uint32)."""
+    where Q_j == 0), src and start (int64), uid (uint32).
+
+    reverb= draws from a key of its own, (seed mod 2^32, (seed div 2^32) ^ REVERB_KEY_XOR), at counter
+    (step mod 2^32, step div 2^32, uid, 0): u_on (apply if < P), u_t60, u_drr, each (r >> 8) 2^-24; T60 and DRR are
+    LO + u (HI - LO) in float64.  No field above depends on it.  It adds t60 and drr (float64, NaN where off), taps (int64,
+    0 where off, else 32 ceil(T60 16000 / 32), at most 16000), slope (float32, -log2(1000) / (T60 16000) rounded once) and
+    alpha (float32, sqrt(10^(-DRR / 10) / E), E = sum_{k=1}^{taps-1} 2^(2 k slope) in float64 over the rounded slope, the
+    geometric series summed in closed form): the tail's expected energy is 10^(-DRR / 10) of the direct path's.  Without reverb= the five fields are absent."""
     import numpy as np
     from . import audio
     uids = np.asarray(uids, dtype=np.int64).reshape(-1)
@@ -2153,7 +2197,44 @@ def waveaug_plan(policy, seed, step, uids, lens, pool_lens=None, pool_q=None, ta
         plan["g_babble"] = np.where(on_q, 10.0 ** (-snr / 10.0) / np.where(q > 0.0, q, 1.0), 0.0).astype(np.float32)
         plan["src"] = src
         plan["start"] = _waveaug_index(u1[2], pool_lens[src])
+    if policy.get("reverb") is not None:
+        plan.update(_reverb_plan(policy["reverb"], seed, step, uids))
     return plan
+
+
+def _reverb_plan(term, seed, step, uids):
+    """the reverb fields of waveaug_plan"""
+    import numpy as np
+    from . import audio
+    p, lo, hi, dlo, dhi = term
+    seed, step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+    r = philox4x32_10(step & 0xFFFFFFFF, step >> 32, np.asarray(uids, dtype=np.uint64), 0, seed & 0xFFFFFFFF,
+                      (seed >> 32) ^ REVERB_KEY_XOR)
+    u = ((r >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)).astype(np.float64)
+    B = len(uids)
+    on = u[0] < p
+    t60 = lo + u[1] * (hi - lo)
+    drr = dlo + u[2] * (dhi - dlo)
+    taps = np.minimum(32 * np.ceil(t60 * audio.SAMPLE_RATE / 32.0).astype(np.int64), REVERB_MAX_TAPS)
+    slope = (-math.log2(1000.0) / (t60 * audio.SAMPLE_RATE)).astype(np.float32)
+    # E = sum_{k=1}^{taps-1} q^k with q = 2^(2 slope) < 1, in closed form (float64): 16000 exponentials per clip on the host
+    # would cost more than the convolution does on the device
+    q = np.exp2(2.0 * slope.astype(np.float64))
+    energy = q * (1.0 - q ** (taps - 1).astype(np.float64)) / (1.0 - q)
+    alpha = np.where(on, np.sqrt(10.0 ** (-drr / 10.0) / energy), 0.0).astype(np.float32)
+    return dict(t60=np.where(on, t60, np.nan), drr=np.where(on, drr, np.nan), taps=np.where(on, taps, 0).astype(np.int64),
+                slope=np.where(on, slope, np.float32(0)).astype(np.float32), alpha=alpha)
+
+
+def reverb_table(plan):
+    """The 16-byte-per-clip table of s2i_reverb_rir and s2i_reverb (REVERB_ENTRY) out of a waveaug_plan made under
+    reverb=."""
+    import numpy as np
+    if "taps" not in plan:
+        raise ValueError("reverb_table: the plan was made without reverb=")
+    t = np.zeros(len(plan["uid"]), dtype=REVERB_ENTRY)
+    t["alpha"], t["slope"], t["taps"], t["uid"] = plan["alpha"], plan["slope"], plan["taps"], plan["uid"]
+    return t
 
 
 def wave_mix_table(plan, pool_offsets=None, pool_lens=None):
@@ -2241,6 +2322,62 @@ def wave_mix(x, offsets, lens, table, seed, step, pool=None):
     `wave_mix_launch` (two launches).  y_i = (x_i + a_w e_i) + a_b v_i with the noise a function of (seed, step, uid, i)
     alone.  No autograd, no CPU fallback.  Returns x."""
     return wave_mix_launch(wave_mix_prepare(x, offsets, lens, table, pool), seed, step)
+
+
+def reverb(x, offsets, lens, table, seed, step, out=None):
+    """Room reverberation of a ragged batch of waveforms: clip b = x[offsets[b] : offsets[b] + lens[b]] of the flat fp32
+    device tensor `x` convolved with the room impulse response that row b of `table` (numpy REVERB_ENTRY rows,
+    reverb_table) and (seed, step, uid) define; include/s2i_hip.h has the definitions.  The clips keep their lengths; a
+    clip with taps == 0 is copied bit for bit.  offsets, lens and table are HOST arrays, checked here against x -- the
+    kernels trust them -- and uploaded in one copy; then s2i_reverb_rir and s2i_reverb on the current stream.  Returns a
+    new flat tensor laid out as x (`out`, where given: same shape, dtype and device, apart from x), of which only the clips
+    are written.  No autograd, no CPU fallback."""
+    import numpy as np
+    _lib_ready()
+    if not x.is_cuda:
+        raise _lib.S2IError("reverb runs on the MI355X kernels: x is on %s" % x.device)
+    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_contiguous():
+        raise ValueError("reverb: x must be a flat contiguous fp32 tensor, got %s %s" % (x.dtype, tuple(x.shape)))
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    lens = np.ascontiguousarray(lens, dtype=np.int64).reshape(-1)
+    table = np.ascontiguousarray(table, dtype=REVERB_ENTRY).reshape(-1)
+    B = len(offsets)
+    if B < 1 or len(lens) != B or len(table) != B:
+        raise ValueError("reverb: offsets, lens and table must have one length >= 1, got %d, %d, %d"
+                         % (B, len(lens), len(table)))
+    if lens.min() < 0 or lens.max() > REVERB_MAX_LEN or offsets.min() < 0 or int((offsets + lens).max()) > x.numel():
+        raise ValueError("reverb: a clip lies outside x (%d floats) or is longer than %d" % (x.numel(), REVERB_MAX_LEN))
+    order = np.argsort(offsets, kind="stable")
+    if np.any(offsets[order][1:] < (offsets + lens)[order][:-1]):
+        raise ValueError("reverb: clips overlap")
+    taps = table["taps"].astype(np.int64)
+    if taps.min() < 0 or taps.max() > REVERB_MAX_TAPS or np.any(taps % 32 != 0):
+        raise ValueError("reverb: taps must be 0 or a multiple of 32 up to %d, got %s" % (REVERB_MAX_TAPS, taps.tolist()))
+    if not (np.all(np.isfinite(table["alpha"])) and np.all(np.isfinite(table["slope"]))):
+        raise ValueError("reverb: alpha and slope must be finite")
+    if out is None:
+        out = torch.empty_like(x)
+    elif (out.dtype != torch.float32 or out.shape != x.shape or not out.is_contiguous() or out.device != x.device
+          or out.data_ptr() == x.data_ptr()):
+        raise ValueError("reverb: out must be a flat contiguous fp32 tensor of x's size on %s, apart from x" % x.device)
+    max_len, max_taps = max(int(lens.max()), 1), max(int(taps.max()), 32)
+    # one upload: offsets | table | lens, each part on a 16-byte boundary
+    at_table = (8 * B + 15) // 16 * 16
+    at_lens = at_table + 16 * B
+    image = np.zeros(at_lens + 4 * B, dtype=np.uint8)
+    image[:8 * B] = offsets.view(np.uint8)
+    image[at_table:at_lens] = table.view(np.uint8)
+    image[at_lens:] = lens.astype(np.int32).view(np.uint8)
+    image_d = torch.from_numpy(image).to(x.device)
+    base = image_d.data_ptr()
+    h = torch.empty(B * max_taps, dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    mask64 = (1 << 64) - 1
+    check(lib.s2i_reverb_rir(base + at_table, B, max_taps, ptr(h), int(seed) & mask64, int(step) & mask64, stream()),
+          "s2i_reverb_rir")
+    check(lib.s2i_reverb(ptr(x), base, base + at_lens, B, max_len, base + at_table, ptr(h), max_taps, ptr(out), stream()),
+          "s2i_reverb")
+    return out
 
 
 # ---- nearest-row search -------------------------------------------------------------------------------------------------
