@@ -1,6 +1,7 @@
 """Hand-written convolution launches at the edges of the tile kernels: partly filled row tiles, column and K tails, short
 last K splits, pixel-chunk tails of the weight gradients, ragged image tiles of the bf16 kernels, and every branch of the
-bf16 planner that no production shape takes (_bf16_branches).
+bf16 planner (_bf16_branches) and of the weight-gradient planner and its finishing paths (_wgrad_branches) that no
+production shape takes.
 
 The train step's census (tests/step_launches.json) holds production shapes only: batches of 24 / 48 (72 / 144 stacked)
 on power-of-two maps, where every GEMM is a whole number of row tiles and pixel chunks.  The records below use the
@@ -12,7 +13,8 @@ census schema, so conv_replay.replay_conv / replay_wgrad run them unchanged, and
              the record in fp64
   tile_rows  the value of ops.TILE_ROWS the replay runs under (0 = the planner's choice)
   tune       planner knobs (_lib.tuning) the replay runs under
-  direct     (bf16 branch rows) the record is also launched through s2i_conv_forward_bf16 itself, into guarded buffers
+  direct     (branch rows) the record is also launched through s2i_conv_forward_bf16 / s2i_conv_wgrad(_dt) itself, into
+             guarded buffers
 
 The constructors fill in the packed-weight shape, wR, ldw, w_offset and fast the way ops.ConvBnAct / ConvAct and
 ops._dgrad / _wgrad launch the layer."""
@@ -46,7 +48,22 @@ REACH = (
     "b16-cls-multi-image",   # class-bias table on a tile of more than one image
     "b16-groups-multi-image",  # grouped BatchNorm statistics on tiles of more than one image
     "b16-wg-split-overwrite",  # bf16 weight gradient: summed from more than one slab into a destination it overwrites
-)
+    "b16-wg-recut-fewer-slabs",  # bf16 weight gradient: the 64-pixel re-cut writes fewer slabs than the workspace was sized for
+    "wg-pixtail-128x32",  # the pixel tail on the one fp32 tile the list above lacks
+    "wg-rows3-coltail",   # row-segment kernel: N is no multiple of the column block (the gcolb == S2I_OOB loads)
+    # fp32-MFMA and row-segment kernels: more than one slab and nchunks % cps != 0, the last pixel split is short
+    "wg-short-last-split-128x128", "wg-short-last-split-128x64", "wg-short-last-split-128x32", "wg-short-last-split-64x64",
+    "wg-short-last-split-96x64", "wg-short-last-split-96x32", "wg-short-last-split-256x128", "wg-short-last-split-256x256",
+    "wg-short-last-split-rows3",
+    # a bf16 operand read by a kernel named f32-* (bload4_any in igemm_wgrad_kernel): the GEMM's gathered operand a, its
+    # plain operand g, or both (both bf16 but Cin % 8 or N % 8 keeps the layer off the bf16 cores)
+    "wg-16-on-f32-a", "wg-16-on-f32-g", "wg-16-on-f32-ag",
+) + tuple(
+    # the finishing path of launch_wgrad (wgrad_finish below): rows per tile of the OIHW transpose, how the slabs were summed
+    # before it, a partly filled last 32-column block, the swapped (and folded) form of the up block
+    "wg-finish-rt%d-%s%s%s" % (rt, path, ctail, swap) for rt in (1, 2, 4, 8) for path in ("direct", "stream", "tree")
+    for ctail in ("", "-ctail") for swap in ("", "-swap"))
+FIN = "wg-finish-"
 
 
 def _r4(v):
@@ -96,9 +113,11 @@ def dgrad(layer, B, H, Cx, O, why, reach, *, bf16=False, fast=None, tile_rows=0,
     return _extra(rec, why, reach, tile_rows, tune)
 
 
-def wgrad(layer, B, H, Cin, N, why, reach, *, Cc=0, a16=False, g16=False, accumulate=False, out=False, i_off=0, tune=None):
+def wgrad(layer, B, H, Cin, N, why, reach, *, Cc=0, a16=False, g16=False, accumulate=False, out=False, i_off=0, tune=None,
+          direct=False):
     """Weight gradient of a layer Cin (+ Cc broadcast) -> N channels on an H x H input (ops._wgrad); the up layer gathers dy
-    by the k4s2 pattern against the layer input (swap, fold).  i_off > 0: the written slice of a wider tensor."""
+    by the k4s2 pattern against the layer input (swap, fold).  i_off > 0: the written slice of a wider tensor.  a16 / g16
+    name the layer's input and its output gradient; under swap they are the GEMM's g and a (rec["g"], rec["a"])."""
     k = KH[layer]
     Ho = {"k1": H, "k3s1": H, "k4s2": H // 2, "up": 2 * H}[layer]
     fn = "wgrad_any" if (a16 or g16) else "wgrad_raw"
@@ -109,6 +128,8 @@ def wgrad(layer, B, H, Cin, N, why, reach, *, Cc=0, a16=False, g16=False, accumu
         rec = dict(fn=fn, kind=ops._KIND[layer], a=[[B, H, H, Cin], _dt(a16)], cvec=Cc, g=[[B, Ho, Ho, N], _dt(g16)],
                    grad_shape=[N, Cin + Cc, k, k] if k > 1 else [N, Cin + Cc], swap=0, fold=0)
     rec.update(out=bool(out or accumulate or i_off), accumulate=accumulate, i_off=i_off, I_total=i_off + Cin if i_off else 0)
+    if direct:
+        rec["direct"] = True
     return _extra(rec, why, reach, 0, tune)
 
 
@@ -173,27 +194,31 @@ def _table():
                    ["single-partial-tile", "rowtail-128x64"]))
     # ---- fp32 weight gradient ----------------------------------------------------------------------------------------
     t.append(wgrad("k3s1", 5, 4, 160, 64, "M = 80: chunks of 32 + 32 + 16 pixels; 128 x 64 tile; K = 1440 (tail 32)",
-                   ["wg-pixtail-128x64"]))
-    t.append(wgrad("k3s1", 3, 4, 40, 136, "M = 48, K = 360, N = 136: pixel, K and column tails together", ["wg-pixtail-128x128"]))
+                   ["wg-pixtail-128x64", FIN + "rt2-direct"]))
+    t.append(wgrad("k3s1", 3, 4, 40, 136, "M = 48, K = 360, N = 136: pixel, K and column tails together",
+                   ["wg-pixtail-128x128", FIN + "rt1-direct-ctail"]))
     for bm, f in ((128, "wg-pixtail-128x128"), (256, "wg-pixtail-256x128")):
-        t.append(wgrad("k4s2", 5, 8, 64, 128, "M = 80, K = 1024", [f], tune=dict(wgrad_bm=bm)))
+        t.append(wgrad("k4s2", 5, 8, 64, 128, "M = 80, K = 1024", [f, FIN + "rt2-direct"], tune=dict(wgrad_bm=bm)))
     for bm, f in ((128, "wg-pixtail-128x128"), (256, "wg-pixtail-256x128"), (512, "wg-pixtail-256x256")):
-        t.append(wgrad("k3s1", 7, 4, 256, 512, "M = 112, K = 2304, N = 512", [f], tune=dict(wgrad_bm=bm)))
-    t.append(wgrad("k4s2", 1, 8, 4, 64, "the first discriminator conv's 64-row tile at one image, M = 16", ["wg-pixtail-64x64"]))
-    t.append(wgrad("k3s1", 5, 8, 32, 64, "K = 288 on 96 x 64 tiles, M = 320", []))
-    t.append(wgrad("k3s1", 5, 4, 32, 64, "K = 288 on 96 x 64 tiles, M = 80", ["wg-pixtail-96x64"]))
-    t.append(wgrad("k3s1", 5, 8, 32, 32, "K = 288 on 96 x 32 tiles, M = 320", []))
-    t.append(wgrad("k3s1", 3, 4, 32, 32, "K = 288 on 96 x 32 tiles, M = 48", ["wg-pixtail-96x32"]))
+        t.append(wgrad("k3s1", 7, 4, 256, 512, "M = 112, K = 2304, N = 512", [f, FIN + "rt8-direct"], tune=dict(wgrad_bm=bm)))
+    t.append(wgrad("k4s2", 1, 8, 4, 64, "the first discriminator conv's 64-row tile at one image, M = 16",
+                   ["wg-pixtail-64x64", FIN + "rt1-direct"]))
+    t.append(wgrad("k3s1", 5, 8, 32, 64, "K = 288 on 96 x 64 tiles, M = 320", [FIN + "rt1-direct"]))
+    t.append(wgrad("k3s1", 5, 4, 32, 64, "K = 288 on 96 x 64 tiles, M = 80", ["wg-pixtail-96x64", FIN + "rt1-direct"]))
+    t.append(wgrad("k3s1", 5, 8, 32, 32, "K = 288 on 96 x 32 tiles, M = 320", [FIN + "rt1-direct"]))
+    t.append(wgrad("k3s1", 3, 4, 32, 32, "K = 288 on 96 x 32 tiles, M = 48", ["wg-pixtail-96x32", FIN + "rt1-direct"]))
     t.append(wgrad("k1", 5, 1, 100, 2048, "the fc's weight gradient at batch 5: one chunk of 5 pixels, broadcast vector",
-                   ["wg-pixtail-128x128"], Cc=128))
-    t.append(wgrad("k3s1", 3, 32, 32, 64, "row-segment kernel, W = 32, 3 images", ["wg-rows3-odd-batch"]))
-    t.append(wgrad("k3s1", 3, 32, 64, 128, "row-segment kernel, 64 -> 128 channels, W = 32, 3 images", ["wg-rows3-odd-batch"]))
+                   ["wg-pixtail-128x128", FIN + "rt8-direct"], Cc=128))
+    t.append(wgrad("k3s1", 3, 32, 32, 64, "row-segment kernel, W = 32, 3 images", ["wg-rows3-odd-batch", FIN + "rt1-stream"]))
+    t.append(wgrad("k3s1", 3, 32, 64, 128, "row-segment kernel, 64 -> 128 channels, W = 32, 3 images",
+                   ["wg-rows3-odd-batch", FIN + "rt2-stream"]))
     t.append(wgrad("up", 5, 4, 64, 128, "up-block weight gradient (swap, 4x4 taps folded to 3x3), M = 80, K = 2048",
-                   ["wg-pixtail-128x64"]))
-    t.append(wgrad("k3s1", 5, 4, 160, 64, "M = 80, accumulated into a prefilled gradient", ["wg-pixtail-128x64"], accumulate=True))
+                   ["wg-pixtail-128x64", FIN + "rt2-direct-swap"]))
+    t.append(wgrad("k3s1", 5, 4, 160, 64, "M = 80, accumulated into a prefilled gradient", ["wg-pixtail-128x64", FIN + "rt2-direct"],
+                   accumulate=True))
     t.append(wgrad("k3s1", 3, 4, 40, 136, "M = 48, written into input channels [32, 72) of a wider tensor",
-                   ["wg-pixtail-128x128"], i_off=32))
-    t.append(wgrad("k4s2", 5, 8, 64, 128, "M = 80, 256 x 128 tile, accumulated into a slice", ["wg-pixtail-256x128"],
+                   ["wg-pixtail-128x128", FIN + "rt1-direct-ctail"], i_off=32))
+    t.append(wgrad("k4s2", 5, 8, 64, 128, "M = 80, 256 x 128 tile, accumulated into a slice", ["wg-pixtail-256x128", FIN + "rt2-direct"],
                    accumulate=True, i_off=8, tune=dict(wgrad_bm=256)))
     # ---- bf16 --------------------------------------------------------------------------------------------------------
     t.append(fwd("k3s1", 5, 4, 256, 512, "4x4 maps: a 128-pixel tile spans 8 images, the batch has 5", ["b16-ragged-128", "b16-tb>1"],
@@ -217,15 +242,91 @@ def _table():
                    bf16=True, tune=v2))
     for bm in (128, 256, 512):
         t.append(wgrad("k3s1", 5, 4, 256, 256, "bf16 x bf16, M = 80: a 64-pixel stage and a 16-pixel one",
-                       ["b16-wg-stagetail"], a16=True, g16=True, tune=dict(wgrad16_bm=bm)))
-        t.append(wgrad("k3s1", 3, 4, 256, 256, "bf16 x bf16, M = 48: less than one stage", ["b16-wg-stagetail"], a16=True,
-                       g16=True, tune=dict(wgrad16_bm=bm)))
-    t.append(wgrad("k4s2", 5, 8, 64, 128, "bf16 x bf16 stride-2, M = 80, accumulated", ["b16-wg-stagetail"], a16=True,
+                       ["b16-wg-stagetail", FIN + "rt8-direct"], a16=True, g16=True, tune=dict(wgrad16_bm=bm)))
+        t.append(wgrad("k3s1", 3, 4, 256, 256, "bf16 x bf16, M = 48: less than one stage", ["b16-wg-stagetail", FIN + "rt8-direct"],
+                       a16=True, g16=True, tune=dict(wgrad16_bm=bm)))
+    t.append(wgrad("k4s2", 5, 8, 64, 128, "bf16 x bf16 stride-2, M = 80, accumulated", ["b16-wg-stagetail", FIN + "rt2-direct"], a16=True,
                    g16=True, accumulate=True))
-    t.append(wgrad("up", 5, 4, 64, 128, "bf16 x bf16 up-block (swap, fold), M = 80", ["b16-wg-stagetail"], a16=True, g16=True))
+    t.append(wgrad("up", 5, 4, 64, 128, "bf16 x bf16 up-block (swap, fold), M = 80", ["b16-wg-stagetail", FIN + "rt2-direct-swap"],
+                   a16=True, g16=True))
     t.append(wgrad("k4s2", 5, 8, 4, 64, "the first discriminator conv in bf16 mode: fp32 NHWC4 image x bf16 gradient, M = 80",
-                   ["b16-wg-stagetail"], g16=True))
+                   ["b16-wg-stagetail", FIN + "rt1-direct"], g16=True))
     t += _bf16_branches(v2)
+    t += _wgrad_branches()
+    return t
+
+
+def _wgrad_branches():
+    """The branches of plan_wgrad and the finishing paths of launch_wgrad that no production shape and no row above takes,
+    each at the smallest shape that still takes it: the 128-thread row-segment kernel rows3-64x32 (never run before), the
+    row-segment kernels off the census batches and with a column tail, the pixel tail of f32-128x32, a short last pixel
+    split on the tiles that only ever ran whole ones, bf16 operands on the fp32-MFMA kernel, every (rows per tile, slab sum)
+    pair of the OIHW finish that was missing.  direct=True: tests/test_conv_edges_gpu.py also calls s2i_conv_wgrad(_dt) itself
+    with ldg = N + 8, the workspace of exactly s2i_wgrad_workspace_bytes(_dt) and the gradient each between sentinels."""
+    t = []
+
+    def w(*a, **k):
+        t.append(wgrad(*a, **k))
+
+    odd = "wg-rows3-odd-batch"
+    # ---- row-segment kernels -------------------------------------------------------------------------------------------
+    w("k3s1", 3, 32, 64, 32, "rows3-64x32 (never run): 128 threads, HPASS = 5, BPASS = 2; 24 slabs", [odd, FIN + "rt1-stream"], direct=True)
+    w("k3s1", 3, 64, 64, 32, "rows3-64x32, W = 64: two chunks per image row, the left halo of the second is a real pixel; "
+      "96 slabs, tree sum", [odd, FIN + "rt1-tree"])
+    w("k3s1", 1, 32, 64, 32, "rows3-64x32, one image", [FIN + "rt1-stream"])
+    w("k3s1", 9, 64, 64, 32, "rows3-64x32, 1152 chunks as 231 slabs of 5, the last of 2",
+      [odd, "wg-short-last-split-rows3", FIN + "rt1-tree"], direct=True)
+    w("k3s1", 3, 32, 32, 32, "rows3-32x32 off the census batches", [odd, FIN + "rt1-stream"])
+    w("k3s1", 3, 32, 64, 64, "rows3-64x64 off the census batches", [odd, FIN + "rt1-stream"])
+    w("k3s1", 3, 32, 32, 96, "rows3-32x64, gy = 2: the second column block half filled", [odd, "wg-rows3-coltail", FIN + "rt1-stream"])
+    w("k3s1", 3, 32, 64, 96, "rows3-64x128 with 96 of 128 columns", [odd, "wg-rows3-coltail", FIN + "rt1-stream"])
+    w("k3s1", 3, 32, 64, 32, "rows3-64x32 accumulated into input channels [8, 72) of a prefilled tensor", [odd, FIN + "rt1-stream"],
+      accumulate=True, i_off=8, direct=True)
+    # ---- f32-128x32 ----------------------------------------------------------------------------------------------------
+    w("k3s1", 3, 4, 40, 32, "f32-128x32, M = 48: pixel tail (and K = 360: K tail)", ["wg-pixtail-128x32", FIN + "rt1-direct"])
+    w("k3s1", 5, 4, 40, 24, "f32-128x32, M = 80, 24 of 32 columns", ["wg-pixtail-128x32", FIN + "rt1-direct-ctail"])
+    w("k3s1", 11, 8, 40, 32, "f32-128x32, 22 chunks as 5 + 5 + 5 + 5 + 2", ["wg-short-last-split-128x32", FIN + "rt1-stream"], direct=True)
+    # ---- a short last pixel split on the other tiles: 22 chunks in 5 slabs ------------------------------------------------
+    w("k3s1", 11, 8, 32, 64, "f32-96x64, 22 chunks as 5 + 5 + 5 + 5 + 2", ["wg-short-last-split-96x64", FIN + "rt1-stream"])
+    w("k3s1", 11, 8, 32, 32, "f32-96x32, 22 chunks as 5 + 5 + 5 + 5 + 2", ["wg-short-last-split-96x32", FIN + "rt1-stream"])
+    w("k4s2", 11, 16, 64, 128, "f32-256x128, 22 chunks as 5 + 5 + 5 + 5 + 2", ["wg-short-last-split-256x128", FIN + "rt2-stream"],
+      tune=dict(wgrad_bm=256))
+    w("k3s1", 11, 8, 256, 256, "f32-256x256, 22 chunks as 5 + 5 + 5 + 5 + 2", ["wg-short-last-split-256x256", FIN + "rt8-stream"],
+      tune=dict(wgrad_bm=512), direct=True)
+    # ---- bf16 operands on the fp32-MFMA kernel ---------------------------------------------------------------------------
+    A, G, AG = "wg-16-on-f32-a", "wg-16-on-f32-g", "wg-16-on-f32-ag"
+    w("k3s1", 5, 4, 64, 128, "bf16 a x fp32 g on f32-128x128", [A, "wg-pixtail-128x128", FIN + "rt2-direct"], a16=True)
+    w("k3s1", 5, 4, 64, 64, "fp32 a x bf16 g on f32-128x64", [G, "wg-pixtail-128x64", FIN + "rt1-direct"], g16=True)
+    w("k3s1", 5, 4, 64, 36, "both bf16, N % 8 != 0 keeps them off the bf16 cores: f32-128x64 with 36 of 64 columns",
+      [AG, "wg-pixtail-128x64", FIN + "rt1-direct-ctail"], a16=True, g16=True, direct=True)
+    w("k3s1", 5, 4, 36, 128, "both bf16, Cin % 8 != 0: f32-128x128, K = 324 (K tail)", [AG, "wg-pixtail-128x128", FIN + "rt1-direct"],
+      a16=True, g16=True)
+    w("k4s2", 5, 8, 4, 72, "the first discriminator conv's shape with N = 72 > 64: not b16d1 but f32-128x128, fp32 image x bf16 "
+      "gradient", [G, "wg-pixtail-128x128", FIN + "rt1-direct-ctail"], g16=True)
+    w("k3s1", 3, 32, 32, 64, "a row-segment shape that a bf16 a keeps off that kernel: f32-128x64, 24 slabs", [A, FIN + "rt1-stream"],
+      a16=True)
+    w("up", 5, 4, 64, 128, "up block (swap, fold) with a bf16 layer input, which the swap makes the GEMM's g: f32-128x64",
+      [G, "wg-pixtail-128x64", FIN + "rt2-direct-swap"], a16=True)
+    w("k1", 3, 4, 64, 64, "bf16 a x fp32 g on f32-64x64", [A, "wg-pixtail-64x64", FIN + "rt1-direct"], a16=True)
+    w("k1", 3, 4, 64, 36, "both bf16 on f32-64x64 with 36 of 64 columns", [AG, "wg-pixtail-64x64", FIN + "rt1-direct-ctail"], a16=True,
+      g16=True)
+    w("k3s1", 5, 4, 64, 20, "both bf16 on f32-128x32 with 20 of 32 columns", [AG, "wg-pixtail-128x32", FIN + "rt1-direct-ctail"], a16=True,
+      g16=True)
+    # ---- finishing paths of launch_wgrad -----------------------------------------------------------------------------------
+    w("k1", 5, 4, 160, 128, "RT = 4 from one slab", ["wg-pixtail-128x128", FIN + "rt4-direct"])
+    w("k1", 11, 8, 160, 128, "RT = 4 after slab_sum_kernel (5 slabs, the last of 2 chunks)",
+      ["wg-short-last-split-128x128", FIN + "rt4-stream"], direct=True)
+    w("k1", 11, 8, 640, 200, "RT = 8 with 8 of 32 columns in the last block, after slab_sum_kernel", ["wg-short-last-split-128x128",
+                                                                                                      FIN + "rt8-stream-ctail"])
+    w("up", 11, 8, 72, 136, "swap + fold with a column tail (72 input channels) after slab_sum_kernel", ["wg-short-last-split-128x128",
+                                                                                                         FIN + "rt2-stream-ctail-swap"])
+    w("k4s2", 8, 64, 4, 64, "64 slabs, tree sum, accumulated into a prefilled gradient", [FIN + "rt1-tree"], accumulate=True, direct=True)
+    w("k1", 9, 32, 64, 36, "72 slabs, tree sum, into input channels [4, 68) of a wider tensor, 4 of 32 columns in the last block",
+      [FIN + "rt1-tree-ctail"], i_off=4)
+    w("k3s1", 5, 16, 40, 136, "10 slabs, stream sum, overwriting a prefilled tensor", [FIN + "rt1-stream-ctail"], out=True)
+    # ---- bf16 cores: the 64-pixel re-cut of the 32-pixel split ------------------------------------------------------------
+    w("k1", 9, 8, 32, 32, "b16-128x32, M = 576: the workspace holds 4 slabs (18 chunks of 32 pixels), the 9 stages of 64 fill 3",
+      ["b16-wg-recut-fewer-slabs", "b16-wg-split-overwrite", FIN + "rt1-stream"], a16=True, g16=True, direct=True)
     return t
 
 
@@ -308,11 +409,12 @@ def _bf16_branches(v2):
     f("k3s1", 6, 8, 256, 72, "3 groups of 2 images, 8 K splits, N = 72: the reduction's rows per group", [gm, tb, ct], groups=3, direct=True)
     f("k3s1", 8, 8, 256, 128, "v2-k3s1: 2 groups of 4 images, 4 K splits", [gm, tb, "b16-v2-split"], groups=2, tune=v2)
     # ---- bf16 weight gradient ----------------------------------------------------------------------------------------
-    w("k1", 3, 4, 64, 64, "b16-64x64 (never run), M = 48: less than one stage", ["b16-wg-stagetail"])
-    w("k1", 3, 8, 32, 40, "b16-64x64 with 40 of 64 columns", [])
-    w("k1", 1, 16, 32, 40, "b16-64x64, 2 slabs summed into a prefilled gradient it overwrites", ["b16-wg-split-overwrite"], out=True)
+    w("k1", 3, 4, 64, 64, "b16-64x64 (never run), M = 48: less than one stage", ["b16-wg-stagetail", FIN + "rt1-direct"])
+    w("k1", 3, 8, 32, 40, "b16-64x64 with 40 of 64 columns", [FIN + "rt1-direct-ctail"])
+    w("k1", 1, 16, 32, 40, "b16-64x64, 2 slabs summed into a prefilled gradient it overwrites",
+      ["b16-wg-split-overwrite", FIN + "rt1-direct-ctail"], out=True)
     w("k3s1", 1, 16, 32, 32, "b16-128x32, 2 slabs summed into input channels [32, 64) of a wider tensor",
-      ["b16-wg-split-overwrite"], i_off=32)
+      ["b16-wg-split-overwrite", FIN + "rt1-direct"], i_off=32)
     return t
 
 
@@ -449,9 +551,11 @@ def _bf16_plan(rec, M, nph):
                 gx=gx, kernel=told["kernel"], npad=told["npad"], parts=told["parts"], ws_bytes=told["ws_bytes"], reach=reach)
 
 
-def wgrad_plan(rec):
-    """dict(M, K, N, tile, rows3, splitk, reach) from what s2i_wgrad_plan_query says: the tile is its (bm, bn), the row-segment
-    and bf16 families are in the kernel's name, the pixel / stage tail is M % stage."""
+def wgrad_plan(rec, table=True):
+    """dict(M, K, N, tile, rows3, splitk, kernel, family, stage, nchunks, cps, slabs, ws_slabs, bn, threads, reach) from what
+    s2i_wgrad_plan_query says: the tile is its (bm, bn), the row-segment and bf16 families are in the kernel's name, the pixel /
+    stage tail is M % stage, a short last split nchunks % cps behind more than one slab; the finish tag is wgrad_finish's.
+    table=False: a census record, which pins no tile."""
     import ctypes
     from speech_to_image_translation_without_text_amd import _lib
     lib = _lib.load()
@@ -469,22 +573,98 @@ def wgrad_plan(rec):
         told = _lib.wgrad_plan(d, int(a16), int(g16))
     assert ws > 0 and ws == told["ws_slabs"] * K * N * 4 and (told["K"], told["M"]) == (K, M), (ws, told, lib.s2i_last_error())
     # the record itself: where the cost model may pick any of the 128- / 256-row fp32 tiles, the record pins one
-    if told["kernel"] in ("f32-128x128", "f32-256x128", "f32-256x256") and K % 256 == 0:
+    if table and told["kernel"] in ("f32-128x128", "f32-256x128", "f32-256x256") and K % 256 == 0:
         assert tune.get("wgrad_bm"), "a weight gradient that may take the 256-row tiles needs wgrad_bm set: %r" % (rec,)
     family = told["kernel"].split("-")[0]
     tile, rows3 = (told["bm"], told["bn"]), family == "rows3"
-    reach = set()
+    # the pixel range in stages, and the stages per slab that cut it into told["slabs"] slabs (the query does not name cps:
+    # every split the planner's search keeps satisfies cdiv(nchunks, cdiv(nchunks, split)) == split, the bf16 re-cut divides
+    # by the workspace's slab count)
+    nchunks = -(-M // told["stage"])
+    cps = -(-nchunks // (told["ws_slabs"] if family in ("b16", "b16d1") else told["slabs"]))
+    assert -(-nchunks // cps) == told["slabs"] == told["gz"] or family == "smalln", told
+    reach = {wgrad_finish(d, told)}
     if family in ("b16", "b16d1"):
         if M % told["stage"]:
             reach.add("b16-wg-stagetail")
         if told["ws_slabs"] > 1 and not rec["accumulate"]:
             reach.add("b16-wg-split-overwrite")
+        if told["slabs"] < told["ws_slabs"]:
+            reach.add("b16-wg-recut-fewer-slabs")
     elif rows3:
         if B & (B - 1):
             reach.add("wg-rows3-odd-batch")
+        if N % told["bn"]:
+            reach.add("wg-rows3-coltail")
     elif M % told["stage"]:
         reach.add("wg-pixtail-%dx%d" % tile)
-    return dict(M=M, K=K, N=N, tile=tile, rows3=rows3, splitk=told["ws_slabs"], kernel=told["kernel"], reach=reach)
+    if family in ("f32", "rows3") and told["slabs"] > 1 and nchunks % cps:
+        reach.add("wg-short-last-split-" + ("rows3" if rows3 else "%dx%d" % tile))
+    if family == "f32" and (a16 or g16):
+        reach.add("wg-16-on-f32-" + "a" * a16 + "g" * g16)
+    return dict(M=M, K=K, N=N, tile=tile, rows3=rows3, splitk=told["ws_slabs"], kernel=told["kernel"], reach=reach, family=family,
+                stage=told["stage"], nchunks=nchunks, cps=cps, slabs=told["slabs"], ws_slabs=told["ws_slabs"], bn=told["bn"],
+                threads=told["threads"])
+
+
+def wgrad_finish(d, told):
+    """The REACH tag of the finish launch_wgrad (csrc/s2i_wgrad.hip) runs behind the kernel of plan `told`.  The plan query
+    does not export this rule, so it is restated here once, as the test side's oracle: the OIHW transpose takes the largest
+    RT in 8, 4, 2, 1 rows per tile that leaves 128 blocks of 32 columns x RT rows (RT = 1 if none does); 32 or more slabs of
+    fewer than 2^20 elements (and the stream kernels) are summed by slab_sum_tree_kernel first, else 3 or more by
+    slab_sum_kernel, else the transpose sums them itself."""
+    ncols, nrows = (d.I, d.O) if d.swap else (d.O, d.I)
+    rt = 8
+    while rt > 1 and -(-ncols // 32) * -(-nrows // rt) < 128:
+        rt >>= 1
+    S, kn = told["slabs"], told["K"] * d.N
+    tree = told["kernel"].startswith("smalln") or (S >= 32 and kn % 4 == 0 and kn // 4 < (1 << 18))
+    path = "tree" if tree else ("stream" if S > 2 and kn % 4 == 0 else "direct")
+    return "%srt%d-%s%s%s" % (FIN, rt, path, "-ctail" if ncols % 32 else "", "-swap" if d.swap else "")
+
+
+def wgrad_mutants(rec, plan, a, g, dw, true=None):
+    """{name: gradient} of the wrong references the branches of `plan` (wgrad_plan) call for, each what a kernel that goes
+    wrong on that branch would produce, accumulation order set aside.  a, g: the fp64 NCHW operands of rec["a"], rec["g"];
+    dw(a=, g=) the fp64 gradient of the record with an operand replaced (conv_replay.wgrad_dw); true = dw().  Built from the
+    reference alone, so tests/test_conv_edges_cpu.py can hold every one of them against the bound without a GPU."""
+    import torch
+    true = dw() if true is None else true
+    reach, out = plan["reach"], {}
+    B, _, Ho, Wo = g.shape                       # the GEMM's pixels are the rows of g, under swap too
+    M, stage = plan["M"], plan["stage"]
+    assert M == B * Ho * Wo, (plan, g.shape)
+
+    def without(m0):
+        return dw(g=g * (torch.arange(M, device=g.device) < m0).view(B, 1, Ho, Wo))
+
+    def bf16(t):
+        return t.float().bfloat16().double()
+
+    if M % stage:
+        out["pixel tail: the pixels of the last chunk dropped"] = without((plan["nchunks"] - 1) * stage)
+    if plan["slabs"] > 1:
+        out["slabs: the last pixel split not summed"] = without((plan["slabs"] - 1) * plan["cps"] * stage)
+    finish = [f for f in reach if f.startswith(FIN)][0]
+    if rec["g"][0][3] % plan["bn"] or "-ctail" in finish:
+        m = true.clone()
+        (m[:, -1] if rec["swap"] else m[-1]).zero_()
+        out["column tail: the last valid column not written"] = m
+    if plan["rows3"]:
+        am = a.clone()
+        am[:, :, 0] = 0
+        out["row segment: input row 0 read as padding"] = dw(a=am)
+        if a.shape[3] > 32:
+            am = a.clone()
+            am[:, :, :, 32] = 0
+            out["row segment: the first pixel of the second chunk of a row read as padding"] = dw(a=am)
+    if "wg-16-on-f32-a" in reach:
+        out["bf16 a: the fp32 g rounded to bf16 too"] = dw(g=bf16(g))
+    if "wg-16-on-f32-g" in reach:
+        out["bf16 g: the fp32 a rounded to bf16 too"] = dw(a=bf16(a))
+    if "-swap" in finish:
+        out["swap + fold: ky and kx exchanged"] = true.transpose(2, 3)
+    return out
 
 
 def plan(rec):

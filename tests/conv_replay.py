@@ -236,18 +236,73 @@ def replay_conv(rec, gen, dev, what, ledger, extra=None, *, weights="dyadic", op
     assert sees_channel, "%s: the bound cannot see one input channel's contribution" % what
 
 
+def wgrad_family(rec):
+    """The family of the kernel plan_wgrad names for this launch under the knobs in force ("f32", "rows3", "b16", "b16d1",
+    "split", "smalln"): the first part of its _lib.WGRAD_KERNELS name, asked of s2i_wgrad_plan_query."""
+    from speech_to_image_translation_without_text_amd import _lib, ops
+    B, H, W, Ca = rec["a"][0]
+    N, gs = rec["g"][0][3], rec["grad_shape"]
+    O, I, KH, KW = gs if len(gs) == 4 else (gs[0], gs[1], 1, 1)
+    d = _lib.WgradDesc(rec["kind"], B, H, W, Ca, rec["cvec"], N, N, rec["swap"], rec["fold"], O, I, KH, KW, int(rec["accumulate"]),
+                       rec["i_off"], rec["I_total"], 0, 0)
+    a16, g16 = rec["a"][1] == "bf16", rec["g"][1] == "bf16"
+    told = _lib.wgrad_plan(d, int(a16), int(g16), 0 if (a16 or g16) else ops.MATH_PLANES)
+    assert told is not None, (_lib.load().s2i_last_error(), rec)
+    return told["kernel"].split("-")[0]
+
+
+def wgrad_on_f32(rec):
+    """The launch runs on the fp32 matrix cores (f32-*, rows3-*): a bf16 operand is converted up as it is staged, an fp32
+    operand is read whole, and the bound is that of the fp32 class whatever the operands' storage."""
+    return wgrad_family(rec) in ("f32", "rows3")
+
+
+def wgrad_dw(rec, layer, ad, gd, cd=None):
+    """dw(absval, channel, image, a=, g=): the fp64 weight gradient of record rec from its fp64 NCHW operands ad, gd (and the
+    broadcast vector cd), in rec["grad_shape"]; of |a| and |g|; with the last input channel or the last image removed; with
+    an operand replaced."""
+    gs = rec["grad_shape"]
+    O, I = gs[0], gs[1]
+    kh = gs[2] if len(gs) == 4 else 1
+    B = ad.shape[0]
+
+    def dw(absval=False, channel=False, image=False, a=None, g=None):
+        A, G = ad if a is None else a, gd if g is None else g
+        if rec["swap"]:
+            X, dy = G[:, :I], A[:, :O]
+        else:
+            X = A if cd is None else torch.cat((cd.view(B, -1, 1, 1).expand(-1, -1, A.shape[2], A.shape[3]), A), 1)
+            X, dy = X[:, :I], G[:, :O]
+        if absval:
+            X, dy = X.abs(), dy.abs()
+        if channel or image:
+            X = X.clone()
+            if channel:
+                X[:, -1] = 0
+            if image:
+                X[-1] = 0
+        r = R.wgrad(layer, X, dy, kh)
+        return r.view(O, I) if len(gs) == 2 else r
+    return dw
+
+
 def replay_wgrad(rec, gen, dev, what, ledger, extra=None, *, operands=None, cls=None):
     """extra(ctx), if given, runs before the assertions, as in replay_conv, and returns a list of failure messages;
-    operands = dict(a=, g=, cvec=) and cls as in replay_conv."""
+    operands = dict(a=, g=, cvec=) and cls as in replay_conv.  Without cls the class of the bound follows the kernel family
+    the plan names: "fp32/wgrad" on f32-* and rows3-*, also where they read a bf16 operand; elsewhere "bf16/wgrad" with a
+    bf16 operand (b16-*, b16d1-*, the stream kernels on a bf16 input) and "fp32/wgrad" without."""
     from speech_to_image_translation_without_text_amd import ops
     given = operands or {}
     op, layer = R.layer_op(rec)
     a = given["a"] if "a" in given else _operand(rec["a"], gen, dev)
     g = given["g"] if "g" in given else _operand(rec["g"], gen, dev)
-    # one bf16 operand (the first discriminator conv's fp32 image x its bf16 output gradient): the launch runs on the bf16
-    # matrix cores and reads the fp32 operand as bf16, so that operand is drawn on the bf16 grid
+    # one bf16 operand on the bf16 matrix cores (b16d1-64x64: the first discriminator conv's fp32 image x its bf16 output
+    # gradient): the kernel reads the fp32 operand as bf16, so that operand is drawn on the bf16 grid.  An f32-* kernel
+    # converts the bf16 operand up, and the fp32 one keeps its full significand: a kernel that truncated it would show.
     mixed = a.dtype != g.dtype
-    if mixed:
+    any16 = torch.bfloat16 in (a.dtype, g.dtype)
+    on_f32 = wgrad_on_f32(rec)
+    if mixed and not on_f32:
         a, g = [t if t.dtype == torch.bfloat16 else t.bfloat16().float() for t in (a, g)]
     B = a.shape[0]
     cvec = torch.randn((B, rec["cvec"]), generator=gen, device=dev) if rec["cvec"] else None
@@ -272,31 +327,16 @@ def replay_wgrad(rec, gen, dev, what, ledger, extra=None, *, operands=None, cls=
     ad, gd = _nchw(a), _nchw(g)
     cd = None if cvec is None else cvec.double()
 
-    def dw(absval=False, channel=False, image=False):
-        if rec["swap"]:
-            X, dy = gd[:, :I], ad[:, :O]
-        else:
-            X = ad if cd is None else torch.cat((cd.view(B, -1, 1, 1).expand(-1, -1, ad.shape[2], ad.shape[3]), ad), 1)
-            X, dy = X[:, :I], gd[:, :O]
-        if absval:
-            X, dy = X.abs(), dy.abs()
-        if channel or image:
-            X = X.clone()
-            if channel:
-                X[:, -1] = 0
-            if image:
-                X[-1] = 0
-        r = R.wgrad(layer, X, dy, kh)
-        return r.view(O, I) if len(gs) == 2 else r
-
+    dw = wgrad_dw(rec, layer, ad, gd, cd)
     resd = res.double()
     sl = (slice(None), slice(i_off, i_off + I)) if I_total else (slice(None),)
     got = resd[sl]
     base = prefill.double()[sl] if rec["accumulate"] else 0.0
-    ref = base + dw()
+    true = dw()
+    ref = base + true
     absref = dw(absval=True)
     rnd = 2 * LH.U if rec["accumulate"] else 0.0      # the one rounding of prefill + gradient
-    cls = cls or ("bf16" if (mixed or a.dtype == torch.bfloat16) else "fp32") + "/wgrad"
+    cls = cls or ("bf16" if any16 and not on_f32 else "fp32") + "/wgrad"
     gamma = GAMMA[cls]
     ratio, ok = LH.compare(got, ref, absref, rnd, gamma)
     ledger.note(cls, ratio, what, gamma)
@@ -309,7 +349,7 @@ def replay_wgrad(rec, gen, dev, what, ledger, extra=None, *, operands=None, cls=
     sees_channel = LH.fails(got, base + dw(channel=True), absref, rnd, gamma)
     sees_image = LH.fails(got, base + dw(image=True), absref, rnd, gamma)
     more = [] if extra is None else extra(dict(rec=rec, layer=layer, a=ad, g=gd, kh=kh, got=got, base=base, ref=ref, absref=absref,
-                                               rnd=rnd, gamma=gamma, ratio=ratio, cls=cls))
+                                               rnd=rnd, gamma=gamma, ratio=ratio, cls=cls, dw=dw, true=true))
     assert ok, "%s: element error %.3e x absref > gamma %.3e" % (what, ratio, gamma)
     assert not more, "%s: %s" % (what, "; ".join(more))
     assert untouched_ok, "%s: elements outside input channels [%d, %d) changed" % (what, i_off, i_off + I)

@@ -17,7 +17,6 @@ import conv_edges as E
 from speech_to_image_translation_without_text_amd import _lib, ops
 
 REACH = E.REACH + (
-    "wg-pixtail-128x32",      # weight gradient: the pixel range ends on a short 32-pixel chunk on the 128 x 32 tile
     "wg-ktail",               # K = taps x channels is no multiple of the tile's K rows
     "wg-coltail",             # N is no multiple of the tile's columns
     "wg-short-last-split",    # the pixel range is split and the last split has fewer chunks than the others

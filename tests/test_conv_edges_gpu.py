@@ -25,9 +25,9 @@ Measured on one MI355X (worst ratio per class: edge table | ragged census | prod
 conv_replay.py; bound):
 
     fp32 forward / input gradient   3.3e-7 | 4.2e-7 | 4.8e-7   (2^-20 = 9.5e-7)
-    fp32 weight gradient            3.2e-7 | 4.1e-7 | 4.0e-7   (8e-7)
+    fp32 weight gradient            2.8e-7 | 4.1e-7 | 4.0e-7   (8e-7)
     bf16 forward / input gradient   1.1e-9 | 3.4e-8 | 5.1e-8   (1e-7)
-    bf16 weight gradient            1.2e-7 | 1.2e-7 | 1.6e-7   (3.2e-7)
+    bf16 weight gradient            1.4e-7 | 1.2e-7 | 1.6e-7   (3.2e-7)
     BatchNorm partial sums          1.1e-7 | 6.0e-8 | 7.4e-8   (1.5e-7)
 
 No class needed a wider bound.  The partial sums' worst edge ratio is the fc layer at batch 5 (five rows per column: the
@@ -78,6 +78,60 @@ absref) and nothing else did; the census replays cannot see it (one image per ti
 
 Wall time of this module on one MI355X: the 204 tests of the parent commit 11.5 s, all 269 tests 10.9 to 11.7 s (the
 6 s census step dominates and varies more than the 65 new tests take together, under 2 s).
+
+The branches of the weight-gradient planner (plan_wgrad) and the finishing paths of launch_wgrad
+---------------------------------------------------------------------------------------------
+tests/conv_edges.py::_wgrad_branches adds 34 records (rows 124 to 157), each the smallest shape that takes its branch.
+tests/test_conv_edges_cpu.py derives every tag from s2i_wgrad_plan_query (the finish tag from conv_edges.wgrad_finish, the
+one rule the query does not export), asserts that every name of _lib.WGRAD_KERNELS but f32in-128x128 is the plan of a
+replayed record, and that no census record reaches what the rows add.  They run through the same replay, constants
+unchanged; replay_wgrad takes the class from the kernel family (f32-* and rows3-* are "fp32/wgrad" whatever the operands'
+storage) and leaves the fp32 operand of a mixed launch on an f32-* kernel its full significand.  The extra hook holds every
+weight-gradient record of the table, old and new, against the wrong references of conv_edges.wgrad_mutants, one per branch
+its plan takes; tests/test_conv_edges_cpu.py shows without a GPU that each lies outside the bound of the true gradient.
+Measured on one MI355X, records of the whole table per tag | worst ratio (bound 8e-7):
+
+    rows3-64x32 (5 records: W = 32 and 64, 1, 3 and 9 images, 8 / 24 / 96 / 231 slabs, accumulated into a slice)
+                                          5 | 5.0e-8
+    wg-rows3-odd-batch                   10 | 3.5e-8    (each of the five instantiations off the census batches)
+    wg-rows3-coltail                      2 | 3.1e-8    (rows3-32x64 with gy = 2, rows3-64x128 with 96 of 128 columns)
+    wg-short-last-split-rows3             1 | 7.6e-9
+    wg-pixtail-128x32                     3 | 2.3e-7
+    wg-short-last-split-128x32 / -96x64 / -96x32 / -256x128 / -256x256 / -128x128
+                              1 / 1 / 1 / 1 / 1 / 3 | 6.4e-8 / 7.1e-8 / 7.8e-8 / 8.6e-8 / 1.0e-7 / 8.9e-8
+    wg-16-on-f32-a / -g / -ag     3 / 3 / 4 | 2.7e-7 / 2.1e-7 / 1.2e-7
+    wg-finish-rt4-direct / rt4-stream 1 / 1 | 2.2e-7 / 6.6e-8
+    wg-finish-rt8-stream / rt8-stream-ctail / rt2-stream-ctail-swap / rt1-stream-ctail
+                              1 / 1 / 1 / 1 | 1.0e-7 / 8.9e-8 / 3.7e-8 / 4.4e-8
+    wg-finish-rt1-tree / rt1-tree-ctail (accumulated; into a slice)
+                                      3 / 1 | 1.2e-8 / 1.3e-8
+    b16-wg-recut-fewer-slabs              1 | 2.0e-8    (bound 3.2e-7)
+
+The other finish tags (rt1 / rt2 / rt8 direct, rt1 / rt2 stream) are those of the rows that were there before, 2.3e-7 to
+2.8e-7.  No record came near its class constant, so none needed explaining from a summation order.  Wrong references
+rejected over the 66 weight-gradient records (accepted: 0): the pixels of the last chunk dropped 37 of 37, the last pixel
+split not summed 28 of 28, the last valid column not written 15 of 15, input row 0 read as padding 11 of 11 and the first
+pixel of a row's second chunk read as padding 2 of 2 (row-segment kernels), the fp32 operand rounded to bf16 on an f32-*
+kernel 3 of 3 (g) and 3 of 3 (a), ky and kx exchanged in the folded gradient 4 of 4.
+
+Nine of the rows are also launched through s2i_conv_wgrad / s2i_conv_wgrad_dt themselves (test_direct_wgrad_*): g with row
+stride N + 8 and NaN in columns [N, ldg), the workspace of exactly s2i_wgrad_workspace_bytes(_dt) bytes and the OIHW tensor
+each between guard bytes, the tensor prefilled where the record accumulates or slices.  Every guard byte came back
+unchanged, the input channels outside the slice bit-identical, the fourth slab of the bf16 row whose 64-pixel re-cut fills
+three of four unwritten, every result finite; worst ratio 1.0e-7 on the fp32 cores (f32-256x256) and 2.0e-8 on the bf16
+cores, the same figures as the replays of these rows, whose operands they share.  A workspace one byte short and ldg < N
+are refused with their message and nothing written.
+
+No kernel was found wrong; rows3-64x32, which had never executed, holds 5.0e-8.  Deliberate mutation, tried once and
+reverted: the channel half of aoff exchanged in the 64 x 32 instantiation of wgrad_k3_rows_kernel (in bounds).  The five
+replays and the two direct calls that planned to rows3-64x32 failed (element error 0.04 to 0.20 x absref) and none of the
+other 305 tests did (the third direct call of that kernel, into a slice, was added after the trial); before this change no
+test of the repository ran that kernel.
+
+Wall time of this module on one MI355X, parent commit and this one run alternately, four times: the parent's 269 tests
+11.2 to 12.6 s, the tests of this one (312, then all 313) 11.2 to 12.1 s.  The 44 new tests take under 1 s together (the
+largest, 9 x 64 x 64 x 64 floats, 0.04 s for its replay and 0.02 s for its direct call); the spread between two runs of
+the same commit is larger.
 """
 import os
 import sys
@@ -238,16 +292,25 @@ def test_plan_without_a_kernel_falls_back_and_holds_the_bf16_bound(gpu, index):
 
 
 def _wgrad_extra(ledger, what):
+    """The worst ratio per branch tag of the record's plan, and the wrong references of conv_edges.wgrad_mutants (one per
+    branch the plan takes), each of which the comparison has to reject."""
     def extra(ctx):
-        for tag in ctx["rec"]["reach"]:
-            if tag.startswith("b16-"):
-                ledger.note("branch " + tag, ctx["ratio"], what, ctx["gamma"])
-        return []
+        rec, bad = ctx["rec"], []
+        plan = E.wgrad_plan(rec)
+        for tag in sorted(plan["reach"]):
+            ledger.note("branch " + tag, ctx["ratio"], what, ctx["gamma"])
+        for name, m in E.wgrad_mutants(rec, plan, ctx["a"], ctx["g"], ctx["dw"], ctx["true"]).items():
+            if LH.fails(ctx["got"], ctx["base"] + m, ctx["absref"], ctx["rnd"], ctx["gamma"]):
+                ledger.reject("wgrad branch: " + name)
+            else:
+                ACCEPTED.append((what, name))
+                bad.append("the bound cannot see: " + name)
+        return bad
     return extra
 
 
 # ---- the bf16 entry point itself: a strided destination, every buffer between sentinels ---------------------------------
-DIRECT = [i for i, r in enumerate(E.RECORDS) if r.get("direct")]
+DIRECT = [i for i, r in enumerate(E.RECORDS) if r.get("direct") and "x" in r]
 
 
 def _guarded(nbytes, dev):
@@ -353,6 +416,114 @@ def test_direct_call_refuses_before_any_launch(gpu):
         for buf in (ybuf, pbuf, sbuf):
             assert bool((buf == LH.GUARD_BYTE).all()), "a refused launch wrote: %s" % text
 
+
+# ---- the weight-gradient entry points themselves: a strided g, the workspace and the gradient between sentinels ---------
+WG_DIRECT = [i for i, r in enumerate(E.RECORDS) if r.get("direct") and "a" in r]
+
+
+def _wgrad_direct(rec, gpu, *, ldg_pad=8, ws_short=0):
+    """One call of s2i_conv_wgrad (fp32 operands) or s2i_conv_wgrad_dt on record rec: g with row stride N + ldg_pad and NaN in
+    columns [N, ldg); the workspace of exactly the bytes the workspace query names (less ws_short) and the OIHW tensor each
+    between guard bytes, the tensor prefilled where the record writes into one.  Returns everything the checks need."""
+    import ctypes
+    from speech_to_image_translation_without_text_amd import _lib
+    lib = _lib.load()
+    gen = LH.gen_rec(gpu, rec)
+    a, g = C._operand(rec["a"], gen, gpu), C._operand(rec["g"], gen, gpu)
+    a16, g16 = a.dtype == torch.bfloat16, g.dtype == torch.bfloat16
+    on_f32 = C.wgrad_on_f32(rec)
+    if a16 != g16 and not on_f32:
+        a, g = [t if t.dtype == torch.bfloat16 else t.bfloat16().float() for t in (a, g)]
+    N = g.shape[-1]
+    M = g.numel() // N
+    gp = torch.full((M, N + max(ldg_pad, 0)), float("nan"), dtype=g.dtype, device=gpu)
+    gp[:, :N] = g.reshape(M, N)
+    good = E.wgrad_desc(rec)
+    good.ldg = N + max(ldg_pad, 0)
+    d = E.wgrad_desc(rec)
+    d.ldg = N + ldg_pad
+    fp32 = not (a16 or g16)
+    ws_bytes = lib.s2i_wgrad_workspace_bytes(ctypes.byref(good)) if fp32 else \
+        lib.s2i_wgrad_workspace_bytes_dt(ctypes.byref(good), int(a16), int(g16))
+    plan = _lib.wgrad_plan(good, int(a16), int(g16))
+    assert ws_bytes > 0 and plan is not None and plan["kernel"] == E.wgrad_plan(rec)["kernel"], (ws_bytes, plan, lib.s2i_last_error())
+    assert ws_bytes == plan["ws_slabs"] * plan["K"] * N * 4
+    full = list(rec["grad_shape"])
+    if rec["I_total"]:
+        full[1] = rec["I_total"]
+    nel = 1
+    for v in full:
+        nel *= v
+    gbuf, gptr = _guarded(nel * 4, gpu)
+    prefill = torch.randn(full, generator=gen, device=gpu) if rec["out"] else None
+    if prefill is not None:
+        _inner(gbuf, nel * 4, torch.float32).copy_(prefill.view(-1))
+    wbuf, wptr = _guarded(ws_bytes, gpu)
+    if fp32:
+        rc = lib.s2i_conv_wgrad(ctypes.byref(d), a.data_ptr(), None, gp.data_ptr(), gptr, wptr, ws_bytes - ws_short, _lib.stream())
+    else:
+        rc = lib.s2i_conv_wgrad_dt(ctypes.byref(d), a.data_ptr(), int(a16), None, gp.data_ptr(), int(g16), gptr, wptr,
+                                   ws_bytes - ws_short, _lib.stream())
+    err = lib.s2i_last_error().decode()
+    torch.cuda.synchronize()
+    return dict(rc=rc, err=err, a=a, g=g, gbuf=gbuf, wbuf=wbuf, nel=nel, ws_bytes=ws_bytes, full=full, prefill=prefill, plan=plan,
+                cls=("bf16" if (a16 or g16) and not on_f32 else "fp32") + "/wgrad")
+
+
+@pytest.mark.parametrize("index", WG_DIRECT, ids=[E.record_id(i, E.RECORDS[i]) for i in WG_DIRECT])
+def test_direct_wgrad_keeps_to_its_workspace_slice_and_columns(gpu, index):
+    """s2i_conv_wgrad / s2i_conv_wgrad_dt with ldg = N + 8: every guard byte around the workspace the query sized and
+    around the OIHW tensor is unchanged, input channels outside [i_off, i_off + I) are bit-identical, the slabs a bf16
+    re-cut does not write stay unwritten, and the result holds the bound of its class and is finite (the NaN columns
+    [N, ldg) of g were not read)."""
+    _default_planner()
+    from speech_to_image_translation_without_text_amd import _lib
+    rec = E.RECORDS[index]
+    what = "direct " + E.record_id(index, rec)
+    with torch.no_grad(), _lib.tuning(**rec["tune"]):
+        r = _wgrad_direct(rec, gpu)
+        eplan = E.wgrad_plan(rec)
+    assert r["rc"] == 0, r["err"]
+    cls = "direct " + r["cls"]
+    chk = LH.Check(what, {cls: C.GAMMA[r["cls"]]}, EDGE_LEDGER)
+    chk.watch(r["gbuf"], LH.GUARD_BYTES, r["nel"] * 4)
+    chk.watch(r["wbuf"], LH.GUARD_BYTES, r["ws_bytes"])
+    plan = r["plan"]
+    if plan["slabs"] < plan["ws_slabs"]:
+        spare = _inner(r["wbuf"], r["ws_bytes"], torch.uint8)[plan["slabs"] * (r["ws_bytes"] // plan["ws_slabs"]):]
+        hit = int((spare != LH.GUARD_BYTE).sum())
+        if hit:
+            chk.bad.append("%d bytes of the slabs behind the %d the re-cut fills were written" % (hit, plan["slabs"]))
+    res = _inner(r["gbuf"], r["nel"] * 4, torch.float32).view(r["full"])
+    gs, i_off = rec["grad_shape"], rec["i_off"]
+    sl = (slice(None), slice(i_off, i_off + gs[1])) if rec["I_total"] else (slice(None),)
+    if rec["I_total"]:
+        keep = torch.ones(r["full"], dtype=torch.bool, device=gpu)
+        keep[sl] = False
+        chk.equal("input channels outside [%d, %d)" % (i_off, i_off + gs[1]), res[keep], r["prefill"][keep])
+    ad, gd = LH.nchw(r["a"].double()), LH.nchw(r["g"].double())
+    dw = C.wgrad_dw(rec, R.layer_op(rec)[1], ad, gd)
+    base = r["prefill"].double()[sl] if rec["accumulate"] else 0.0
+    true = dw()
+    got = res[sl]
+    if not bool(torch.isfinite(got).all()):
+        chk.bad.append("the result is not finite: columns [N, ldg) of g were read")
+    mutants = {k: base + m for k, m in E.wgrad_mutants(rec, eplan, ad, gd, dw, true).items()}
+    chk.close(cls, "grad", got, base + true, dw(absval=True), 2 * LH.U if rec["accumulate"] else 0.0, mutants)
+    chk.done()
+
+
+def test_direct_wgrad_refuses_before_any_launch(gpu):
+    """A workspace one byte short and ldg < N: error code and text, and no kernel ran -- workspace and gradient keep their fill."""
+    from speech_to_image_translation_without_text_amd import _lib
+    rec = E.RECORDS[WG_DIRECT[0]]
+    assert not rec["out"]
+    with torch.no_grad(), _lib.tuning(**rec["tune"]):
+        for kw, text in ((dict(ws_short=1), "workspace too small"), (dict(ldg_pad=-4), "ldg < N")):
+            r = _wgrad_direct(rec, gpu, **kw)
+            assert r["rc"] == 1 and text in r["err"], (r["rc"], r["err"])
+            for buf in (r["gbuf"], r["wbuf"]):
+                assert bool((buf == LH.GUARD_BYTE).all()), "a refused launch wrote: %s" % text
 
 
 
