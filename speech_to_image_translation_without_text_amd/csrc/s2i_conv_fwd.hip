@@ -166,6 +166,44 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ slab, int S, long
   }
 }
 
+// splitk_reduce_kernel for N % 4 == 0 && ldy % 4 == 0: one column quad per thread and turn, 16-byte loads and stores, the
+// (row, column) of the quad carried from turn to turn (srow, scol = the grid's stride in rows and columns).  Per element
+// the same chain: 0 + slab0 + slab1 ..., bias, activation.
+__global__ __launch_bounds__(256) void splitk_reduce_v4_kernel(const float* __restrict__ slab, int S, long long rows, int N,
+                                                               const float* __restrict__ bias, int act,
+                                                               float* __restrict__ y, int ldy, int y16, long long srow,
+                                                               int scol) {
+  const long long total = rows * N;
+  const long long e0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (e0 >= total) return;
+  long long row = e0 / N;
+  int n = (int)(e0 - row * N);
+  for (; row < rows;) {
+    const float* sp = slab + row * N + n;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < S; ++s) v += *reinterpret_cast<const f32x4*>(sp + (size_t)s * total);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float t = v[j];
+      if (bias) t += bias[n + j];
+      if (act == S2I_ACT_LRELU) t = t > 0.f ? t : 0.2f * t;
+      else if (act == S2I_ACT_TANH) t = tanhf(t);
+      else if (act == S2I_ACT_RELU) t = fmaxf(t, 0.f);
+      v[j] = t;
+    }
+    if (y16) {
+      unsigned short* yp = reinterpret_cast<unsigned short*>(y) + row * ldy + n;
+      *reinterpret_cast<u32x2_t*>(yp) = u32x2_t{(unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16),
+                                               (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16)};
+    } else {
+      *reinterpret_cast<f32x4*>(y + row * ldy + n) = v;
+    }
+    row += srow;
+    n += scol;
+    if (n >= N) { n -= N; ++row; }
+  }
+}
+
 // split-K reduction fused with the BatchNorm column statistics: y = sum_s slab[s], part = per-row-chunk column
 // sums and sums of squares (the layout s2i_colstats writes).  256 threads = cpb column quads x 256/cpb row lanes.
 __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const float* __restrict__ slab, int S, long long rows,
@@ -214,6 +252,98 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const float* _
   }
 }
 
+// The same reduction for cpb >= 32 (N > 64), spread over the chip: a block owns QB column quads of one row chunk, its 256
+// threads are QB quads x 256 / QB row workers that load, sum over the slabs and store y for 512 / QB rows per turn (two
+// each), and hand the sums through LDS to the QB x rpb threads that own the statistics (QB = 32, 16 rows per turn, for row
+// chunks of at most 16 rows; 16 otherwise).  Those walk the rows as the kernel above does (rpb = 256 / cpb row lanes per
+// quad, rows r0 + lane, + rpb, ...; then lanes 1 .. rpb-1 onto lane 0), so y and part come out bit for bit the same.  The
+// first two slabs of the next turn are loaded before the walk and summed after it.
+constexpr int RS_AHEAD = 2;
+template <int RS_QB>
+__global__ __launch_bounds__(256) void splitk_reduce_stats_wide_kernel(const float* __restrict__ slab, int S,
+                                                                       long long rows, int N, float* __restrict__ y,
+                                                                       int ldy, float* __restrict__ part, int nparts,
+                                                                       int rpb, int ppg, long long Rg, int y16) {
+  constexpr int RS_RW = 256 / RS_QB, RS_ROWS = 2 * RS_RW;
+  __shared__ f32x4 vt[RS_ROWS][RS_QB];       // 8 KB: the turn's sums over the slabs
+  __shared__ f32x4 sh[2][8 * RS_QB];         // 4 or 8 KB: the row lanes' statistics (rpb <= 8)
+  const int tid = threadIdx.x;
+  const int ql = tid % RS_QB, rw = tid / RS_QB;
+  const int quad = blockIdx.y * RS_QB + ql;
+  const int Q = N / 4;
+  const int grp = blockIdx.x / ppg, pp = blockIdx.x - grp * ppg;  // BatchNorm group of this row chunk
+  const long long chunk = (Rg + ppg - 1) / ppg;
+  const long long r0 = grp * Rg + pp * chunk;
+  const long long gend = (grp + 1) * Rg < rows ? (grp + 1) * Rg : rows;
+  const long long r1 = r0 + chunk < gend ? r0 + chunk : gend;
+  const size_t sstride = (size_t)rows * N;
+  const bool colok = quad < Q;
+  const bool owner = tid < RS_QB * rpb && colok;  // (quad ql, row lane rw) of the statistics
+  const int ahead = S < RS_AHEAD ? S : RS_AHEAD;
+  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 t[2][RS_AHEAD];
+  auto issue = [&](long long base) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const long long row = base + rw + h * RS_RW;
+      if (colok && row < r1) {
+        const float* sp = slab + row * N + quad * 4;
+#pragma unroll
+        for (int k = 0; k < RS_AHEAD; ++k)
+          if (k < ahead) t[h][k] = *reinterpret_cast<const f32x4*>(sp + k * sstride);
+      }
+    }
+  };
+  if (r0 < r1) issue(r0);
+  for (long long base = r0; base < r1; base += RS_ROWS) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const long long row = base + rw + h * RS_RW;
+      if (colok && row < r1) {
+        const float* sp = slab + row * N + quad * 4;
+        f32x4 v = t[h][0];
+#pragma unroll
+        for (int k = 1; k < RS_AHEAD; ++k)
+          if (k < ahead) v += t[h][k];
+        for (int s = RS_AHEAD; s < S; ++s) v += *reinterpret_cast<const f32x4*>(sp + s * sstride);
+        if (y16) {
+          unsigned short* yp = reinterpret_cast<unsigned short*>(y) + row * ldy + quad * 4;
+          *reinterpret_cast<u32x2_t*>(yp) = u32x2_t{(unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16),
+                                                   (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16)};
+        } else {
+          *reinterpret_cast<f32x4*>(y + row * ldy + quad * 4) = v;
+        }
+        vt[rw + h * RS_RW][ql] = v;
+      }
+    }
+    __syncthreads();
+    if (base + RS_ROWS < r1) issue(base + RS_ROWS);
+    if (owner) {
+      const long long left = r1 - base;
+      const int jend = left < RS_ROWS ? (int)left : RS_ROWS;
+      for (int j = rw; j < jend; j += rpb) {  // RS_ROWS % rpb == 0: lane rw's rows of the chunk, in their order
+        const f32x4 v = vt[j][ql];
+        s0 += v;
+        s1 += v * v;
+      }
+    }
+    __syncthreads();
+  }
+  if (owner) {
+    sh[0][tid] = s0;
+    sh[1][tid] = s1;
+  }
+  __syncthreads();
+  if (rw == 0 && colok) {
+    for (int r = 1; r < rpb; ++r) {
+      s0 += sh[0][r * RS_QB + ql];
+      s1 += sh[1][r * RS_QB + ql];
+    }
+    *reinterpret_cast<f32x4*>(part + ((size_t)0 * nparts + blockIdx.x) * N + quad * 4) = s0;
+    *reinterpret_cast<f32x4*>(part + ((size_t)1 * nparts + blockIdx.x) * N + quad * 4) = s1;
+  }
+}
+
 }  // namespace
 
 int launch_igemm_fwd(const FwdPlan& pl, const IgemmP& p, hipStream_t st) {
@@ -249,17 +379,36 @@ int launch_splitk_reduce(const s2i_conv_desc* d, const FwdPlan& pl, const float*
     while (cpb < Q && cpb < 256) cpb <<= 1;
     const int groups = d->groups < 1 ? 1 : d->groups;
     const int nparts = stat_parts(pl, groups);
-    hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3(nparts, (Q + cpb - 1) / cpb), dim3(256), 0, st,
-                       (const float*)ws, pl.splitk, pl.Mrows, d->N, y, d->ldy, part, nparts, cpb, nparts / groups,
-                       pl.Mrows / groups, y16);
+    // cpb fixes the statistics' summation order (256 / cpb row lanes per quad) in both kernels; the wide one only spreads
+    // the loads over more blocks
+    const int ppg = nparts / groups;
+    const long long Rg = pl.Mrows / groups;
+    if (cpb >= 32 && s2i_cdiv(Rg, ppg) <= 16)
+      hipLaunchKernelGGL(splitk_reduce_stats_wide_kernel<32>, dim3(nparts, (Q + 31) / 32), dim3(256), 0, st,
+                         (const float*)ws, pl.splitk, pl.Mrows, d->N, y, d->ldy, part, nparts, 256 / cpb, ppg, Rg, y16);
+    else if (cpb >= 32)
+      hipLaunchKernelGGL(splitk_reduce_stats_wide_kernel<16>, dim3(nparts, (Q + 15) / 16), dim3(256), 0, st,
+                         (const float*)ws, pl.splitk, pl.Mrows, d->N, y, d->ldy, part, nparts, 256 / cpb, ppg, Rg, y16);
+    else
+      hipLaunchKernelGGL(splitk_reduce_stats_kernel, dim3(nparts, (Q + cpb - 1) / cpb), dim3(256), 0, st,
+                         (const float*)ws, pl.splitk, pl.Mrows, d->N, y, d->ldy, part, nparts, cpb, nparts / groups,
+                         pl.Mrows / groups, y16);
     S2I_LAUNCH_CHECK("splitk_reduce_stats");
     return 0;
   }
   const long long total = pl.Mrows * d->N;
-  int blocks = s2i_cdiv(total, 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)ws, pl.splitk,
-                     pl.Mrows, d->N, bias, d->act, y, d->ldy, y16);
+  if ((d->N & 3) == 0 && (d->ldy & 3) == 0) {
+    int blocks = s2i_cdiv(total / 4, 256);
+    if (blocks > 2048) blocks = 2048;
+    const long long stride = (long long)blocks * 256 * 4;
+    hipLaunchKernelGGL(splitk_reduce_v4_kernel, dim3(blocks), dim3(256), 0, st, (const float*)ws, pl.splitk, pl.Mrows,
+                       d->N, bias, d->act, y, d->ldy, y16, stride / d->N, (int)(stride % d->N));
+  } else {
+    int blocks = s2i_cdiv(total, 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)ws, pl.splitk,
+                       pl.Mrows, d->N, bias, d->act, y, d->ldy, y16);
+  }
   S2I_LAUNCH_CHECK("splitk_reduce");
   if (pl.reduce == FWD_REDUCE_COLSTATS) return s2i_colstats(y, pl.Mrows, d->N, d->ldy, part, stat_parts(pl, 1), stream);
   return 0;

@@ -673,41 +673,69 @@ __global__ __launch_bounds__(256) void slab_sum_kernel(float* __restrict__ slab,
 // LDS so that both the slab reads (32 consecutive columns) and the OIHW writes (runs of (cin, ky, kx) for one
 // cout) are coalesced.  fold: the 3x3 parameter tap (ky,kx) collects the 4 effective 4x4 taps it was summed into.
 //   non-swap: slab rows (tap, cin), columns cout;   swap: slab rows (tap, cout), columns cin.
-__global__ __launch_bounds__(256) void wgrad_finish_kernel(const float* __restrict__ slab, int S, int K, int N,
-                                                           int Cg, int O, int I, int Tp, int T, int swap, int fold,
-                                                           int accumulate, int RT, float* __restrict__ grad,
-                                                           int i_off, int I_total) {
-  extern __shared__ float tile[];  // [T][RT][33]
+//   The tile is [T][TS] with rows of 33 floats inside a tap and TS = RT * 33 padded (wg_finish_tap_stride) so that the taps
+// of the OIHW write loop, its fastest index, fall on different LDS banks.  RT is a power of two (lgRT); TP is the number
+// of parameter taps as a constant (9, 16, 1) or 0 for any (Tp).
+//   Each element is 0 + slab0 + slab1 ..., read 16 bytes wide where V4 (N % 4 == 0).
+struct WgFinishP {
+  const float* slab;
+  float* grad;
+  int S, K, N, Cg, O, I, Tp, T, swap, fold, accumulate, lgRT, TS, i_off, I_total;
+};
+
+template <int TP, bool V4>
+__global__ __launch_bounds__(256) void wgrad_finish_kernel(const WgFinishP p) {
+  extern __shared__ float tile[];  // [T][TS]
   const int tid = threadIdx.x;
-  const int ncols = swap ? I : O, nrows = swap ? O : I;
+  const int Tp = TP > 0 ? TP : p.Tp;
+  const int lgRT = p.lgRT, RT = 1 << lgRT, TS = p.TS, N = p.N, S = p.S;
+  const int ncols = p.swap ? p.I : p.O, nrows = p.swap ? p.O : p.I;
   const int c0 = blockIdx.x * 32, r0 = blockIdx.y * RT;
-  const size_t sstride = (size_t)K * N;
-  const int nload = T * RT * 32;
-  for (int e = tid; e < nload; e += 256) {
-    const int c_l = e & 31;
-    const int r_l = (e >> 5) % RT;
-    const int t = (e >> 5) / RT;
-    const int c = c0 + c_l, r = r0 + r_l;
-    float v = 0.f;
-    if (c < ncols && r < nrows) {
-      const float* sp = slab + ((size_t)t * Cg + r) * N + c;
-      for (int s = 0; s < S; ++s) v += sp[s * sstride];
+  const size_t sstride = (size_t)p.K * N;
+  if (V4) {
+    const int nload = (p.T << lgRT) * 8;
+    for (int e = tid; e < nload; e += 256) {
+      const int c_l = (e & 7) * 4;
+      const int r_l = (e >> 3) & (RT - 1);
+      const int t = (e >> 3) >> lgRT;
+      const int c = c0 + c_l, r = r0 + r_l;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (c < ncols && r < nrows) {
+        const float* sp = p.slab + ((size_t)t * p.Cg + r) * N + c;
+        for (int s = 0; s < S; ++s) v += *reinterpret_cast<const f32x4*>(sp + s * sstride);
+      }
+      float* tp = tile + t * TS + r_l * 33 + c_l;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tp[j] = c + j < ncols ? v[j] : 0.f;
     }
-    tile[(t * RT + r_l) * 33 + c_l] = v;
+  } else {
+    const int nload = (p.T << lgRT) * 32;
+    for (int e = tid; e < nload; e += 256) {
+      const int c_l = e & 31;
+      const int r_l = (e >> 5) & (RT - 1);
+      const int t = (e >> 5) >> lgRT;
+      const int c = c0 + c_l, r = r0 + r_l;
+      float v = 0.f;
+      if (c < ncols && r < nrows) {
+        const float* sp = p.slab + ((size_t)t * p.Cg + r) * N + c;
+        for (int s = 0; s < S; ++s) v += sp[s * sstride];
+      }
+      tile[t * TS + r_l * 33 + c_l] = v;
+    }
   }
   __syncthreads();
   const int nout = 32 * RT * Tp;
   for (int w = tid; w < nout; w += 256) {
-    const int tapo = w % Tp;
     const int rest = w / Tp;
+    const int tapo = w - rest * Tp;
     int o_l, i_l, r_l, c_l;
-    if (swap) { i_l = rest & 31; o_l = rest >> 5; r_l = o_l; c_l = i_l; }
-    else { i_l = rest % RT; o_l = rest / RT; r_l = i_l; c_l = o_l; }
-    const int o = swap ? r0 + o_l : c0 + o_l;
-    const int i = swap ? c0 + i_l : r0 + i_l;
-    if (o >= O || i >= I) continue;
+    if (p.swap) { i_l = rest & 31; o_l = rest >> 5; r_l = o_l; c_l = i_l; }
+    else { i_l = rest & (RT - 1); o_l = rest >> lgRT; r_l = i_l; c_l = o_l; }
+    const int o = p.swap ? r0 + o_l : c0 + o_l;
+    const int i = p.swap ? c0 + i_l : r0 + i_l;
+    if (o >= p.O || i >= p.I) continue;
     float v;
-    if (fold) {
+    if (p.fold) {
       const int ky = tapo / 3, kx = tapo - ky * 3;
       v = 0.f;
 #pragma unroll
@@ -715,14 +743,33 @@ __global__ __launch_bounds__(256) void wgrad_finish_kernel(const float* __restri
 #pragma unroll
         for (int ax = 0; ax < 2; ++ax) {
           const int t = ((2 - ky) + ay) * 4 + (2 - kx) + ax;  // ky=0:{2,3} ky=1:{1,2} ky=2:{0,1}
-          v += tile[(t * RT + r_l) * 33 + c_l];
+          v += tile[t * TS + r_l * 33 + c_l];
         }
     } else {
-      v = tile[(tapo * RT + r_l) * 33 + c_l];
+      v = tile[tapo * TS + r_l * 33 + c_l];
     }
-    float* gp = grad + ((size_t)o * I_total + i_off + i) * Tp + tapo;
-    *gp = accumulate ? *gp + v : v;
+    float* gp = p.grad + ((size_t)o * p.I_total + p.i_off + i) * Tp + tapo;
+    *gp = p.accumulate ? *gp + v : v;
   }
+}
+
+// floats from one tap of the finish tile to the next: RT rows of 33, padded so that TS = 32 / Tp (rounded) mod 32.  The
+// write loop's lanes run over the taps first, then over a few rows or columns (one bank each): 4 banks per tap for the 9 taps
+// of a 3x3, 2 for the 16 of a 4x4.
+static int wg_finish_tap_stride(int RT, int Tp) {
+  int q = (32 + Tp / 2) / Tp;
+  if (q < 1) q = 1;
+  int ts = RT * 33;
+  while ((ts & 31) != (q & 31)) ++ts;
+  return ts;
+}
+
+template <bool V4>
+static void launch_wgrad_finish(const WgFinishP& fp, dim3 grid, size_t shb, hipStream_t st) {
+  if (fp.Tp == 9) hipLaunchKernelGGL((wgrad_finish_kernel<9, V4>), grid, dim3(256), shb, st, fp);
+  else if (fp.Tp == 16) hipLaunchKernelGGL((wgrad_finish_kernel<16, V4>), grid, dim3(256), shb, st, fp);
+  else if (fp.Tp == 1) hipLaunchKernelGGL((wgrad_finish_kernel<1, V4>), grid, dim3(256), shb, st, fp);
+  else hipLaunchKernelGGL((wgrad_finish_kernel<0, V4>), grid, dim3(256), shb, st, fp);
 }
 
 }  // namespace
@@ -798,27 +845,32 @@ static int launch_wgrad(const s2i_wgrad_desc* d, const WgPlan& pl, const float* 
     const int ncols = d->swap ? d->I : d->O, nrows = d->swap ? d->O : d->I;
     int RT = 8;
     while (RT > 1 && (long long)s2i_cdiv(ncols, 32) * s2i_cdiv(nrows, RT) < 128) RT >>= 1;
+    const int Tp = d->KH * d->KW;
     dim3 fgrid(s2i_cdiv(ncols, 32), s2i_cdiv(nrows, RT));
-    const size_t shb = (size_t)pl.T * RT * 33 * sizeof(float);
-    // two passes (measured: 27 + 17 us against 53 us for one pass that walks the slabs tile by tile): first a
-    // float4 stream folds the split slabs into slab 0, then the tile kernel transposes slab 0 into OIHW
-    int S = pl.slabs;
+    WgFinishP fp;
+    fp.slab = (const float*)ws; fp.grad = grad_oihw;
+    fp.S = pl.slabs; fp.K = pl.K; fp.N = d->N; fp.Cg = pl.Cin; fp.O = d->O; fp.I = d->I; fp.Tp = Tp; fp.T = pl.T;
+    fp.swap = d->swap; fp.fold = d->fold; fp.accumulate = d->accumulate; fp.lgRT = s2i_ilog2(RT);
+    fp.TS = wg_finish_tap_stride(RT, Tp); fp.i_off = d->i_off; fp.I_total = d->I_total > 0 ? d->I_total : d->I;
+    const size_t shb = (size_t)pl.T * fp.TS * sizeof(float);
     const long long kn = (long long)pl.K * d->N;
-    if (pl.kernel >= WG_SMALLN_16 || (S >= 32 && (kn % 4) == 0 && kn / 4 < (1 << 18))) {
+    // two passes (measured: 27 + 17 us against 53 us for one pass that walks the slabs tile by tile, and 215 against
+    // 16 + 10 us with the tree sum inside the finish blocks of a small K x N): first the split slabs are folded into slab 0,
+    // then the tile kernel transposes slab 0 into OIHW
+    if (pl.kernel >= WG_SMALLN_16 || (fp.S >= 32 && (kn % 4) == 0 && kn / 4 < (1 << 18))) {
       // many slabs of a small K x N: the float4 stream below would run on a handful of blocks
-      hipLaunchKernelGGL(slab_sum_tree_kernel, dim3(s2i_cdiv(kn / 4, 4)), dim3(256), 0, st, (float*)ws, S, (int)(kn / 4));
+      hipLaunchKernelGGL(slab_sum_tree_kernel, dim3(s2i_cdiv(kn / 4, 4)), dim3(256), 0, st, (float*)ws, fp.S, (int)(kn / 4));
       S2I_LAUNCH_CHECK("slab_sum_tree");
-      S = 1;
-    } else if (S > 2 && (kn % 4) == 0) {
+      fp.S = 1;
+    } else if (fp.S > 2 && (kn % 4) == 0) {
       int sb = s2i_cdiv(kn / 4, 256);
       if (sb > 4096) sb = 4096;
-      hipLaunchKernelGGL(slab_sum_kernel, dim3(sb), dim3(256), 0, st, (float*)ws, S, kn / 4);
+      hipLaunchKernelGGL(slab_sum_kernel, dim3(sb), dim3(256), 0, st, (float*)ws, fp.S, kn / 4);
       S2I_LAUNCH_CHECK("slab_sum");
-      S = 1;
+      fp.S = 1;
     }
-    hipLaunchKernelGGL(wgrad_finish_kernel, fgrid, dim3(256), shb, st, (const float*)ws, S, pl.K, d->N,
-                       pl.Cin, d->O, d->I, d->KH * d->KW, pl.T, d->swap, d->fold, d->accumulate, RT, grad_oihw,
-                       d->i_off, d->I_total > 0 ? d->I_total : d->I);
+    if ((d->N & 3) == 0 && ncols <= d->N) launch_wgrad_finish<true>(fp, fgrid, shb, st);
+    else launch_wgrad_finish<false>(fp, fgrid, shb, st);
   }
   S2I_LAUNCH_CHECK("wgrad_finish");
   return 0;
