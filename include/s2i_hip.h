@@ -526,6 +526,60 @@ int s2i_reverb_rir(const void* table, int B, int max_taps, float* h, unsigned lo
 int s2i_reverb(const float* x, const long long* offsets, const int* lens, int B, int max_len, const void* table,
                const float* h, int max_taps, float* y, void* stream);
 
+/* ---- time stretch of a batch of waveforms: the short-time phase vocoder (csrc/s2i_stretch.hip) -----------------------------
+   librosa.effects.time_stretch with n_fft 512, hop 128, a periodic Hann window and zero centre padding, the phase kept in
+   turns; with the resampler behind it, it is also the pitch shift.  x: a flat fp32 batch, clip b is
+   x[offsets[b] .. offsets[b] + n), offsets DEVICE int64 [B] in floats, n = lens[b] (DEVICE int32 [B], clamped to
+   [0, max_len]); max_len is the host's bound on the lens, in [1, 2^29 - 1025].  y: a second flat fp32 buffer, disjoint from
+   x; clip b is written to y[out_offsets[b] .. out_offsets[b] + out_len), out_offsets DEVICE int64 [B].  x, y, the basis
+   and the workspace are 16-byte aligned.  table: DEVICE, 16 bytes per clip, 16-byte aligned:
+     double rate; int out_len; int out_frames;
+   rate == 1.0 exactly copies the first min(n, out_len) samples bit for bit.  Otherwise rate lies in [0.25, 4] and, with
+   F = 1 + n div 128, out_len = floor(n / rate + 0.5) and out_frames = ceil(F / rate), both computed in float64 by the
+   host; out_len is clamped to [0, max_out_len] (the host's bound on the out_len, at most 4 max_len) and out_frames to
+   [0, 4 F].  A clip with n == 0 or a rate outside [0.25, 4] (NaN included) is left unwritten.  So is a stretched
+   clip whose frames, counted behind those of every stretched clip before it in the table, reach beyond the totals given,
+   and with it every stretched clip behind it; copied clips are written all the same.  Floats outside the clips are never written.
+   basis: DEVICE fp32 [s2i_stretch_basis_elems() = 2 x 512 x 512 + 512], built in float64 and rounded once:
+     forward [512 samples i][512 columns]: column tile 2 t + h (16 columns, c the column inside it) holds, for bin
+       k = 16 t + c, w[i] cos(2 pi i k / 512) where h = 0 and -w[i] sin(2 pi i k / 512) where h = 1; bin 0 has no sine and
+       its h = 1 column is bin 256's cosine, w[i] cos(pi i);
+     inverse [512 rows][512 samples i]: row k <= 256 is c_k w[i] / 512 cos(2 pi i k / 512) and row 256 + k, k = 1..255, is
+       -2 w[i] / 512 sin(2 pi i k / 512), c_0 = c_256 = 1 and c_k = 2 otherwise;
+     both stored in fragment order: element (row r, column c of column tile nt) at
+       ((r div 16 * 32 + nt) * 64 + (r mod 4) * 16 + c) * 4 + (r mod 16) div 4;
+     then w[512], w[i] = 0.5 - 0.5 cos(2 pi i / 512).
+   analysis:  the clip is zero-padded by 256 samples at both ends; X_t[k] = sum_i w[i] xpad[128 t + i] e^(-2 pi i k / 512)
+           for t < F, k = 0..256 (frames F and F + 1 are zero); |X| = hypotf(re, im) and
+           arg X / 2 pi = atan2f(im, re) 0x1.45f306p-3f are what is kept (arg(0) = 0).
+   stretch:  for output frame t < out_frames: s = (double)t rate, j = floor(s), a = (float)(s - j);
+             M_t[k] = (1 - a) |X_j[k]| + a |X_j+1[k]|, each product rounded, then the sum;
+             Y_t[k] = M_t[k] (cos, sin)(2 pi theta_t[k]) through sincospif(2 theta);
+             theta_0[k] = arg X_0[k] / 2 pi;  with phi_k = (k mod 4) / 4 and wrap(v) = v - rintf(v),
+             d = wrap((arg X_j+1[k] / 2 pi - arg X_j[k] / 2 pi) - phi_k),  theta_t+1[k] = wrap((theta_t[k] + phi_k) + d).
+   synthesis:  y_t[i] = sum over the 512 rows of the inverse basis of [Re Y_t[0..256] | Im Y_t[1..255]] times the row.
+   overlap-add:  for m in [0, out_len), u = m + 256: the frames t < out_frames with 0 <= u - 128 t < 512, in ascending t,
+           add y_t[u - 128 t] to a numerator and w[u - 128 t] w[u - 128 t] (rounded) to a denominator, both from 0;
+           out[m] = numerator / denominator (a correctly rounded division) where the denominator exceeds 1e-10f, else the
+           numerator; 0 where no frame covers u.
+   order:  each output of a transform is summed in SIXTEEN runs of 32 consecutive samples (analysis) or basis rows
+           (synthesis).  A run has an fp32 accumulator p_r of its own that starts at +0 and takes its 32 products on
+           v_mfma_f32_16x16x4_f32 in ascending order, each product an fmaf; the output is
+           (((0 + p_0) + p_1) + ...) + p_15.  A product with a zero of the padding adds +-0.  The phase recursion of a (clip, bin) is one
+           thread's, in ascending t.  Every order depends on the clip alone: the same clip with the same rate gives the
+           same bits alone or in any batch, at any offset and for any max_len, on every run.
+   Five launches on `stream` (the clips' places in the workspace, analysis, recursion, synthesis, overlap-add), no atomics,
+   no block waits on another, no host round trip.  The caller owns the workspace of
+   s2i_time_stretch_workspace_bytes(B, in_frames_total, out_frames_total) bytes, the totals being at least the sums of F
+   and of out_frames over the clips with rate != 1.  Bad arguments (a null pointer, B < 1, max_len or max_out_len outside its
+   range, negative totals, a misaligned buffer, y == x, a workspace too small) return non-zero before any launch;
+   s2i_time_stretch_workspace_bytes returns 0 for them. */
+size_t s2i_stretch_basis_elems(void);
+size_t s2i_time_stretch_workspace_bytes(int B, long long in_frames_total, long long out_frames_total);
+int s2i_time_stretch(const float* x, const long long* offsets, const int* lens, int B, int max_len, const void* table,
+                     const float* basis, float* y, const long long* out_offsets, int max_out_len,
+                     long long in_frames_total, long long out_frames_total, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- CA_NET reparameterisation + KL (model.py:182-200, trainer.py:54-58) -------------------- */
 /* h = GLU output [B][2E] = [mu | logvar];  c = eps*exp(0.5*logvar) + mu */
 int s2i_reparam_forward(const float* h, const float* eps, int B, int E, float* c, void* stream);

@@ -156,6 +156,9 @@ _SIGNATURES = {
     "s2i_wave_mix": (c_int, [P, P, P, c_int, c_int, P, P, ctypes.c_ulonglong, ctypes.c_ulonglong, P, c_size_t, P]),
     "s2i_reverb_rir": (c_int, [P, c_int, c_int, P, ctypes.c_ulonglong, ctypes.c_ulonglong, P]),
     "s2i_reverb": (c_int, [P, P, P, c_int, c_int, P, P, c_int, P, P]),
+    "s2i_stretch_basis_elems": (c_size_t, []),
+    "s2i_time_stretch_workspace_bytes": (c_size_t, [c_int, c_ll, c_ll]),
+    "s2i_time_stretch": (c_int, [P, P, P, c_int, c_int, P, P, P, P, c_int, c_ll, c_ll, P, c_size_t, P]),
     "s2i_reparam_forward": (c_int, [P, P, c_int, c_int, P, P]),
     "s2i_reparam_backward": (c_int, [P, P, P, P, P, c_int, c_int, P, P]),
     "s2i_kl_forward": (c_int, [P, c_int, P, c_int, c_int, c_int, P, P]),

@@ -17,7 +17,8 @@ applied to the lengths first (`chunk_sources`) and any number of files runs as o
 NHWC) straight into CNNRNN.forward_nhwc.
 
 --waveaug 'speed=1.1,white=1@20:20' --waveaug_seed S writes the embeddings of perturbed audio instead (ops.waveaug_policy,
-wave_loader.perturb): every file at a drawn speed, in a drawn room (reverb=P@LO:HI@DLO:DHI, T60 in seconds and the
+wave_loader.perturb): every file at a drawn speed, tempo (tempo=F/F/..., duration only) and pitch (pitch=S/S/...
+semitones, pitch only; `retrieval` over such files measures the sensitivity to a shifted voice), in a drawn room (reverb=P@LO:HI@DLO:DHI, T60 in seconds and the
 direct-to-reverberant ratio in dB) and under white noise at a drawn signal-to-noise ratio, the draws a
 function of (S, 0, the file's running number in its split) alone, so a run repeats bit for bit.  The `retrieval` CLI over
 such files measures how accuracy, AP@50 and recall@k fall with noise or tempo.  babble= needs a pool of training
@@ -157,7 +158,8 @@ def get_parser():
                         "decoded, mixed down and resampled to 16 kHz on the GPU (audio.to_16k)")
     p.add_argument("--waveaug", type=str, default="",
                    help="write the embeddings of perturbed audio, e.g. 'speed=1.1,reverb=1@0.3:0.3@5:5,white=1@20:20' "
-                        "(ops.waveaug_policy; speed=, reverb=P@T60LO:T60HI@DRRLO:DRRHI and white= are taken; "
+                        "(ops.waveaug_policy; speed=, tempo=F/F/..., pitch=S/S/... in semitones, "
+                        "reverb=P@T60LO:T60HI@DRRLO:DRRHI and white= are taken; "
                         "babble= is refused: it needs a pool of training utterances); default '': off")
     p.add_argument("--waveaug_seed", type=int, default=0, help="seed of --waveaug's draws")
     return p
@@ -175,7 +177,7 @@ def make_aug(spec, seed):
     aug = WaveAug(spec, seed)
     if aug.policy["babble"] is not None:
         raise SystemExit("--waveaug: babble= draws its interferers from a pool of training utterances, which an extraction "
-                         "does not have: use speed=, reverb= and white= here")
+                         "does not have: use speed=, tempo=, pitch=, reverb= and white= here")
     return aug
 
 

@@ -2000,6 +2000,13 @@ REVERB_MAX_TAPS = 16000
 REVERB_MAX_LEN = 2 ** 31 - 8225
 # the device table of s2i_reverb_rir and s2i_reverb, 16 bytes per clip (include/s2i_hip.h)
 REVERB_ENTRY = [("alpha", "<f4"), ("slope", "<f4"), ("taps", "<i4"), ("uid", "<u4")]
+STRETCH_KEY_XOR = 0x53545243        # "STRC" into key word 1: the tempo and pitch draws share no block with any other draw
+STRETCH_MAX_CHOICES = 8
+STRETCH_RATE_GRID = 50              # Hz: a pitch-shifted read rate is a multiple of it, so the polyphase table has L <= 320
+STRETCH_NFFT, STRETCH_HOP = 512, 128
+STRETCH_MAX_LEN = 2 ** 29 - 1025
+# the device table of s2i_time_stretch, 16 bytes per clip (include/s2i_hip.h)
+STRETCH_ENTRY = [("rate", "<f8"), ("out_len", "<i4"), ("out_frames", "<i4")]
 
 
 def _waveaug_noise(token, value):
@@ -2064,6 +2071,38 @@ def _waveaug_speeds(token, value):
     return tuple(rates)
 
 
+def _waveaug_choices(token, value, what, lo, hi):
+    parts = value.split("/")
+    if not 1 <= len(parts) <= STRETCH_MAX_CHOICES:
+        raise ValueError("bad augmentation %r: 1 to %d %s" % (token, STRETCH_MAX_CHOICES, what))
+    out = []
+    for part in parts:
+        try:
+            v = float(part)
+        except ValueError:
+            raise ValueError("bad augmentation %r: %r is not a number" % (token, part)) from None
+        if not lo <= v <= hi:       # a NaN fails both
+            raise ValueError("bad augmentation %r: %s must lie in [%g, %g]" % (token, what, lo, hi))
+        out.append(v)
+    return tuple(out)
+
+
+def _waveaug_tempo(token, value):
+    return _waveaug_choices(token, value, "tempo factors", 0.5, 2.0)
+
+
+def _waveaug_pitch(token, value):
+    return _waveaug_choices(token, value, "semitone values", -12.0, 12.0)
+
+
+def stretch_read_rate(speed_rate, semitones):
+    """The rate a clip drawn at `speed_rate` Hz and shifted by `semitones` is read at: the speed's own rate where the
+    shift is 0, else 50 round(speed_rate 2^(semitones / 12) / 50) in float64 (under 6 cents off the asked pitch)."""
+    if semitones == 0:
+        return int(speed_rate)
+    return STRETCH_RATE_GRID * int(round(speed_rate * 2.0 ** (semitones / 12.0) / STRETCH_RATE_GRID))
+
+
 def waveaug_policy(spec):
     """'speed=0.9/1.0/1.1,reverb=0.3@0.2:0.6@0:15,white=0.3@5:25,babble=0.2@0:15' (any order, any subset; '' = off ->
     None) -> a dict
@@ -2077,8 +2116,18 @@ def waveaug_policy(spec):
     noise, whose power is then the reverberated clip's.  white= and babble= add noise or another utterance with
     probability P in (0, 1] at a signal-to-noise ratio drawn uniformly from [LO, HI] dB.  There is no gain key on purpose:
     power_to_db(ref=max) and the mean subtraction of the log-mel front end make the features invariant to a clip's
-    gain."""
-    values = {"speed": None, "white": None, "babble": None, "reverb": None}
+    gain.
+    tempo=F/F/... (1 to 8 factors in [0.5, 2.0]) divides a clip's duration by the factor it draws and keeps its pitch;
+    pitch=S/S/... (1 to 8 semitone values in [-12, 12]) multiplies the pitch by 2^(S / 12) and keeps the duration.  Both
+    run the phase vocoder s2i_time_stretch before the resampler, which then reads the clip at one combined rate
+    (`waveaug_plan`); the order is stretch, resample, reverb, noise.  "tempo" and "pitch" (tuples of floats) are in the dict
+    only where given (read them with .get).  Every rate a (speed, pitch) pair of the spec can produce must be one
+    `audio.resample_plan` accepts, and every (speed, tempo, pitch) triple's stretch tau Rs / R must lie in [0.25, 4], the
+    kernel's range (at the corners of the two ranges the 50 Hz grid can round it past 4); the pitch token is named
+    otherwise."""
+    from . import audio
+    values = {"speed": None, "white": None, "babble": None, "reverb": None, "tempo": None, "pitch": None}
+    tokens = {}
     seen = set()
     for token in str(spec).split(","):
         token = token.strip()
@@ -2088,17 +2137,35 @@ def waveaug_policy(spec):
         key = key.strip()
         if not sep or key not in values:
             raise ValueError("unknown augmentation %r: expected a comma-separated subset of speed=S/S/..., white=P@LO:HI, "
-                             "babble=P@LO:HI, reverb=P@LO:HI@DLO:DHI" % token)
+                             "babble=P@LO:HI, reverb=P@LO:HI@DLO:DHI, tempo=F/F/..., pitch=S/S/..." % token)
         if key in seen:
             raise ValueError("augmentation %r given twice" % token)
         seen.add(key)
-        parse = {"speed": _waveaug_speeds, "reverb": _waveaug_reverb}.get(key, _waveaug_noise)
+        tokens[key] = token
+        parse = {"speed": _waveaug_speeds, "reverb": _waveaug_reverb, "tempo": _waveaug_tempo,
+                 "pitch": _waveaug_pitch}.get(key, _waveaug_noise)
         values[key] = parse(token, value.strip())
     if not seen:
         return None
     policy = {"rates": values["speed"], "white": values["white"], "babble": values["babble"]}
-    if values["reverb"] is not None:
-        policy["reverb"] = values["reverb"]
+    for key in ("reverb", "tempo", "pitch"):
+        if values[key] is not None:
+            policy[key] = values[key]
+    if values["pitch"] is not None:
+        for speed_rate in values["speed"] or (audio.SAMPLE_RATE,):
+            for semis in values["pitch"]:
+                try:
+                    audio.resample_plan(stretch_read_rate(speed_rate, semis))
+                except ValueError as e:
+                    raise ValueError("bad augmentation %r: %s semitones at %d Hz: %s"
+                                     % (tokens["pitch"], semis, speed_rate, e)) from None
+                # the 50 Hz grid can round the rate past the corner of the two ranges: 7225 Hz -> 7200, tempo 2 -> 4.014
+                rate = stretch_read_rate(speed_rate, semis)
+                for tempo in values["tempo"] or (1.0,):
+                    rho = tempo * speed_rate / rate
+                    if not 0.25 <= rho <= 4.0:
+                        raise ValueError("bad augmentation %r: %s semitones at %d Hz and tempo %s need a time stretch by "
+                                         "%.4f, outside [0.25, 4]" % (tokens["pitch"], semis, speed_rate, tempo, rho))
     return policy
 
 
@@ -2152,7 +2219,18 @@ def waveaug_plan(policy, seed, step, uids, lens, pool_lens=None, pool_q=None, ta
     LO + u (HI - LO) in float64.  No field above depends on it.  It adds t60 and drr (float64, NaN where off), taps (int64,
     0 where off, else 32 ceil(T60 16000 / 32), at most 16000), slope (float32, -log2(1000) / (T60 16000) rounded once) and
     alpha (float32, sqrt(10^(-DRR / 10) / E), E = sum_{k=1}^{taps-1} 2^(2 k slope) in float64 over the rounded slope, the
-    geometric series summed in closed form): the tail's expected energy is 10^(-DRR / 10) of the direct path's.  Without reverb= the five fields are absent."""
+    geometric series summed in closed form): the tail's expected energy is 10^(-DRR / 10) of the direct path's.  Without reverb= the five fields are absent.
+
+    tempo= and pitch= draw from a third key, (seed mod 2^32, (seed div 2^32) ^ STRETCH_KEY_XOR), at counter
+    (step mod 2^32, step div 2^32, uid, 0): word 0 gives the tempo index and word 1 the pitch index, each
+    min(int(u (float)n), n - 1) with u = (r >> 8) 2^-24 (a key that is absent draws tempo 1 / 0 semitones).  With Rs the
+    drawn speed rate (16000 without speed=), tau the tempo and S the semitones, all in float64: the read rate is R = Rs
+    where S == 0, else 50 round(Rs 2^(S / 12) / 50); the stretch is rho = tau Rs / R (no stretch where rho == 1: the clip
+    is read in place); stretch_len = floor(n / rho + 0.5) and out_len = audio.resampled_length(stretch_len, R), so the
+    duration is n / (tau Rs / 16000) whatever S is.  A clip whose out_len would have under 64 frames is left wholly
+    unperturbed (16000 Hz, no stretch), the speed rule.  `rate` is then R and `out_len` the final length; the fields tempo,
+    semitones, stretch_rate (float64) and stretch_len (int64) are added.  Without the two keys they are absent and no field
+    above changes."""
     import numpy as np
     from . import audio
     uids = np.asarray(uids, dtype=np.int64).reshape(-1)
@@ -2166,11 +2244,16 @@ def waveaug_plan(policy, seed, step, uids, lens, pool_lens=None, pool_q=None, ta
     if policy["rates"] is not None:
         rates = np.array(policy["rates"], dtype=np.int64)
         rate = rates[_waveaug_index(u0[0], np.full(B, len(rates)))]
-    out_len = np.array([audio.resampled_length(n, r) for n, r in zip(lens, rate)], dtype=np.int64)
     nf = (audio.n_frames if target_length is None else lambda n: audio.n_frames(n, target_length))
-    for b in range(B):
-        if rate[b] != audio.SAMPLE_RATE and nf(out_len[b]) < WAVEAUG_MIN_FRAMES:
-            rate[b], out_len[b] = audio.SAMPLE_RATE, lens[b]
+    stretch = None
+    if policy.get("tempo") is not None or policy.get("pitch") is not None:
+        stretch = _stretch_plan(policy, seed, step, uids, lens, rate, nf)
+        rate, out_len = stretch.pop("rate"), stretch.pop("out_len")
+    else:
+        out_len = np.array([audio.resampled_length(n, r) for n, r in zip(lens, rate)], dtype=np.int64)
+        for b in range(B):
+            if rate[b] != audio.SAMPLE_RATE and nf(out_len[b]) < WAVEAUG_MIN_FRAMES:
+                rate[b], out_len[b] = audio.SAMPLE_RATE, lens[b]
     plan = dict(rate=rate, out_len=out_len, uid=uids.astype(np.uint32), white_snr=np.full(B, np.nan),
                 babble_snr=np.full(B, np.nan), g_white=np.zeros(B, np.float32), g_babble=np.zeros(B, np.float32),
                 src=np.zeros(B, np.int64), start=np.zeros(B, np.int64))
@@ -2199,7 +2282,93 @@ def waveaug_plan(policy, seed, step, uids, lens, pool_lens=None, pool_q=None, ta
         plan["start"] = _waveaug_index(u1[2], pool_lens[src])
     if policy.get("reverb") is not None:
         plan.update(_reverb_plan(policy["reverb"], seed, step, uids))
+    if stretch is not None:
+        plan.update(stretch)
     return plan
+
+
+def _stretch_plan(policy, seed, step, uids, lens, speed_rate, nf):
+    """the tempo= / pitch= fields of waveaug_plan, with the rate and out_len they replace"""
+    import numpy as np
+    from . import audio
+    tempos, pitches = policy.get("tempo") or (1.0,), policy.get("pitch") or (0.0,)
+    seed, step = int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1)
+    r = philox4x32_10(step & 0xFFFFFFFF, step >> 32, np.asarray(uids, dtype=np.uint64), 0, seed & 0xFFFFFFFF,
+                      (seed >> 32) ^ STRETCH_KEY_XOR)
+    u = (r >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    B = len(uids)
+    tempo = np.array(tempos, dtype=np.float64)[_waveaug_index(u[0], np.full(B, len(tempos)))]
+    semis = np.array(pitches, dtype=np.float64)[_waveaug_index(u[1], np.full(B, len(pitches)))]
+    rate, out_len = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+    rho, stretch_len = np.ones(B, dtype=np.float64), np.zeros(B, dtype=np.int64)
+    for b in range(B):
+        n, rs = int(lens[b]), int(speed_rate[b])
+        rate[b] = stretch_read_rate(rs, float(semis[b]))
+        rho[b] = float(tempo[b]) * rs / float(rate[b])
+        stretch_len[b] = n if rho[b] == 1.0 else int(math.floor(n / rho[b] + 0.5))
+        out_len[b] = audio.resampled_length(stretch_len[b], rate[b])
+        if (rate[b] != audio.SAMPLE_RATE or rho[b] != 1.0) and nf(out_len[b]) < WAVEAUG_MIN_FRAMES:
+            rate[b], out_len[b], stretch_len[b] = audio.SAMPLE_RATE, n, n
+            rho[b], tempo[b], semis[b] = 1.0, 1.0, 0.0
+    return dict(rate=rate, out_len=out_len, tempo=tempo, semitones=semis, stretch_rate=rho, stretch_len=stretch_len)
+
+
+def stretch_table(plan):
+    """The 16-byte-per-clip table of s2i_time_stretch (STRETCH_ENTRY) out of a waveaug_plan made under tempo= or pitch=:
+    rate = stretch_rate and out_len = stretch_len.  out_frames = ceil((1 + n div 128) / rate) needs the clips' lengths,
+    which the plan does not hold: `time_stretch_prepare` fills it in from its `lens`."""
+    import numpy as np
+    if "stretch_rate" not in plan:
+        raise ValueError("stretch_table: the plan was made without tempo= or pitch=")
+    t = np.zeros(len(plan["uid"]), dtype=STRETCH_ENTRY)
+    t["rate"], t["out_len"] = plan["stretch_rate"], plan["stretch_len"]
+    return t
+
+
+def stretch_basis64():
+    """(forward [512 samples][512 columns], inverse [512 rows][512 samples], window [512]) of s2i_time_stretch in float64,
+    the periodic Hann window folded into both matrices (include/s2i_hip.h).  Forward column 32 t + 16 h + c is bin
+    k = 16 t + c: w cos where h = 0, -w sin where h = 1; bin 0's h = 1 column is bin 256's cosine."""
+    import numpy as np
+    N = STRETCH_NFFT
+    i = np.arange(N)
+    w = 0.5 - 0.5 * np.cos(2.0 * np.pi * i / N)
+    ang = lambda k: 2.0 * np.pi * ((i * k) % N) / N          # noqa: E731
+    fwd, inv = np.zeros((N, N)), np.zeros((N, N))
+    for k in range(N // 2):
+        t, c = divmod(k, 16)
+        fwd[:, 32 * t + c] = w * np.cos(ang(k))
+        fwd[:, 32 * t + 16 + c] = -w * np.sin(ang(k)) if k else w * np.cos(ang(N // 2))
+    for k in range(N // 2 + 1):
+        inv[k] = (1.0 if k in (0, N // 2) else 2.0) * (w / N) * np.cos(ang(k))
+    for k in range(1, N // 2):
+        inv[N // 2 + k] = -2.0 * (w / N) * np.sin(ang(k))
+    return fwd, inv, w
+
+
+def pack_stretch_basis(m):
+    """[512][512] -> the fragment order of include/s2i_hip.h: element (r, c of column tile nt) at
+    ((r // 16 * 32 + nt) * 64 + (r % 4) * 16 + c) * 4 + (r % 16) // 4"""
+    import numpy as np
+    b = np.asarray(m).reshape(STRETCH_NFFT // 16, 4, 4, STRETCH_NFFT // 16, 16)     # [kg][u][g][nt][c], r = 16 kg + 4 u + g
+    return np.ascontiguousarray(b.transpose(0, 3, 2, 4, 1)).reshape(-1)             # [kg][nt][g][c][u]
+
+
+_STRETCH_BASIS = {}
+
+
+def device_stretch_basis(device):
+    """forward | inverse | window as one fp32 device tensor, rounded once from float64 and built once per device"""
+    import numpy as np
+    key = str(device)
+    if key not in _STRETCH_BASIS:
+        lib = _lib.load()
+        fwd, inv, w = stretch_basis64()
+        flat = np.concatenate([pack_stretch_basis(fwd), pack_stretch_basis(inv), w]).astype(np.float32)
+        if flat.size != lib.s2i_stretch_basis_elems():
+            raise _lib.S2IError("the stretch basis has %d floats, the library expects %d" % (flat.size, lib.s2i_stretch_basis_elems()))
+        _STRETCH_BASIS[key] = torch.from_numpy(flat).to(device)
+    return _STRETCH_BASIS[key]
 
 
 def _reverb_plan(term, seed, step, uids):
@@ -2378,6 +2547,90 @@ def reverb(x, offsets, lens, table, seed, step, out=None):
     check(lib.s2i_reverb(ptr(x), base, base + at_lens, B, max_len, base + at_table, ptr(h), max_taps, ptr(out), stream()),
           "s2i_reverb")
     return out
+
+
+def time_stretch_prepare(x, offsets, lens, table, out=None):
+    """The checked and uploaded arguments of one s2i_time_stretch call, for `time_stretch_launch`: clip b is
+    x[offsets[b] : offsets[b] + lens[b]] of the flat fp32 device tensor `x`; `table` is a numpy array of STRETCH_ENTRY rows
+    (stretch_table) whose out_frames are filled in here from lens and rate.  offsets, lens and table are HOST arrays: they
+    are checked against x here -- the kernels trust them -- and go up in one copy.  The stretched clips are laid out back
+    to back, each on a 16-byte boundary, in a new flat tensor (`out`, where given: flat fp32 on x's device, apart from x,
+    large enough).  Nothing is launched."""
+    import numpy as np
+    _lib_ready()
+    if not x.is_cuda:
+        raise _lib.S2IError("time_stretch runs on the MI355X kernels: x is on %s" % x.device)
+    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_contiguous() or x.data_ptr() % 16:
+        raise ValueError("time_stretch: x must be a flat contiguous 16-byte aligned fp32 tensor, got %s %s"
+                         % (x.dtype, tuple(x.shape)))
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    lens = np.ascontiguousarray(lens, dtype=np.int64).reshape(-1)
+    table = np.array(table, dtype=STRETCH_ENTRY).reshape(-1)
+    B = len(offsets)
+    if B < 1 or len(lens) != B or len(table) != B:
+        raise ValueError("time_stretch: offsets, lens and table must have one length >= 1, got %d, %d, %d"
+                         % (B, len(lens), len(table)))
+    if lens.min() < 0 or lens.max() > STRETCH_MAX_LEN or offsets.min() < 0 or int((offsets + lens).max()) > x.numel():
+        raise ValueError("time_stretch: a clip lies outside x (%d floats) or is longer than %d" % (x.numel(), STRETCH_MAX_LEN))
+    if np.any(offsets % 4):
+        raise ValueError("time_stretch: every clip must start on a 16-byte boundary")
+    rate = table["rate"]
+    if not np.all((rate == 1.0) | ((rate >= 0.25) & (rate <= 4.0))):       # a NaN fails both
+        raise ValueError("time_stretch: a rate must be 1 or lie in [0.25, 4], got %s" % rate.tolist())
+    on = (rate != 1.0) & (lens > 0)
+    frames = np.where(on, 1 + lens // STRETCH_HOP, 0)
+    want_len = np.where(rate == 1.0, lens, np.floor(lens / rate + 0.5)).astype(np.int64)
+    if np.any(table["out_len"] != want_len):
+        raise ValueError("time_stretch: out_len must be floor(n / rate + 0.5), got %s for %s" % (table["out_len"].tolist(), want_len.tolist()))
+    out_frames = np.where(on, np.ceil(frames / rate), 0).astype(np.int64)
+    table["out_frames"] = out_frames
+    padded = (want_len + 3) // 4 * 4
+    out_offsets = np.cumsum(padded) - padded
+    floats = max(int(padded.sum()), 4)
+    if out is None:
+        out = torch.empty(floats, dtype=torch.float32, device=x.device)
+    elif (out.dtype != torch.float32 or out.dim() != 1 or not out.is_contiguous() or out.device != x.device
+          or out.numel() < floats or out.data_ptr() % 16 or out.data_ptr() == x.data_ptr()):
+        raise ValueError("time_stretch: out must be a flat contiguous 16-byte aligned fp32 tensor of at least %d floats on %s, "
+                         "apart from x" % (floats, x.device))
+    # one upload: offsets | out offsets | table | lens, each part on a 16-byte boundary
+    at_out = (8 * B + 15) // 16 * 16
+    at_table = 2 * at_out
+    at_lens = at_table + 16 * B
+    image = np.zeros(at_lens + 4 * B, dtype=np.uint8)
+    image[:8 * B] = offsets.view(np.uint8)
+    image[at_out:at_out + 8 * B] = out_offsets.astype(np.int64).view(np.uint8)
+    image[at_table:at_lens] = table.view(np.uint8)
+    image[at_lens:] = lens.astype(np.int32).view(np.uint8)
+    image_d = torch.from_numpy(image).to(x.device)
+    base = image_d.data_ptr()
+    return dict(x=x, out=out, image=image_d, offsets=base, out_offsets=base + at_out, table=base + at_table,
+                lens=base + at_lens, B=B, max_len=max(int(lens.max()), 1), max_out_len=int(want_len.max()),
+                in_frames=int(frames.sum()), out_frames=int(out_frames.sum()), host_out_offsets=out_offsets,
+                host_out_lens=want_len)
+
+
+def time_stretch_launch(args):
+    """s2i_time_stretch on the current stream over `time_stretch_prepare`'s arguments: the five launches, after the one
+    allocation of their workspace.  Returns (out, out_offsets, out_lens), the last two int64 host arrays."""
+    lib = _lib.load()
+    x, out = args["x"], args["out"]
+    need = lib.s2i_time_stretch_workspace_bytes(args["B"], args["in_frames"], args["out_frames"])
+    if need == 0:
+        raise _lib.S2IError("s2i_time_stretch_workspace_bytes: %s" % lib.s2i_last_error().decode())
+    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=x.device)
+    check(lib.s2i_time_stretch(ptr(x), args["offsets"], args["lens"], args["B"], args["max_len"], args["table"],
+                               ptr(device_stretch_basis(x.device)), ptr(out), args["out_offsets"], args["max_out_len"],
+                               args["in_frames"], args["out_frames"], ptr(ws), ws.numel() * 4, stream()), "s2i_time_stretch")
+    return out, args["host_out_offsets"], args["host_out_lens"]
+
+
+def time_stretch(x, offsets, lens, table, out=None):
+    """The phase-vocoder time stretch of a ragged batch of waveforms: clip b of the flat fp32 device tensor `x` comes back
+    floor(n / rate + 0.5) samples long, its pitch unchanged (include/s2i_hip.h has the arithmetic); a clip whose rate is
+    exactly 1 is copied bit for bit.  `time_stretch_prepare` (checks, one upload) then `time_stretch_launch` (five
+    launches).  Returns (out, out_offsets, out_lens).  No autograd, no CPU fallback."""
+    return time_stretch_launch(time_stretch_prepare(x, offsets, lens, table, out))
 
 
 # ---- nearest-row search -------------------------------------------------------------------------------------------------

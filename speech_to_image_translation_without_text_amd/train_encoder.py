@@ -17,8 +17,8 @@ own way to run this training, run_audio_encoder.sh, is data-parallel, and here t
         --distributed --dataset birds --data_dir data/birds --output_dir output/encoder --epoch 1000 --bidirectional --jel_flag
 
 Every rank builds the same seeded model (or loads the same checkpoint) and rank 0's parameters and BatchNorm buffers are
-broadcast; --resident keeps the whole pool on every rank.  --specaug and --waveaug (speed, reverberation, white noise and
-babble on the training waveforms, wave_loader.py) are train_encoder_head's as well.
+broadcast; --resident keeps the whole pool on every rank.  --specaug and --waveaug (speed, tempo, pitch, reverberation, white noise
+and babble on the training waveforms, wave_loader.py) are train_encoder_head's as well.
 Not built: bf16, more than one LSTM layer (and so nn.LSTM's dropout).
 """
 import torch

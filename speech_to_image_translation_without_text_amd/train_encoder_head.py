@@ -49,7 +49,10 @@ checkpoints never see a mask.  Default '': off.
 the log-mel front end (wave_loader.py, ops.waveaug_policy): a speed factor drawn from the list, white noise and another
 training utterance (babble) each with its probability at a signal-to-noise ratio drawn from LO:HI dB.
 reverb=P@LO:HI@DLO:DHI adds a room between the speed and the noise: with probability P the clip is convolved on the GPU
-with an impulse response of T60 drawn from LO:HI seconds at a direct-to-reverberant ratio drawn from DLO:DHI dB.  It keeps the
+with an impulse response of T60 drawn from LO:HI seconds at a direct-to-reverberant ratio drawn from DLO:DHI dB.
+tempo=F/F/... and pitch=S/S/... vary the speaker: a drawn tempo factor in [0.5, 2] divides the duration at an unchanged
+pitch, a drawn number of semitones in [-12, 12] moves the pitch at an unchanged duration; both run a phase vocoder on the
+GPU (s2i_time_stretch) in front of the resampler, so the order is stretch, resample, reverb, noise.  It keeps the
 training split's 16 kHz samples in device memory (wave_loader.ResidentWaveSet; --waveaug_max_bytes refuses a pool above
 it) whether or not --resident is given; the test split stays as it is and is never perturbed.  The draws come from a
 counter-based generator keyed by --waveaug_seed (default --seed; the rank is added to either under --distributed) and counted by the
@@ -201,9 +204,10 @@ def get_parser(description="fine-tune the speech encoder's LSTM head (conv stack
                         "width of the frequency and time masks, `ratio` the largest share of an utterance one time mask "
                         "may take (ops.specaug_policy); default '': off")
     p.add_argument("--waveaug", type=str, default="",
-                   help="speed, reverberation and noise augmentation of every training utterance's waveform on the GPU, e.g. "
-                        "'speed=0.9/1.0/1.1,reverb=0.3@0.2:0.6@0:15,white=0.3@5:25,babble=0.2@0:15': speed factors, "
-                        "reverb=P@T60LO:T60HI@DRRLO:DRRHI in seconds and dB, white= and babble=P@SNRLO:SNRHI in dB "
+                   help="speed, tempo, pitch, reverberation and noise augmentation of every training utterance's waveform on the "
+                        "GPU, e.g. 'speed=0.9/1.0/1.1,reverb=0.3@0.2:0.6@0:15,white=0.3@5:25,babble=0.2@0:15': speed factors, "
+                        "reverb=P@T60LO:T60HI@DRRLO:DRRHI in seconds and dB, white= and babble=P@SNRLO:SNRHI in dB, "
+                        "tempo=F/F/... factors in [0.5, 2] (duration only) and pitch=S/S/... semitones in [-12, 12] (pitch only) "
                         "(ops.waveaug_policy); keeps the training split's samples in device memory; default '': off")
     p.add_argument("--waveaug_seed", type=int, default=None,
                    help="seed of --waveaug's draws (default: --seed); under --distributed the rank is added to it, whether "

@@ -1,12 +1,13 @@
 """The encoder's training utterances resident in device memory as 16 kHz waveforms, so that waveform-domain augmentation
-can run on them: speed perturbation through the resampler, room reverberation through s2i_reverb and additive noise /
-babble through s2i_wave_mix, in that order.
+can run on them: tempo and pitch through the phase vocoder s2i_time_stretch, speed (and the pitch's rate) through the
+resampler, room reverberation through s2i_reverb and additive noise / babble through s2i_wave_mix, in that order.
 
 `ResidentSpeechSet` (speech_loader.py) keeps finished log-mel rows, to which no waveform operation can be applied.
 `ResidentWaveSet` keeps the fp32 samples of every utterance a draw can return -- those with at least 64 frames -- back to
 back in one flat device buffer, each clip on a 16-byte boundary, so that `s2i_pcm_resample` reads a clip in place
 (raw = the pool, format S2I_PCM_F32, byte offset = the clip's start).  A batch is: one resample launch per distinct speed
-(speed 1.0 is the kernel's bypass L = M = 1, which then is the gather), the two reverberation launches where a clip drew
+(speed 1.0 is the kernel's bypass L = M = 1, which then is the gather; where a clip drew a tempo or a pitch, the five
+stretch launches come first and the resampler reads their buffer instead of the pool), the two reverberation launches where a clip drew
 a room, the mix launches where a noise term is on, and the three log-mel launches.  fp32 is the stored type because it reproduces the host path bit for bit, stereo mixdown and the
 resampled files of `resample=True` included: with augmentation off a batch equals `SplitData.batches` and
 `ResidentSpeechSet.batches` under the same `random` seed (tests/test_waveaug_gpu.py).
@@ -92,6 +93,16 @@ def render(pool, in_offsets, in_lens, rate, out_lens):
     return flat, out_offsets
 
 
+def _stretch(pool, offsets, lens, plan):
+    """(buffer, offsets, lens) the resampler reads: the pool's clips themselves, or -- where a clip of the batch drew a
+    tempo or a pitch that needs the phase vocoder -- the whole batch written by s2i_time_stretch into a new flat buffer,
+    the clips with rate 1 copied bit for bit"""
+    from . import ops
+    if plan is None or "stretch_rate" not in plan or not np.any(plan["stretch_rate"] != 1.0):
+        return pool, offsets, lens
+    return ops.time_stretch(pool, offsets, lens, ops.stretch_table(plan))
+
+
 def _reverberate(flat, offsets, plan, aug, step):
     """`flat` under the plan's room impulse responses (a new buffer), or `flat` itself where no clip drew one"""
     from . import ops
@@ -101,13 +112,13 @@ def _reverberate(flat, offsets, plan, aug, step):
 
 
 def perturb(waves, aug, device, step=0, uids=None):
-    """The waveforms (16 kHz mono: numpy arrays or device tensors) under `aug`, without a pool of other utterances: speed,
-    reverberation and white noise; babble= is refused.  Clip k draws with uid uids[k] (default: k).  Returns fp32 device tensors, views of
+    """The waveforms (16 kHz mono: numpy arrays or device tensors) under `aug`, without a pool of other utterances: tempo,
+    pitch, speed, reverberation and white noise; babble= is refused.  Clip k draws with uid uids[k] (default: k).  Returns fp32 device tensors, views of
     one flat buffer, which `audio.log_mel` takes unchanged."""
     from . import _lib, ops
     if aug.policy["babble"] is not None:
         raise ValueError("babble= draws its interferers from a pool of training utterances (wave_loader.ResidentWaveSet), "
-                         "which an extraction does not have: use speed=, reverb= and white= here")
+                         "which an extraction does not have: use tempo=, pitch=, speed=, reverb= and white= here")
     _lib.load()
     _lib.require_device()
     dev = torch.device(device)
@@ -125,7 +136,7 @@ def perturb(waves, aug, device, step=0, uids=None):
             for o, w in zip(offsets, waves):
                 pool[o:o + len(w)] = torch.as_tensor(w).to(device=dev, dtype=torch.float32)
         plan = ops.waveaug_plan(aug.policy, aug.seed, step, np.arange(len(waves)) if uids is None else uids, lens)
-        flat, out_offsets = render(pool, offsets, lens, plan["rate"], plan["out_len"])
+        flat, out_offsets = render(*_stretch(pool, offsets, lens, plan), plan["rate"], plan["out_len"])
         flat = _reverberate(flat, out_offsets, plan, aug, step)
         if np.any(plan["g_white"] != 0):
             ops.wave_mix(flat, out_offsets, plan["out_len"], ops.wave_mix_table(plan), aug.seed, step)
@@ -242,7 +253,7 @@ class ResidentWaveSet:
             plan = ops.waveaug_plan(aug.policy, aug.seed, step, uids, lens_in, self.stored_lens, self.stored_q, self.T)
             rate, out_lens = plan["rate"], plan["out_len"]
         with torch.cuda.device(self.device):
-            flat, out_offsets = render(self.pool, self.offsets[flat_ids], lens_in, rate, out_lens)
+            flat, out_offsets = render(*_stretch(self.pool, self.offsets[flat_ids], lens_in, plan), rate, out_lens)
             flat = _reverberate(flat, out_offsets, plan, aug, step)
             if plan is not None and (np.any(plan["g_white"] != 0) or np.any(plan["g_babble"] != 0)):
                 table = ops.wave_mix_table(plan, self.stored_offsets, self.stored_lens)
