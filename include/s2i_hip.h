@@ -762,6 +762,36 @@ int s2i_adam_l2_step(float* p, const float* g, float* m, float* v, long long n, 
 /* *counter += 1 on the stream (device-resident Adam step count, so a captured hipGraph of the
    train step replays with the right bias correction) */
 int s2i_increment(int* counter, void* stream);
+/* Gradient-norm clipping and the non-finite guard of the fused optimiser: three launches, nothing read by the host.
+   The layout is trainer.FlatNet's: tensor s holds sizes[s] >= 1 elements from element offsets[s] (a multiple of 4) of the flat
+   buffer g of n elements, cut into chunks of S2I_GRAD_CHUNK elements from its first element on; chunk0[s] is the index of
+   its first chunk among all chunks and chunk0[S] = nchunks.  offsets, sizes [S] and chunk0 [S + 1] are device arrays.
+   s2i_grad_sumsq: partials[c] = sum of the squares of chunk c, every element converted to fp64 first (the square is then
+   exact and no sum over fp32 data overflows or underflows), one block per chunk, 16-byte loads where the chunk's first
+   element is 16-byte aligned, elements between tensors never read, no atomics; the order of the additions is a function of
+   the layout alone (csrc/s2i_optim.hip states it), so equal inputs give equal bits.  A chunk that would leave [0, n) is
+   not read and its partial is NaN.
+   s2i_grad_clip_scale (one block): seg[s] = sum of tensor s's partials, total = sum of seg in ascending s,
+   norm = sqrt(total) |gscale|, coef = min(1, max_norm / (norm + 1e-6)) if max_norm > 0 else 1 (torch.nn.utils.clip_grad_norm_),
+   scale_dev[0] = (float)(gscale coef), apply_dev[0] = isfinite(total); if that holds and step_dev is given, step_dev[0] += 1
+   (it stands in for s2i_increment).  stats, S2I_GRAD_STATS_HEAD + 2 S doubles, zeroed by the caller before the first call:
+   [0] norm [1] coef [2] scale [3] apply of this call; since the caller last zeroed them [4] applied updates, [5] those with
+   coef < 1, [6] skipped ones, [7] sum and [8] maximum of norm over the applied ones; [9] total; [HEAD + s] the norm of
+   tensor s, sqrt(seg[s]) |gscale|; [HEAD + S + s] seg[s]. */
+#define S2I_GRAD_CHUNK 4096
+#define S2I_GRAD_STATS_HEAD 16
+int s2i_grad_sumsq(const float* g, long long n, const long long* offsets, const long long* sizes, const long long* chunk0,
+                   int S, long long nchunks, double* partials, void* stream);
+int s2i_grad_clip_scale(const double* partials, const long long* chunk0, int S, double gscale, double max_norm, int* step_dev,
+                        float* scale_dev, int* apply_dev, double* stats, void* stream);
+/* s2i_adam_step / s2i_adam_l2_step with the step count, gscale and a flag read from the device: gscale_dev[0] takes
+   gscale's place, and with apply_dev[0] == 0 nothing is stored: p, m and v stay as they are, weight decay included.  With
+   gscale_dev[0] == gscale the results are those of the host-value entry points bit for bit. */
+int s2i_adam_step_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+                      float eps, const int* step_dev, const float* gscale_dev, const int* apply_dev, void* stream);
+int s2i_adam_l2_step_dev(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, const int* step_dev, const float* gscale_dev, const int* apply_dev,
+                         void* stream);
 /* avg = decay*avg + (1-decay)*p */
 int s2i_ema_update(float* avg, const float* p, long long n, float decay, void* stream);
 /* y = x * a_dev[0] (the scalar lives on the device: no host synchronisation) */

@@ -28,6 +28,7 @@ RESAMPLE_MAX_WINDOW = 13826
 TOPK_MAX = 64
 RANK_GATHER, RANK_COUNT = 0, 1      # s2i_rank_rows modes (S2I_RANK_*)
 DIFFAUG_COLOR, DIFFAUG_TRANSLATION, DIFFAUG_CUTOUT = 1, 2, 4
+GRAD_CHUNK, GRAD_STATS_HEAD = 4096, 16      # S2I_GRAD_CHUNK, S2I_GRAD_STATS_HEAD
 ABI_VERSION = 7
 # s2i_wgrad_plan_query: the WgKernel values of csrc/s2i_igemm.h in order, and the twelve outputs
 WGRAD_KERNELS = ("f32-128x128", "f32-128x64", "f32-128x32", "f32-64x64", "f32-256x128", "f32-256x256", "f32-96x64", "f32-96x32",
@@ -196,6 +197,10 @@ _SIGNATURES = {
     "s2i_adam_step": (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_int, P, c_float, P]),
     "s2i_adam_l2_step": (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_int, P, c_float, P]),
     "s2i_increment": (c_int, [P, P]),
+    "s2i_grad_sumsq": (c_int, [P, c_ll, P, P, P, c_int, c_ll, P, P]),
+    "s2i_grad_clip_scale": (c_int, [P, P, c_int, ctypes.c_double, ctypes.c_double, P, P, P, P, P]),
+    "s2i_adam_step_dev": (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, P, P, P, P]),
+    "s2i_adam_l2_step_dev": (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, P, P, P, P]),
     "s2i_ema_update": (c_int, [P, P, c_ll, c_float, P]),
     "s2i_scale_dev": (c_int, [P, P, c_ll, P, P]),
     "s2i_axpby": (c_int, [P, P, c_ll, c_float, c_float, P]),

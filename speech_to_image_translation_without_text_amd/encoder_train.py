@@ -33,6 +33,22 @@ generator state: `steps` is already in state_dict(), and a trainer that loads a 
 A checkpoint without training state (save(); the CLIs' plain --resume epoch_N.pth) restarts the counter at 0, so its
 masks repeat the run's first ones: that path carries no Adam moments either and was never exact.  step_features, embed,
 evaluate and save never see a mask.
+
+`clip_grad=F` (> 0), `accum=N` (> 1) and `skip_nonfinite=True` are off by default, and then no launch, allocation or bit
+of the step changes; any of them implies fused_adam.  With clip_grad or skip_nonfinite the optimiser step is
+FlatNet._adam_guarded: one fixed-order fp64 reduction over the flat gradient buffer (ops.grad_sumsq), one small launch that
+keeps the norm, torch.nn.utils.clip_grad_norm_'s coefficient and the decision to apply on the device and counts the Adam step
+(ops.grad_clip_scale), and the Adam launch that reads them: no host round trip, bit-reproducible.  The norm is that of the
+gradient the optimiser uses, behind 1 / (world * accum).  A gradient whose sum of squares is not finite (a NaN or an inf
+anywhere in it) is skipped on that path, with or without clip_grad: parameters, moments and the Adam step stay bit for bit as
+they were, weight decay included, and the skip is counted; skip_nonfinite selects the path without clipping.
+grad_stats() reads the record.  `accum=N`: the flat gradient buffer is zeroed before the first micro-batch of a group only
+and autograd adds the others into it; the all-reduce and the optimiser step follow the N-th, scaled by 1 / (world * N);
+end_epoch flushes an incomplete group of k by 1 / (world * k), so no gradient is pending at an epoch boundary.  `steps`
+keeps counting step() calls (the augmentations' counter), `updates` counts optimiser steps, BatchNorm's running statistics
+move with every micro-batch as under torch.  Accumulation is not a larger batch: the joint-embedding loss takes its
+negatives from the micro-batch, so N micro-batches of B give the mean of N losses over B, not one loss over N * B, and
+train-mode BatchNorm normalises each micro-batch by its own statistics.
 """
 import copy
 import warnings
@@ -46,16 +62,21 @@ from . import _lib, ops, retrieval
 class HeadTrainer:
     def __init__(self, model, lr=1e-3, weight_decay=1e-5, step_size=30, gamma=0.2, loss_diff=1, loss_same=1, jel=True,
                  l1=False, lambda_l1=1, distill=False, distill_T=2, lambda_distill=1, fused_adam=False, distributed=False,
-                 specaug='', specaug_seed=0):
+                 specaug='', specaug_seed=0, clip_grad=0.0, accum=1, skip_nonfinite=False):
         if model.rnn_layers != 1:
             raise _lib.S2IError("HeadTrainer supports rnn_layers=1 (the reference's default)")
+        self.clip_grad, self.accum, self.skip_nonfinite = float(clip_grad), int(accum), bool(skip_nonfinite)
+        if not self.clip_grad >= 0.0 or self.accum < 1:
+            raise ValueError("clip_grad must be >= 0 (0: off) and accum >= 1, got %r and %r" % (clip_grad, accum))
+        self.guarded = self.clip_grad > 0.0 or self.skip_nonfinite      # the optimiser step is FlatNet's three-launch one
         self.model = model.eval()
         self.distributed = bool(distributed)
         self.world = torch.distributed.get_world_size() if self.distributed else 1
         self.step_size, self.gamma, self.epoch, self.steps = int(step_size), gamma, 0, 0
+        self.updates, self.pending = 0, 0       # optimiser steps (skipped ones included); micro-batches in the open group
         self.specaug, self.specaug_seed = ops.specaug_policy(specaug), int(specaug_seed)      # None: off
         self.flat = self.optimizer = self.scheduler = None
-        if fused_adam or self.distributed:
+        if fused_adam or self.distributed or self.guarded or self.accum > 1:
             from .trainer import FlatNet
             self.flat = FlatNet(model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=weight_decay,
                                 params=self._trained())
@@ -116,15 +137,35 @@ class HeadTrainer:
             self.optimizer.zero_grad(set_to_none=True)
             loss["loss"].backward()
             self.optimizer.step()
+            self.updates += 1
         else:
-            self.flat.zero_grad()           # one memset; never set_to_none, which would detach the views
-            loss["loss"].backward()
-            if self.distributed:            # on the current stream, behind the backward's launches
-                torch.distributed.all_reduce(self.flat.g, op=torch.distributed.ReduceOp.SUM)
-            self.flat.adam(1.0 / self.world)
-            self._stale()
+            if self.pending == 0:
+                self.flat.zero_grad()       # one memset; never set_to_none, which would detach the views
+            loss["loss"].backward()         # a group's further micro-batches are added into the flat buffer by autograd
+            self.pending += 1
+            if self.pending >= self.accum:
+                self._update()
         self.steps += 1
         return {k: v.detach() for k, v in loss.items()}
+
+    def _update(self):
+        """The optimiser step on the `pending` micro-batches summed in the flat gradient buffer, scaled by
+        1 / (world * pending).  Under `distributed` the norm is taken behind the all-reduce, on a buffer every rank holds
+        alike: all ranks clip by the same coefficient and skip together, a non-finite value on one rank reaching all of them
+        through the sum."""
+        if self.distributed:            # on the current stream, behind the backward's launches
+            torch.distributed.all_reduce(self.flat.g, op=torch.distributed.ReduceOp.SUM)
+        if self.guarded:
+            self.flat.adam(1.0 / (self.world * self.pending), max_norm=self.clip_grad, guard=True)
+        else:
+            self.flat.adam(1.0 / (self.world * self.pending))
+        self.pending = 0
+        self.updates += 1
+        self._stale()
+
+    def grad_stats(self, reset=False):
+        """FlatNet.grad_stats of the guarded step (clip_grad or skip_nonfinite; one synchronisation), else None."""
+        return self.flat.grad_stats(reset) if self.guarded else None
 
     def step(self, mel_nhwc, cap_lens, image_feature, label):
         """Sort by length, conv features, lstm_sentence, the loss, backward, Adam.  Returns the loss dict (device tensors:
@@ -137,7 +178,10 @@ class HeadTrainer:
         return self.step_features(self.features(mel_nhwc), cap_lens, image_feature, label)
 
     def end_epoch(self):
-        """StepLR: the learning rate is multiplied by gamma every step_size epochs."""
+        """StepLR: the learning rate is multiplied by gamma every step_size epochs.  An incomplete accumulation group of k
+        micro-batches is flushed first, as an optimiser step scaled by 1 / (world * k) at the epoch's learning rate."""
+        if self.pending:
+            self._update()
         self.epoch += 1
         if self.flat is None:
             self.scheduler.step()
@@ -176,16 +220,27 @@ class HeadTrainer:
         `lr`, and `optimizer`, which is always a torch.optim.Adam.state_dict() over the trained parameters in _trained()
         order -- torch's own, or with fused_adam the flat moments and step count in that form
         (train_state.flat_to_adam_state) -- so a state written by either kind of trainer loads into the other, and into the
-        reference's resume_model."""
+        reference's resume_model.  With clip_grad, accum or skip_nonfinite on, `updates` counts the optimiser steps and `skipped` those of them the non-finite guard
+        dropped; the Adam `step` in `optimizer` is the number of applied updates, updates - skipped.  A state is taken between
+        accumulation groups (end_epoch closes an open one); with micro-batches pending it is refused."""
         from . import train_state
+        if self.pending:
+            raise ValueError("state_dict: %d micro-batches of an accumulation group are pending; call end_epoch() first"
+                             % self.pending)
+        skipped = 0
         if self.flat is None:
             opt = train_state.to_cpu(self.optimizer.state_dict())
         else:
             f = self.flat
-            opt = train_state.flat_to_adam_state(f.m.cpu(), f.v.cpu(), f.step_count, [tuple(p.shape) for p in f.params],
+            if self.guarded:        # before the first guarded step there is no record yet: the count a loaded state brought
+                skipped = f.grad_stats()["skipped_total"] if f.clip is not None else f.skipped_before
+            opt = train_state.flat_to_adam_state(f.m.cpu(), f.v.cpu(), f.sync_step_count(), [tuple(p.shape) for p in f.params],
                                                  f.offsets, f.lr, f.betas, f.eps, f.weight_decay)
-        return {"state_dict": {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
-                "epoch": int(self.epoch), "steps": int(self.steps), "lr": float(self.lr), "optimizer": opt}
+        state = {"state_dict": {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
+                 "epoch": int(self.epoch), "steps": int(self.steps), "lr": float(self.lr), "optimizer": opt}
+        if self.guarded or self.accum > 1:      # with the options off the state has the keys it always had
+            state.update(updates=int(self.updates), skipped=int(skipped))
+        return state
 
     def load_state_dict(self, state):
         """Inverse of state_dict(), in place: with fused_adam the parameters stay views of the flat buffer.  The learning
@@ -193,6 +248,7 @@ class HeadTrainer:
         from . import train_state
         self.model.load_state_dict(state["state_dict"])
         self.epoch, self.steps = int(state["epoch"]), int(state["steps"])
+        self.updates, self.pending = int(state.get("updates", self.steps)), 0
         lr = float(state["lr"])
         if self.flat is None:
             # a copy: torch keeps the `step` tensors it is handed and increments them in place
@@ -210,6 +266,9 @@ class HeadTrainer:
                 f.v.copy_(v)
             f.step_count = step
             f.step_dev.fill_(step)
+            f.skipped_before = int(state.get("skipped", 0))
+            if f.clip is not None:
+                f.clip.reset_stats()
             f.lr = lr
             ops.refresh_packed(f.params)
             ops.invalidate_derived(f.params)

@@ -1774,6 +1774,115 @@ def increment(counter):
     check(lib.s2i_increment(ptr(counter), stream()), "s2i_increment")
 
 
+# ---- gradient norm, clip coefficient and the non-finite guard (include/s2i_hip.h) ---------------------------------------------
+GRAD_CHUNK = _lib.GRAD_CHUNK
+GRAD_STATS_HEAD = _lib.GRAD_STATS_HEAD
+GRAD_STATS_FIELDS = ("norm", "coef", "scale", "apply", "updates", "clipped", "skipped", "norm_sum", "norm_max", "sumsq")
+
+
+def grad_chunk_table(offsets, sizes):
+    """The chunks s2i_grad_sumsq cuts a flat layout into -> [(first element, length, tensor)], in block order: tensor s from
+    offsets[s] on in pieces of GRAD_CHUNK, the last one shorter.  Refuses what does not describe a FlatNet layout: an empty
+    tensor, an offset that is not a multiple of 4, tensors that overlap or are out of order."""
+    offsets, sizes = [int(o) for o in offsets], [int(n) for n in sizes]
+    if not sizes or len(offsets) != len(sizes):
+        raise ValueError("grad_chunk_table: %d offsets for %d sizes" % (len(offsets), len(sizes)))
+    table, end = [], 0
+    for s, (o, n) in enumerate(zip(offsets, sizes)):
+        if n < 1 or o % 4 or o < end:
+            raise ValueError("grad_chunk_table: tensor %d (offset %d, %d elements) behind element %d: sizes must be >= 1, "
+                             "offsets multiples of 4 and ascending without overlap" % (s, o, n, end))
+        table += [(o + c, min(GRAD_CHUNK, n - c), s) for c in range(0, n, GRAD_CHUNK)]
+        end = o + n
+    return table
+
+
+class GradLayout:
+    """A flat layout's device-side description and the workspace of the three-launch clipped step, allocated once:
+    `offsets`, `sizes` [S] and `chunk0` [S + 1] (int64), `partials` [chunks] and `stats` [GRAD_STATS_HEAD + 2 S] (fp64),
+    `scale` [1] (fp32) and `apply` [1] (int32).  `total` is the length of the buffers the layout describes."""
+
+    def __init__(self, offsets, sizes, total, device):
+        table = grad_chunk_table(offsets, sizes)
+        self.S, self.total, self.nchunks = len(sizes), int(total), len(table)
+        if table[-1][0] + table[-1][1] > self.total:
+            raise ValueError("GradLayout: the layout ends at element %d of a buffer of %d" % (table[-1][0] + table[-1][1],
+                                                                                            self.total))
+        chunk0 = [0]
+        for n in sizes:
+            chunk0.append(chunk0[-1] + -(-int(n) // GRAD_CHUNK))
+        i64 = lambda v: torch.tensor([int(x) for x in v], dtype=torch.int64, device=device)
+        self.offsets, self.sizes, self.chunk0 = i64(offsets), i64(sizes), i64(chunk0)
+        self.partials = torch.zeros(self.nchunks, dtype=torch.float64, device=device)
+        self.stats = torch.zeros(GRAD_STATS_HEAD + 2 * self.S, dtype=torch.float64, device=device)
+        self.scale = torch.zeros(1, dtype=torch.float32, device=device)
+        self.apply = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def read_stats(self):
+        """The stats record on the host (one synchronisation) -> dict of GRAD_STATS_FIELDS, `tensor_norms` and
+        `tensor_sumsq` (lists of S)."""
+        st = self.stats.cpu().tolist()
+        out = dict(zip(GRAD_STATS_FIELDS, st))
+        for k in ("apply", "updates", "clipped", "skipped"):
+            out[k] = int(out[k])
+        out["tensor_norms"] = st[GRAD_STATS_HEAD:GRAD_STATS_HEAD + self.S]
+        out["tensor_sumsq"] = st[GRAD_STATS_HEAD + self.S:GRAD_STATS_HEAD + 2 * self.S]
+        return out
+
+    def reset_stats(self):
+        """Zero the running aggregates (updates, clipped, skipped, norm_sum, norm_max)."""
+        self.stats[4:9].zero_()
+
+
+def _flat_f32(t, n, what):
+    if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise _lib.S2IError("%s: expected a contiguous fp32 buffer of %d elements, got %s %s" % (what, n, tuple(t.shape), t.dtype))
+
+
+def grad_sumsq(g, layout):
+    """layout.partials[c] = fp64 sum of squares of chunk c of the flat gradient buffer g (s2i_grad_sumsq)."""
+    lib = _lib_ready()
+    _flat_f32(g, layout.total, "grad_sumsq")
+    check(lib.s2i_grad_sumsq(ptr(g), g.numel(), ptr(layout.offsets), ptr(layout.sizes), ptr(layout.chunk0), layout.S,
+                             layout.nchunks, ptr(layout.partials), stream()), "s2i_grad_sumsq")
+
+
+def grad_clip_scale(layout, gscale, max_norm=0.0, step_dev=None):
+    """Finish grad_sumsq on the device (s2i_grad_clip_scale): layout.scale[0] = float(gscale * coef) with clip_grad_norm_'s
+    coef for max_norm > 0 (0: coef = 1), layout.apply[0] = the sum is finite, step_dev[0] += 1 if it is; layout.stats."""
+    lib = _lib_ready()
+    gscale, max_norm = float(gscale), float(max_norm)
+    if not (max_norm >= 0.0) or gscale != gscale:
+        raise _lib.S2IError("grad_clip_scale: max_norm must be >= 0 (0: no clipping), got %r" % max_norm)
+    if step_dev is not None and (step_dev.dtype != torch.int32 or step_dev.numel() != 1):
+        raise _lib.S2IError("grad_clip_scale: step_dev is one int32")
+    check(lib.s2i_grad_clip_scale(ptr(layout.partials), ptr(layout.chunk0), layout.S, gscale, max_norm, ptr(step_dev),
+                                  ptr(layout.scale), ptr(layout.apply), ptr(layout.stats), stream()), "s2i_grad_clip_scale")
+
+
+def _dev_scalars(step_dev, scale_dev, apply_dev, what):
+    for t, dt in ((step_dev, torch.int32), (scale_dev, torch.float32), (apply_dev, torch.int32)):
+        if t is None or t.dtype != dt or t.numel() != 1:
+            raise _lib.S2IError("%s: step_dev (int32), scale_dev (fp32) and apply_dev (int32) are one-element device tensors"
+                                % what)
+
+
+def adam_step_dev(p, g, m, v, lr, beta1, beta2, eps, step_dev, scale_dev, apply_dev):
+    """adam_step with the step count, gscale (scale_dev[0]) and the apply flag on the device; apply_dev[0] == 0 stores nothing."""
+    lib = _lib_ready()
+    _dev_scalars(step_dev, scale_dev, apply_dev, "adam_step_dev")
+    check(lib.s2i_adam_step_dev(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, ptr(step_dev),
+                                ptr(scale_dev), ptr(apply_dev), stream()), "s2i_adam_step_dev")
+
+
+def adam_l2_step_dev(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step_dev, scale_dev, apply_dev):
+    """adam_l2_step with the step count, gscale (scale_dev[0]) and the apply flag on the device."""
+    lib = _lib_ready()
+    _dev_scalars(step_dev, scale_dev, apply_dev, "adam_l2_step_dev")
+    check(lib.s2i_adam_l2_step_dev(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, weight_decay,
+                                   ptr(step_dev), ptr(scale_dev), ptr(apply_dev), stream()), "s2i_adam_l2_step_dev")
+
+
 
 
 # ---- evaluation output ---------------------------------------------------------------------------------------------

@@ -60,6 +60,13 @@ trainer's step counter, with the batch position as the utterance's id: they take
 --state_every state continues the sequence exactly.  A plain --resume epoch_N.pth restarts the counter at 0.  With
 --specaug the waveform is perturbed first and the masks go over its log-mel.  Default '': off, and then nothing of it is
 imported, drawn, launched or allocated.
+--clip_grad F clips the global gradient norm to F, --skip_nonfinite skips (and counts) an optimiser step whose gradient
+holds a NaN or an inf, --accum N sums the gradients of N batches per optimiser step (an epoch's last, incomplete group is
+stepped at the epoch's end); each implies --fused_adam, and all of it runs inside the fused optimiser with nothing read
+back per step (encoder_train.py).  With --clip_grad or --skip_nonfinite the epoch line gains
+`gnorm mean/max A/B, clipped k/n, skipped s` (one read per epoch: the norm of the gradient the optimiser used over the n
+applied steps, how many of them were clipped, how many steps were skipped), and state.pth's `meta` carries `steps`,
+`updates` and `skipped`.  Defaults 0, 1 and off: every line and file is then what it was.
 """
 import argparse
 import json
@@ -214,6 +221,14 @@ def get_parser(description="fine-tune the speech encoder's LSTM head (conv stack
                         "it was given or defaulted, so that the ranks draw independently")
     p.add_argument("--waveaug_max_bytes", type=int, default=None,
                    help="refuse a waveform pool above this many bytes (default: no limit)")
+    p.add_argument("--clip_grad", type=float, default=0.0,
+                   help="clip the global gradient norm to this value inside the fused optimiser (clip_grad_norm_'s rule, on "
+                        "the device); 0 = off; implies --fused_adam")
+    p.add_argument("--accum", type=int, default=1,
+                   help="accumulate the gradients of this many batches per optimiser step; implies --fused_adam")
+    p.add_argument("--skip_nonfinite", action="store_true", default=False,
+                   help="skip an optimiser step whose gradient holds a NaN or an inf (parameters, moments and the Adam step "
+                        "stay as they were) and count it; implies --fused_adam")
     return p
 
 
@@ -222,6 +237,10 @@ def check_args(args):
         raise SystemExit("--batch_size, --epoch and --eval_every must be >= 1")
     if args.state_every < 0:
         raise SystemExit("--state_every must be >= 0")
+    if not getattr(args, "clip_grad", 0.0) >= 0.0:
+        raise SystemExit("--clip_grad must be >= 0 (0 = off)")
+    if getattr(args, "accum", 1) < 1:
+        raise SystemExit("--accum must be >= 1")
     try:
         ops.specaug_policy(getattr(args, "specaug", ""))
     except ValueError as e:
@@ -238,11 +257,14 @@ def trainer_kwargs(args):
     specaug_seed = args.seed or 0
     if args.distributed and torch.distributed.is_available() and torch.distributed.is_initialized():
         specaug_seed += torch.distributed.get_rank()
+    clip_grad, accum, skip = getattr(args, "clip_grad", 0.0), getattr(args, "accum", 1), getattr(args, "skip_nonfinite", False)
     return dict(lr=args.learning_rate, weight_decay=1e-5, step_size=args.lr_scheduler_step_size,
                 gamma=args.lr_scheduler_gamma, loss_diff=args.loss_diff, loss_same=args.loss_same, jel=args.jel_flag,
                 l1=args.l1_flag, lambda_l1=args.lambda_l1, distill=args.distill_flag, distill_T=args.distill_T,
-                lambda_distill=args.lambda_distill, fused_adam=args.fused_adam, distributed=args.distributed,
-                specaug=getattr(args, "specaug", ""), specaug_seed=specaug_seed)
+                lambda_distill=args.lambda_distill,
+                fused_adam=bool(args.fused_adam or clip_grad > 0 or accum > 1 or skip), distributed=args.distributed,
+                specaug=getattr(args, "specaug", ""), specaug_seed=specaug_seed, clip_grad=clip_grad, accum=accum,
+                skip_nonfinite=skip)
 
 
 def make_resident(split, name, dev, workers, say=print, resample=False):
@@ -314,7 +336,10 @@ def write_state(trainer, path, epoch, best, distributed):
     if distributed and torch.distributed.get_rank() != 0:
         return
     st = trainer.state_dict()
-    train_state.atomic_save({"format": train_state.FORMAT, "meta": {"epoch": int(epoch), "best_accu": float(best)},
+    meta = {"epoch": int(epoch), "best_accu": float(best)}
+    if "updates" in st:     # --clip_grad, --accum, --skip_nonfinite: step() calls, optimiser steps and skipped ones part ways
+        meta.update(steps=st["steps"], updates=st["updates"], skipped=st["skipped"])
+    train_state.atomic_save({"format": train_state.FORMAT, "meta": meta,
                              "state_dict": st["state_dict"], "optimizer": st["optimizer"], "rng": rng}, path)
 
 
@@ -329,8 +354,11 @@ def resume_state(trainer, ckpt, path, rank, world):
     opt, meta = ckpt["optimizer"], ckpt.get("meta", {})
     steps = max([int(e["step"]) for e in opt["state"].values()] or [0])
     epoch = int(meta.get("epoch", 0))
-    trainer.load_state_dict({"state_dict": ckpt["state_dict"], "epoch": epoch, "steps": steps,
-                             "lr": opt["param_groups"][0]["lr"], "optimizer": opt})
+    state = {"state_dict": ckpt["state_dict"], "epoch": epoch, "steps": int(meta.get("steps", steps)),
+             "lr": opt["param_groups"][0]["lr"], "optimizer": opt}
+    if "updates" in meta:
+        state.update(updates=int(meta["updates"]), skipped=int(meta.get("skipped", 0)))
+    trainer.load_state_dict(state)
     if rng is not None:
         random.setstate(train_state.as_tuple(rng))
     return epoch + 1, float(meta.get("best_accu", -1.0))
@@ -407,7 +435,12 @@ def run(trainer, args, dev):
             seen += len(cap_lens)
         trainer.end_epoch()
         mean_loss, mean_accu = (total / seen).tolist()
-        say("epoch %d: loss %.4f, batch accu %.2f" % (epoch, mean_loss, mean_accu))
+        line = "epoch %d: loss %.4f, batch accu %.2f" % (epoch, mean_loss, mean_accu)
+        gs = trainer.grad_stats(reset=True) if hasattr(trainer, "grad_stats") else None      # one read per epoch
+        if gs is not None:
+            line += ", gnorm mean/max %.4g/%.4g, clipped %d/%d, skipped %d" % (gs["norm_mean"], gs["norm_max"], gs["clipped"],
+                                                                              gs["updates"], gs["skipped"])
+        say(line)
         scheduled, last = epoch % args.eval_every == 0, epoch == args.epoch
         if scheduled:
             best = evaluate(epoch, best)

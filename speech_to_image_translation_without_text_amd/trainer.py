@@ -239,6 +239,7 @@ class FlatNet:
         self.lr, self.betas, self.eps = lr, betas, eps
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.step_count = 0
+        self.clip, self.skipped_before = None, 0     # ops.GradLayout of the guarded step, built at its first use
         ops.refresh_packed(self.params)
 
     def zero_grad(self):
@@ -251,7 +252,11 @@ class FlatNet:
         for p in self.params:
             p.requires_grad_(flag)
 
-    def adam(self, gscale=1.0):
+    def adam(self, gscale=1.0, max_norm=None, guard=False):
+        """One optimiser step on gscale * g.  With `max_norm` (> 0) or `guard` it is the three-launch guarded step
+        (_adam_guarded); without them, the default and all the GAN trainer uses, s2i_increment and one Adam launch."""
+        if max_norm or guard:
+            return self._adam_guarded(gscale, float(max_norm or 0.0))
         ops.increment(self.step_dev)
         self.step_count += 1
         if self.weight_decay:
@@ -261,6 +266,50 @@ class FlatNet:
             ops.adam_step(self.p, self.g, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
                           step_dev=self.step_dev, gscale=gscale)
         ops.refresh_packed(self.params)
+
+    def _adam_guarded(self, gscale, max_norm):
+        """ops.grad_sumsq over the flat gradient buffer, ops.grad_clip_scale (the norm of gscale * g, clip_grad_norm_'s
+        coefficient for max_norm > 0, the skip decision and the step counter's increment, all on the device) and the Adam
+        launch that reads them.  A gradient whose sum of squares is not finite is skipped whether or not max_norm is set: p,
+        m, v and the step counter stay as they were.  Nothing is read back here, so `step_count` lags until sync_step_count()."""
+        if self.clip is None:
+            self.clip = ops.GradLayout(self.offsets, self.sizes, self.total, self.p.device)
+        c = self.clip
+        ops.grad_sumsq(self.g, c)
+        ops.grad_clip_scale(c, gscale, max_norm, self.step_dev)
+        if self.weight_decay:
+            ops.adam_l2_step_dev(self.p, self.g, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
+                                 self.weight_decay, self.step_dev, c.scale, c.apply)
+        else:
+            ops.adam_step_dev(self.p, self.g, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps,
+                              self.step_dev, c.scale, c.apply)
+        ops.refresh_packed(self.params)
+
+    def sync_step_count(self):
+        """`step_count` as the device counts it: behind guarded steps the number of applied updates (one synchronisation;
+        without a guarded step the host count is already right and nothing is read)."""
+        if self.clip is not None:
+            self.step_count = int(self.step_dev)
+        return self.step_count
+
+    def grad_stats(self, reset=False):
+        """The guarded steps' record on the host (one synchronisation): the last step's `norm` (of the gradient the
+        optimiser used, gscale included), `coef`, `scale` and `apply`; since the last reset `updates` (applied), `clipped`
+        (coef < 1), `skipped`, `norm_mean` and `norm_max` over the applied ones; `skipped_total` since construction or
+        load_state_dict; `tensor_norms`, the last step's norm per parameter name.  None before the first guarded step."""
+        if self.clip is None:
+            return None
+        st = self.clip.read_stats()
+        names = {id(p): n for n, p in self.net.named_parameters()} if self.net is not None else {}
+        norms, sumsq = st.pop("tensor_norms"), st.pop("tensor_sumsq")
+        st["tensor_norms"] = {names.get(id(p), "param%d" % k): norms[k] for k, p in enumerate(self.params)}
+        st["tensor_sumsq"] = sumsq
+        st["norm_mean"] = st["norm_sum"] / st["updates"] if st["updates"] else 0.0
+        st["skipped_total"] = self.skipped_before + st["skipped"]
+        if reset:
+            self.skipped_before += st["skipped"]
+            self.clip.reset_stats()
+        return st
 
     def ema(self, decay=0.999):
         ops.ema_update(self.avg, self.p, decay)
@@ -272,6 +321,7 @@ class FlatNet:
         """Clones of the parameters, both Adam moments and the EMA copy (if kept), the step count and learning rate, and
         the layout (`sizes`, `offsets`) that load_state_dict checks.  The gradient buffer is not state: every update
         zeroes it first."""
+        self.sync_step_count()
         sd = {"p": self.p.detach().clone(), "m": self.m.clone(), "v": self.v.clone(), "step_count": int(self.step_count),
               "lr": float(self.lr), "sizes": list(self.sizes), "offsets": list(self.offsets)}
         if self.avg is not None:
